@@ -12,10 +12,16 @@ catalog, seq_len 50, batch 512 per GPU (weak scaling), dense regime (every posit
 dropout 0.3, lr 5e-4, hidden 150, 2 blocks, 1 head (reference defaults main.py:98-107).
 
 The headline is the float32-grade step (`--logits x3`: every GEMM as three bf16 MFMAs on hi/lo operand splits, ~2^-16 relative
-per product, fp32 accumulate -- the reference's arithmetic is float32, ADER.py:91-93); the bf16-operand step is reported beside it
-as `value_bf16`.  The timed region is repeated `--reps` times (K steps each) and `value` is the MEDIAN repetition (min / max in
-`reps_ms`).  Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed on the launch stream inside the
-timed region; `logit_gemm`, `gather`, `herding` sub-blocks) and `cpu_baseline` (the CPU oracle timed on this host's cores).
+per product, fp32 accumulate -- the reference's arithmetic is float32, ADER.py:91-93).  The timed region is repeated `--reps` times
+(K steps each; 1 by default, so a plain run times exactly K steps) and `value` is the MEDIAN repetition (min / max in `reps_ms`);
+`ms_per_step` is the milliseconds of one timed step.  Prints ONE JSON line on rank 0.
+
+A plain run does only what that line needs: set-up, the untimed initialisation and W warm-up steps, the timed steps, and, with
+`--dump-outputs DIR`, the outputs of the last timed step (dump_outputs).  `--full` adds everything else the benchmark measures, as
+before: 5 repetitions by default, `roofline` (dominant kernel, HIP-event timed on the launch stream inside the timed region;
+`logit_gemm`, `gather`, `herding` sub-blocks), the bf16-operand step beside the headline (`value_bf16`), `sustained`,
+`cpu_baseline` (the CPU oracle timed on this host's cores), `real_shapes`, and with N > 1 the other data-parallel scheme and
+`real_shapes_dp`.
 """
 import subprocess
 import argparse
@@ -342,6 +348,38 @@ def cpu_baseline(N, B, T, H, L, heads, rate, lr, E=0, Np=0):
     return out
 
 
+DUMP_BYTES = 64 * 2 ** 20       # --dump-outputs: at most this much in all
+DUMP_TABLE_ROWS = 32768         # item-table rows drawn with a fixed seed (besides the rows the last step's batch names)
+
+
+def dump_outputs(eng, out_dir, batch, N, rank):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step -- the step's loss and the updated parameters
+    -- as float32 DIR/<name>.npy: loss.npy, one file per parameter (pos.npy, b0.wq.npy, ...).  The item table (N + 1 rows) is written
+    as a fixed sample: DUMP_TABLE_ROWS rows drawn with a fixed seed plus every row the last step's batch names, ascending, in emb.npy,
+    their row numbers in emb_rows.npy (float64); thinned with a fixed seed if that would pass DUMP_BYTES in all.  Every rank calls
+    this (a catalog-sharded table is gathered first: a collective); rank 0 writes."""
+    eng.sync_table()
+    torch.cuda.synchronize()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"loss": eng.loss.detach().float().cpu().numpy().reshape(-1)}
+    for k in eng.layout:
+        if k != "emb":
+            out[k] = eng.param(k).detach().float().cpu().numpy()
+    seq, pos = batch
+    named = np.concatenate([seq.cpu().numpy().reshape(-1), pos.cpu().numpy().reshape(-1)]).astype(np.int64)
+    drawn = np.random.RandomState(12345).choice(N + 1, min(DUMP_TABLE_ROWS, N + 1), replace=False)
+    rows = np.union1d(drawn, named)
+    room = (DUMP_BYTES - sum(a.nbytes for a in out.values()) - 64 * 1024) // (eng.H * 4 + 8)     # (64 KB: the files' headers)
+    if len(rows) > room:
+        rows = np.sort(np.random.RandomState(54321).choice(rows, room, replace=False))
+    out["emb_rows"] = rows.astype(np.float64)
+    out["emb"] = eng.param("emb")[torch.from_numpy(rows).to(eng.device)].float().cpu().numpy()
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64 if k == "emb_rows" else np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -349,7 +387,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--items", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=512)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed region (K steps each); value = median")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the timed region (K steps each); value = median (default: 1, or 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-kernel sections and roofline, the companion logits type, "
+                         "the sustained region, the gather and herding measurements, the CPU baseline, the real-data step shapes and "
+                         "(N > 1) the other data-parallel scheme.  The --no-* / --sustained-steps options below apply to it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, updated parameters; the item table "
+                         "as a fixed sample of rows) as DIR/<name>.npy, float32 (the sampled row numbers float64)")
     ap.add_argument("--logits", choices=["bf16", "x3", "f32"], default="x3",
                     help="operand type of the logit GEMMs (fp32 master table, fp32 accumulate/softmax either way)")
     ap.add_argument("--regime", choices=["dense", "realistic"], default="dense",
@@ -386,6 +432,9 @@ def main():
                     help="after the median-of-reps block: ONE more timed region of this many steps of the same kernels (~4 s), so the "
                          "line also says what a power-limited chip sustains (0 = skip)")
     args = ap.parse_args()
+    full = args.full
+    if args.reps is None:
+        args.reps = 5 if full else 1
 
     # ---- N > 1 without a launcher: start the ranks as children BEFORE anything touches the GPU (never re-exec a GPU process)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -547,14 +596,16 @@ def main():
         return dts, {**sec_all, **sec}, float(eng_.loss.item())
 
     eng = make_engine(args.logits)
-    dts, sections, loss = timed(eng, args.reps, not args.no_sections)
+    dts, sections, loss = timed(eng, args.reps, full and not args.no_sections)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, batches[(args.steps - 1) % nbatch], N, rank)
     session_tiles = "packed" if eng._act.get("pack") is not None else "one session per workgroup"
     dt = float(np.median(dts))
     value_dp_mode = eng.dp_mode if world > 1 else None
     # the other data-parallel scheme in the same invocation (north_star words the replicated one: dense all-reduce over xGMI overlapped
     # with backward; `value` is the catalog-sharded default): one repetition of the same K steps
     other_leg = None
-    if world > 1 and not args.no_other_dp_leg and args.logits == "x3" and not E:
+    if full and world > 1 and not args.no_other_dp_leg and args.logits == "x3" and not E:
         other = "replicated" if eng.dp_mode == "catalog" else "catalog"
         eng_o = make_engine(args.logits, dp_mode=other)
         dts_o, _, loss_o = timed(eng_o, 1, False)
@@ -565,7 +616,7 @@ def main():
 
     # ---- configs[3] (YOOCHOOSE ADER, global batch 512 x N) in the same multi-GPU invocation, both schemes: every rank takes part
     real_dp = None
-    if world > 1 and not args.no_real_shapes and args.workload == "cfgS" and not E and args.logits == "x3":
+    if full and world > 1 and not args.no_real_shapes and args.workload == "cfgS" and not E and args.logits == "x3":
         try:
             real_dp = {"cfgY": dp_shape_legs("cfgY", dev, rank, world, steps=max(10, min(40, args.steps)))}
         except Exception as e:          # (collectives inside: a failure on one rank is fatal for all, so it is re-raised after the note)
@@ -575,7 +626,7 @@ def main():
     # ---- sustained figure: the K-step repetitions above are ~40 ms bursts on a chip that clocks down under the logit kernels
     # (MI355X_MICROARCH.md, DVFS): one multi-second region of the SAME steps, no per-kernel events, same barrier + synchronize
     sustained = None
-    if args.sustained_steps > 0 and args.workload == "cfgS":
+    if full and args.sustained_steps > 0 and args.workload == "cfgS":
         eng.timer = None
         sync()
         t0 = time.perf_counter()
@@ -596,7 +647,7 @@ def main():
     # ---- standalone embedding gather (north_star: "rocprof HBM GB/s on the gather"): in the step it is fused into the one-launch
     # forward, so it is timed here as its own kernel on the same batch (ader_embed_fwd: ids -> x0 = drop(E[ids]*sqrt(H) + P) * mask)
     gather = None
-    if rank == 0 and not args.no_sections:
+    if full and rank == 0 and not args.no_sections:
         import ctypes
         from ader_amd._lib import AderDrop, call, ptr
         seq0 = batches[0][0][:B].contiguous()
@@ -654,7 +705,7 @@ def main():
 
     # ---- companion run of the other logits type (bf16 operands beside the float32-grade headline, or the reverse)
     comp, comp_name = None, {"x3": "bf16", "bf16": "x3"}.get(args.logits)
-    if world == 1 and comp_name and not args.no_companion and not E:
+    if full and world == 1 and comp_name and not args.no_companion and not E:
         del eng
         torch.cuda.empty_cache()
         engc = make_engine(comp_name)
@@ -695,10 +746,10 @@ def main():
         pmc, sq, pmc_src = {}, {}, None
         std = N == 1_000_000 and B == 512 and not E and world == 1 and args.regime == "dense"
         try:
-            if args.pmc_json:
+            if full and args.pmc_json:
                 pmc = json.load(open(args.pmc_json))["kernels"]
                 pmc_src = {"file": os.path.relpath(os.path.abspath(args.pmc_json), ROOT), "stale": False}
-            elif std:
+            elif full and std:
                 cur = json.load(open(os.path.join(ROOT, "profiles", "CURRENT.json")))
                 tag = cur[args.logits]
                 stale = cur.get("src_sha16") != csrc_sha16()
@@ -796,13 +847,13 @@ def main():
                                     "unpack the exchanged rows); the dense all-reduce overlaps the blocks backward",
                     "exchange_bytes_per_step": int(rb)}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:      # the CPU baseline is a rank-0, N = 1 leg only
+        if full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is a rank-0, N = 1 leg only
             try:
                 cpu = cpu_baseline(N, B, T, H, L, heads, rate, lr, E, int(0.9 * N) if E else 0)
             except Exception as e:  # report, never fake
                 cpu = {"value": None, "unit": "sessions/s", "cores": os.cpu_count(), "kind": "port", "sample": "failed: %r" % (e,)}
         herd = None
-        if world == 1 and not args.no_herding and args.workload == "cfgS" and not E:
+        if full and world == 1 and not args.no_herding and args.workload == "cfgS" and not E:
             try:        # exemplar selection of YOOCHOOSE period 1 (groups up to 1,710 rows, SURVEY 8d "Herding measurement")
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
                 import contextlib
@@ -815,7 +866,7 @@ def main():
         if roof is not None:
             roof["herding"] = herd
         real = None
-        if world == 1 and not args.no_real_shapes and args.workload == "cfgS" and not E and args.regime == "dense":
+        if full and world == 1 and not args.no_real_shapes and args.workload == "cfgS" and not E and args.regime == "dense":
             # the workloads the reference trains on (BASELINE.json configs[1], [2]) on the driver-run line, after everything else
             real = {}
             for nm in list(REAL_SHAPES) + ["ader128"]:

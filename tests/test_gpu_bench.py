@@ -1,10 +1,12 @@
-"""bench.py contract checks on the GPU box: the N = 1 line carries the roofline / reps blocks, and `--gpus 2` starts its own ranks
+"""bench.py contract checks on the GPU box: a plain line times exactly K steps and carries nothing else, `--dump-outputs` writes the
+same files from run to run, the `--full` N = 1 line carries the roofline / reps blocks, and `--full --gpus 2` starts its own ranks
 (two ranks share cuda:0 with ADER_DIST_BACKEND=gloo: the 8-GPU run is the driver's) in both data-parallel modes."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,8 +28,33 @@ def _run(args, env=None):
     return out
 
 
+def test_plain_line_times_k_steps_and_dumps_the_same_outputs(tmp_path):
+    args = ["--steps", "5", "--warmup", "2", "--items", "30000"]
+    runs = []
+    for name in ("a", "b"):
+        d = _run(args + ["--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == 5 and d["reps"] == 1 and d["unit"] == "sessions/s" and d["higher_is_better"] is True
+        assert d["dtype"].startswith("bf16x3") and d["ms_per_step"] > 0
+        assert abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert abs(d["reps_ms"]["all"][0] - d["ms_per_step"]) < 1e-3
+        for k in ("roofline", "cpu_baseline", "sustained", "companion", "real_shapes", "value_bf16"):
+            assert d[k] is None, k
+        runs.append(d)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "emb.npy", "emb_rows.npy", "pos.npy", "b0.wq.npy", "lnf_g.npy"} <= set(files)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 2 ** 20
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), f
+        assert np.array_equal(x, y), f
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == pytest.approx(runs[0]["config"]["final_loss"], rel=1e-6)
+    emb, rows = np.load(tmp_path / "a" / "emb.npy"), np.load(tmp_path / "a" / "emb_rows.npy")
+    assert emb.shape == (len(rows), 150) and rows.max() <= 30000 and (np.diff(rows) > 0).all()
+
+
 def test_single_gpu_line_has_the_contract_fields():
-    d = _run(["--steps", "3", "--warmup", "3", "--reps", "3", "--items", "30000", "--no-cpu-baseline", "--no-herding",
+    d = _run(["--full", "--steps", "3", "--warmup", "3", "--reps", "3", "--items", "30000", "--no-cpu-baseline", "--no-herding",
               "--sustained-steps", "40"])
     assert d["n_gpus"] == 1 and d["dtype"].startswith("bf16x3") and d["unit"] == "sessions/s" and d["scaling"] == "weak"
     assert d["reps"] == 3 and d["reps_ms"]["min"] <= d["reps_ms"]["median"] <= d["reps_ms"]["max"]
@@ -54,8 +81,8 @@ def test_single_gpu_line_has_the_contract_fields():
 
 @pytest.mark.parametrize("mode", ["catalog", "replicated"])
 def test_gpus_2_starts_its_own_ranks(mode):
-    d = _run(["--gpus", "2", "--steps", "2", "--warmup", "2", "--reps", "1", "--items", "20000", "--no-cpu-baseline", "--dp-mode", mode,
-              "--sustained-steps", "0"],
+    d = _run(["--full", "--gpus", "2", "--steps", "2", "--warmup", "2", "--reps", "1", "--items", "20000", "--no-cpu-baseline",
+              "--dp-mode", mode, "--sustained-steps", "0"],
              env={"ADER_DIST_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["config"]["rccl_ranks"] == 2 and d["config"]["global_batch"] == 1024
     assert d["comm"]["exchange_bytes_per_step"] > 0 and d["comm"]["comm_ms"] >= 0

@@ -6,7 +6,7 @@ shift || true
 EXTRA="$@"
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
-python3 bench.py --steps 40 --warmup 5 $EXTRA > $OUT/bench.json 2> $OUT/bench.err || true
+python3 bench.py --full --steps 40 --warmup 5 $EXTRA > $OUT/bench.json 2> $OUT/bench.err || true
 cd /tmp && export TMPDIR=/tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-sections --no-companion --no-herding --no-real-shapes --sustained-steps 0 $EXTRA"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o k -- $B --steps 20 --warmup 3 > $OUT/stats.log 2>&1
