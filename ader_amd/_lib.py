@@ -80,7 +80,6 @@ _SIGS = {
     "ader_host_prefix_rows": [P, P, L, I, P, P],
     "ader_host_pack_rows_at": [P, L, P, P, L, I, P, P],
     "ader_x3_rep_image_bytes": [I],
-    "ader_x3_update_pair_min_tiles": [I],
     "ader_x3_rep_image": [P, P, I, P, P],
     "ader_tab_update_x3": [P, P, P, I, I, I, I, I, P, P, P, I, P, F, P, P, I, P, P, P, P, P, F, F, F, F, I, I, P, P],
     "ader_tab_update_x3_kd": [P, P, P, I, I, I, I, I, I, P, P, P, I, P, F, P, P, I, P, P, P, L, P, P, P, P, P, F, F, F, F, P],
@@ -123,8 +122,7 @@ _SIGS = {
 }
 # cross-check kernels of the tests (libader_xcheck.so, built with -DADER_XCHECK): not in the product library
 _XSIGS = {
-    "ader_tab_update": [P, P, P, I, I, I, I, I, P, P, P, I, P, F, P, P, I, P, P, P, P, P, F, F, F, F, I, I, P, P],
-    "ader_tab_update_kd": [P, P, I, I, I, I, I, I, P, P, P, I, P, F, P, P, I, P, P, P, L, P, P, P, P, P, F, F, F, F, P],
+    "ader_tab_update": [P, P, I, I, I, I, I, P, P, P, I, P, F, P, P, I, P, P, P, P, P, F, F, F, F, I, I, P, P],
     "ader_herding_select_generic": [P, P, P, P, I, L, I, P, P, P, P, P, P],
 }
 SEQ_MAXL = 4
@@ -192,7 +190,7 @@ class AderStepKey(ctypes.Structure):
     _fields_ = [("blob", c_int), ("site", c_int), ("offset", c_size_t)]
 
 
-_NO_CHECK = {"ader_step_fn_index", "ader_step_fn_args", "ader_step_plan_failed_op", "ader_ln_bwd_slabs", "ader_gemm_atb_batch_slabs", "ader_gemm_atb_slabs", "ader_logits_sub", "ader_logits_parts", "ader_logits_ranges", "ader_lbf_ranges", "ader_lbf_ranges_kd", "ader_lbf_readout_ranges", "ader_lx3_readout_ranges", "ader_wprep_elems", "ader_fused_bucket_gran", "ader_fused_bucket_id0", "ader_tab_meta_ints", "ader_x3_rep_image_bytes", "ader_x3_update_pair_min_tiles", "ader_sparse_lists_scratch_n", "ader_sparse_lists_starts"}
+_NO_CHECK = {"ader_step_fn_index", "ader_step_fn_args", "ader_step_plan_failed_op", "ader_ln_bwd_slabs", "ader_gemm_atb_batch_slabs", "ader_gemm_atb_slabs", "ader_logits_sub", "ader_logits_parts", "ader_logits_ranges", "ader_lbf_ranges", "ader_lbf_ranges_kd", "ader_lbf_readout_ranges", "ader_lx3_readout_ranges", "ader_wprep_elems", "ader_fused_bucket_gran", "ader_fused_bucket_id0", "ader_tab_meta_ints", "ader_x3_rep_image_bytes", "ader_sparse_lists_scratch_n", "ader_sparse_lists_starts"}
 
 
 class AderHipError(RuntimeError):

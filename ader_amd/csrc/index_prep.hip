@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void k_ip_rank(const int* __restrict__ ids0, i
 // 1,024-thread workgroup, counters and offsets in LDS, the phases of the kernels above separated by workgroup barriers (its global
 // writes -- tmp, tmp_id, the lists -- are read back by the same workgroup only), and the per-tile records of the update kernels
 // (k_tile_meta's: {k0, k1, first 8 (id, row)} per list) written at the end.  Same lists bit for bit: the rank fixes every slot.
-// Five launches and a memset fewer per step where the host, not the GPU, sets the pace.
+// Five launches and a memset fewer per step where the host, not the GPU, sets the pace (NOTEBOOK.md).
 #define IP1_T 1024
 __global__ __launch_bounds__(IP1_T) void k_ip_one(const int* __restrict__ ids0, int n0, const int* __restrict__ ids1, int n1, int gran,
                                                   int nkeys, int* __restrict__ tmp, int* __restrict__ tmp_id, int* __restrict__ sid0,

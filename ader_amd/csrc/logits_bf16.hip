@@ -27,7 +27,6 @@
 //
 // LDS tiles are row-major bf16 with a 168-element (336 B) row stride: ds_read_b128 operand reads are conflict-free
 // (20 r mod 64 covers 16 distinct 4-bank slots).  gfx950 only.
-#include <stdlib.h>
 #include "lbf_common.h"
 #include "x3_image.h"
 #include "../../include/ader_hip.h"
@@ -578,7 +577,7 @@ __global__ __launch_bounds__(256) void k_lx3_prep(const float* __restrict__ rep,
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Bp * LDR) return;
     const int b = i / LDR, c = i - b * LDR;
-    const float x = ((b < B && c < H) ? rep[(size_t)b * H + c] : 0.0f) * X3_SR;      // (X3_SR = 1 in the product build)
+    const float x = (b < B && c < H) ? rep[(size_t)b * H + c] : 0.0f;
     const bf16 h = (bf16)x, l = (bf16)(x - (float)h);
     rep_hi[i] = h;
     rep_lo[i] = l;
@@ -690,12 +689,7 @@ __global__ __launch_bounds__(256, OCC) void k_lx3_fwd(Lx3Args a) {
         float tc[16], tn[16];
 #pragma unroll
         for (int s_ = 0; s_ < XRD; ++s_) if (s_ < nb_blocks) LX3_LOAD(s_, blk_begin + s_);
-#if defined(LX3RO_KO) && LX3RO_KO == 1
-#define RO_TLOAD(t_, blk_) { _Pragma("unroll") for (int j_ = 0; j_ < 16; ++j_) t_[j_] = -3.0f; }
-#else
-#define RO_TLOAD(t_, blk_) LBF_TLOAD(t_, blk_)
-#endif
-        if (nb_blocks > 0) RO_TLOAD(tc, blk_begin);
+        if (nb_blocks > 0) LBF_TLOAD(tc, blk_begin);
         __syncthreads();
         int cur = 0, i = 0;
         while (i < nb_blocks) {
@@ -705,10 +699,8 @@ __global__ __launch_bounds__(256, OCC) void k_lx3_fwd(Lx3Args a) {
                 const int blk = blk_begin + i;
                 const int i0 = blk * FB;
                 LX3_STORE(s_, cur);
-#if !(defined(LX3RO_KO) && LX3RO_KO == 2)
                 if (i + XRD < nb_blocks) LX3_LOAD(s_, blk + XRD);
-#endif
-                if (i + 1 < nb_blocks) { RO_TLOAD(tn, blk + 1); }
+                if (i + 1 < nb_blocks) { LBF_TLOAD(tn, blk + 1); }
                 __syncthreads();
                 const bf16* Eh = E_l + cur * 2 * FB * LDR;
                 f32x16 S;
@@ -721,9 +713,6 @@ __global__ __launch_bounds__(256, OCC) void k_lx3_fwd(Lx3Args a) {
                 bf16x8 pl0, pl1;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { pl0[j] = (bf16)(S[j] - (float)pa0[j]); pl1[j] = (bf16)(S[8 + j] - (float)pa1[j]); }
-#if defined(LX3RO_KO) && LX3RO_KO == 3
-                if (a.H == 1)
-#endif
 #pragma unroll
                 for (int nb = 0; nb < 5; ++nb) {
                     const bf16* base = Eh + (4 * hh + q4) * LDR + 32 * nb + 16 * g1 + 4 * p4;
@@ -853,33 +842,15 @@ __global__ __launch_bounds__(256, OCC) void k_lx3_fwd(Lx3Args a) {
     }
 }
 
-// the x3 forwards of logits_x3.hip on conflict-free block images: k_lx3g (32x32x16, any supported H), k_lx3p (the same with the
-// vector work inside the MFMA phases; H = 150: the default) and the teacher readout of distilled steps k_lx3r
+// the x3 forwards of logits_x3.hip on conflict-free block images: k_lx3p (k_lx3g, 32x32x16, with the vector work inside the MFMA
+// phases; it launches k_lx3g itself for H != 150) and the teacher readout of distilled steps k_lx3r
 bool lx3f_supports(int H);
-int lx3g_launch(const Lx3Args& x, void* stream);
 int lx3p_launch(const Lx3Args& x, void* stream);
 // lx3r_supports: H = 150, 16-byte aligned teacher rows, at least one whole block
 bool lx3r_supports(const Lx3Args& x);
 int lx3r_launch(const Lx3Args& x, void* stream);
-// ADER_X3_FWD = old | g | p: the round-2 kernel (k_lx3_fwd), k_lx3g, or k_lx3p (default; falls back to k_lx3g for H != 150)
-// (read only by diagnostic builds, -DADER_DIAG: a production build takes no kernel choice from the environment)
-static int lx3_env() {
-#ifdef ADER_DIAG
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ADER_X3_FWD"); v = !e ? 4 : (e[0] == 'o' ? 0 : (e[0] == 'g' ? 2 : 4)); }
-    return v;
-#else
-    return 4;
-#endif
-}
 // 2: the block-image kernels (Bp % 128 == 0 and a supported H), 0: k_lx3_fwd
-static int lx3_kind(int H, int Bp) {
-    if (!lx3f_supports(H)) return 0;
-    return (lx3_env() >= 2 && Bp % 128 == 0) ? 2 : 0;
-}
-static int lx3gh_launch(const Lx3Args& x, void* stream) {
-    return lx3_env() == 4 ? lx3p_launch(x, stream) : lx3g_launch(x, stream);
-}
+static int lx3_kind(int H, int Bp) { return lx3f_supports(H) && Bp % 128 == 0 ? 2 : 0; }
 
 // ============================================================================================= C ABI
 static const size_t kFwdLds = (size_t)2 * FB * LDR * sizeof(bf16);
@@ -1110,7 +1081,7 @@ int ader_lx3_fwd_img_lnf(const float* rep, const float* emb, int item_num, int B
     a.sh1 = nullptr; a.vrows = item_num; a.tile_off = 0; a.rep_bf = (const bf16*)rep_hi; a.B = B; a.Bp = Bp; a.H = H; a.N = N;
     a.ranges = x.ranges; a.pm = pm; a.pl = pl; a.pO = pO; a.off = nullptr; a.demb1 = nullptr; lbf_no_kd(a);
     hipLaunchKernelGGL(k_lx3_prep, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_hi, (bf16*)rep_lo, B, Bp, H, (char*)rep_img);
-    if (nk) { rc = lx3gh_launch(x, stream); if (rc) return rc; }
+    if (nk) { rc = lx3p_launch(x, stream); if (rc) return rc; }
     else hipLaunchKernelGGL((k_lx3_fwd<2, 2>), dim3(x.ranges * (Bp / 128)), dim3(256), lds, st, x);
     hipLaunchKernelGGL(k_lbf_combine<true>, dim3(Bp), dim3(640), 0, st, a, lab, wrow, lse, off, rowloss, drep, emb + H, rep,
                        lnf ? *lnf : AderLnfBwd{});
@@ -1172,7 +1143,7 @@ int ader_lx3_fwd_kd_lnf(const float* rep, const float* emb, int item_num, int n_
     a.pO2 = pO2; a.ranges2 = x.ranges2;
     hipLaunchKernelGGL(k_lbf_prep_kd, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_hi, (bf16*)rep_lo, n_train, n_ex,
                        kd_row0, Bp, H, pos, ex_trow, tlse_all, w_train, w_ex, lab, wrow, trow, tlse2, (char*)rep_img);
-    if (nk) { rc = lx3gh_launch(x, stream); if (rc) return rc; }
+    if (nk) { rc = lx3p_launch(x, stream); if (rc) return rc; }
     else hipLaunchKernelGGL((k_lx3_fwd<2, 2>), dim3(x.ranges * (Bp / 128)), dim3(256), lds, st, x);
     if (lx3r_supports(x)) { rc = lx3r_launch(x, stream); if (rc) return rc; }
     else hipLaunchKernelGGL((k_lx3_fwd<2, 2, true>), dim3(x.ranges2 * ((Bp - kd_row0) / 128)), dim3(256), lds, st, x);
@@ -1205,7 +1176,7 @@ int ader_lx3_fwd_shard(const void* rep_hi, const void* rep_lo, const float* emb,
     a.ranges = x.ranges; a.pm = pm; a.pl = pl; a.pO = pO; a.off = nullptr; a.demb1 = nullptr; lbf_no_kd(a);
     if (x.ranges > 0) {
         int rc = 0;
-        if (lx3_kind(H, Bp) == 2) rc = lx3gh_launch(x, stream);
+        if (lx3_kind(H, Bp) == 2) rc = lx3p_launch(x, stream);
         else {
             rc = lx3_attr();
             if (!rc) hipLaunchKernelGGL((k_lx3_fwd<2, 2>), dim3(x.ranges * (Bp / 128)), dim3(256), (size_t)2 * 2 * FB * LDR * sizeof(bf16), st, x);

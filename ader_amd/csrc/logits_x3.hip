@@ -11,7 +11,7 @@
 //   k_lx3p  k_lx3g with the softmax / staging vector work issued inside the MFMA phases (H = 150: the default forward)
 //   k_lx3r  the teacher readout of distilled steps (ADER.py:132-137) on the same images
 // (k_lx3f, 16 rows per wave on 16x16x32 tiles, and k_lx3h, k_lx3g's blocking on 16x16x32 tiles, were measured 25 % and 4 % slower in
-// round 3 -- DESIGN.md 6a -- and removed in round 4.)
+// round 3 -- NOTEBOOK.md -- and removed in round 4.)
 // Output partials (pm, pl, pO per item range) and the merge (k_lbf_combine<true>) are those of k_lx3_fwd.  gfx950 only.
 #include "lbf_common.h"
 #include "x3_image.h"
@@ -29,14 +29,6 @@ struct __attribute__((packed, aligned(8))) F3Vec { f32x4_t v; };      // 16-byte
 // feeds twice the flops of a 16x16x32 form with 16-row waves, which keeps the LDS pipe as busy as the matrix pipe.
 // Register plan (<= 256): rep fragments 80, O 80, S / P 16, one block in flight 24, operand sets 16 / 32.
 #define G3_ROWS 128
-#ifdef G3_STAMP     // diagnostic build only (tools/build_variant.sh ... -DG3_STAMP): per-segment clocks of wave 0 of every workgroup
-__device__ unsigned long long g3_dbg[8 * 1024];
-#define STAMP(k_) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                    __builtin_amdgcn_sched_barrier(0); seg[k_] += t_ - tprev; tprev = t_; }
-extern "C" int ader_dbg_read(void* dst, int n) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g3_dbg), (size_t)n * 8); }
-#else
-#define STAMP(k_)
-#endif
 template <int HT>
 __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [2 buffers][block image]
@@ -102,8 +94,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
         _Pragma("unroll") for (int r = 0; r < 5; ++r) {                                                   \
             const int p_ = qb + 8 * r;                          /* piece 37 = channels 148, 149 and two floats of the next row */ \
             float x_[4];                                        /* pieces 38, 39 = channels 152..159: zeros (no branch) */ \
-            x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[r][0]; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[r][1]; \
-            x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[r][2]; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[r][3]; \
+            x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[r][0]; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[r][1];                  \
+            x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[r][2]; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[r][3];                  \
             bf16x4 h_, l_;                                                                                \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) { h_[j] = (bf16)x_[j]; l_[j] = (bf16)(x_[j] - (float)h_[j]); } \
             *(bf16x4*)(dst_ + dstb + 4 * X3B_KC * r) = h_;                                                \
@@ -161,17 +153,10 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
     if (nb_blocks > 0) G3_STOREBLK(0);
     if (nb_blocks > 1) { G3_LOADBLK(blk_begin + 1); G3_STOREBLK(1); }
     int bcur = 0;                                          // i % 3
-#ifdef G3_STAMP
-    unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev) :: "memory");
-#endif
     for (int i = 0; i < nb_blocks; ++i) {
-        STAMP(0)
         __syncthreads();                                   // blocks i and i + 1 are in LDS; every wave is done with block i - 1
-        STAMP(1)
         const bool more = i + 2 < nb_blocks;
         if (more) G3_LOADBLK(blk_begin + i + 2);
-        STAMP(2)
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
         const int bnew = bcur == 0 ? 2 : bcur - 1;         // (i + 2) % 3
         const int i0 = (blk_begin + i) * F3_FB;
@@ -199,10 +184,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
             if (ks + 2 < 10) G3_LOADA(fa[ks & 1], ks + 2);
             __builtin_amdgcn_sched_barrier(0);
         }
-        STAMP(3)
         if (more) G3_STOREBLK(bnew);
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(4)
         // the first transposed reads of the readout do not depend on S: in flight under the softmax section
         bf16x4 ft[3][4];        // half sets: {items 4hh.., 8 + 4hh.., 16 + 4hh.., 24 + 4hh..} of ONE plane; hi, lo, hi, lo ...
         G3_LOADT(ft[0], 0, 0);
@@ -242,7 +225,6 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) { pl0[j] = (bf16)(S[j] - (float)pa0[j]); pl1[j] = (bf16)(S[8 + j] - (float)pa1[j]); }
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(5)
 #pragma unroll
         for (int hs = 0; hs < 10; ++hs) {                        // half step: (channel block nb = hs >> 1, plane hs & 1)
             bf16x4* T_ = ft[hs % 3];
@@ -262,11 +244,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
             __builtin_amdgcn_sched_barrier(0);
         }
         bcur = bcur == 2 ? 0 : bcur + 1;
-        STAMP(6)
     }
-#ifdef G3_STAMP
-    if (tid == 0 && blockIdx.x < 1024) { for (int k_ = 0; k_ < 8; ++k_) g3_dbg[blockIdx.x * 8 + k_] = seg[k_]; g3_dbg[blockIdx.x * 8 + 7] = nb_blocks; }
-#endif
 #undef G3_LOADA
 #undef G3_LOADT
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -282,16 +260,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// k_lx3p: k_lx3g with the softmax of block i issued INSIDE the S phase of block i + 1.  Stamps of k_lx3g: a wave
+// k_lx3p: k_lx3g with the softmax of block i issued INSIDE the S phase of block i + 1.  Stamps of k_lx3g (NOTEBOOK.md): a wave
 // spends 2,400 of a block's 5,300 clocks in vector-only phases (staging, softmax) and the two waves of a SIMD mostly take turns --
 // the kernel is bound by the waves' serial chains, not by the matrix pipe (68 % busy).  Here the logits of the NEXT block are
 // accumulated (a second S, 16 registers) while the exp / sum / hi-lo split of the current block's logits are placed between its
 // MFMAs; the rescale test (a branch) stays in front.  Same arithmetic in the same order as k_lx3g: bit-equal results.
 template <int HT>
 __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
-    // (product build: LOG2E_S = LOG2E and the two factors are 1: the compiler folds them; -DADER_X3_F16: see lbf_common.h)
-    constexpr float LOG2E_S = LOG2E / (X3_SR * X3_SE);
-    constexpr float X3_INV_P = 1.0f / (X3_SPL == 0.0f ? 1.0f : 256.0f), X3_INV_PE = X3_INV_P / X3_SE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [2 buffers][block image]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -355,8 +330,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
         _Pragma("unroll") for (int r = 0; r < 5; ++r) {                                                   \
             const int p_ = qb + 8 * r;                          /* piece 37 = channels 148, 149 and two floats of the next row */ \
             float x_[4];                                        /* pieces 38, 39 = channels 152..159: zeros (no branch) */ \
-            x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[r][0] * X3_SE; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[r][1] * X3_SE; \
-            x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[r][2] * X3_SE; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[r][3] * X3_SE; \
+            x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[r][0]; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[r][1];                  \
+            x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[r][2]; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[r][3];                  \
             bf16x4 h_, l_;                                                                                \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) { h_[j] = (bf16)x_[j]; l_[j] = (bf16)(x_[j] - (float)h_[j]); } \
             *(bf16x4*)(dst_ + dstb + 4 * X3B_KC * r) = h_;                                                \
@@ -424,8 +399,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
     // softmax of ONE pair of logits of the current block (elements 2 q_, 2 q_ + 1 of S): p = exp2(s log2e - m), running sum in
     // element order (the order of k_lx3g: bit-equal results), hi / lo split into packed pairs
 #define P3_PAIR(q_)                                                                                       \
-    { const float p0_ = __builtin_amdgcn_exp2f(fmaf(S[2 * (q_)], LOG2E_S, nm));                             \
-      const float p1_ = __builtin_amdgcn_exp2f(fmaf(S[2 * (q_) + 1], LOG2E_S, nm));                         \
+    { const float p0_ = __builtin_amdgcn_exp2f(fmaf(S[2 * (q_)], LOG2E, nm));                             \
+      const float p1_ = __builtin_amdgcn_exp2f(fmaf(S[2 * (q_) + 1], LOG2E, nm));                         \
       ls += p0_; ls += p1_;                                                                               \
       bf16x2 h_; h_[0] = (bf16)p0_; h_[1] = (bf16)p1_;                                                    \
       bf16x2 l_; l_[0] = (bf16)(p0_ - (float)h_[0]); l_[1] = (bf16)(p1_ - (float)h_[1]);                  \
@@ -459,7 +434,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
         }                                                                                                 \
         float tmax = S[0];                                                                                \
         _Pragma("unroll") for (int j = 1; j < 16; ++j) tmax = fmaxf(tmax, S[j]);                          \
-        float t2 = tmax * LOG2E_S;                                                                          \
+        float t2 = tmax * LOG2E;                                                                          \
         if (__any(t2 > m_run + RESCALE_THR)) {                                                            \
             t2 = fmaxf(t2, __shfl_xor(t2, 32, 64));                                                       \
             const float m_new = (t2 > m_run + RESCALE_THR) ? t2 : m_run;                                  \
@@ -471,7 +446,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
                 _Pragma("unroll") for (int nb = 0; nb < 5; ++nb) O[nb][j] *= ar;                          \
             }                                                                                             \
         }                                                                                                 \
-        const float nm = (X3_SPL == 0.0f) ? -m_run : X3_SPL - m_run;     /* (product build: -m_run) */            \
+        const float nm = -m_run;                                                                          \
         float ls = 0.0f;                                                                                  \
         uint32_t ph2[8], pl2[8];                           /* P hi / lo as packed bf16 pairs */
     // ... and behind it: the block in flight goes to LDS, then the readout O += P^T . E of the current block
@@ -537,8 +512,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
             Sn = mfma_bf16(A_[1], rh[ks], Sn);
             __builtin_amdgcn_sched_barrier(0);
             if (ks < 8) {                                   // exp of pair ks
-                S[2 * ks] = __builtin_amdgcn_exp2f(fmaf(S[2 * ks], LOG2E_S, nm));
-                S[2 * ks + 1] = __builtin_amdgcn_exp2f(fmaf(S[2 * ks + 1], LOG2E_S, nm));
+                S[2 * ks] = __builtin_amdgcn_exp2f(fmaf(S[2 * ks], LOG2E, nm));
+                S[2 * ks + 1] = __builtin_amdgcn_exp2f(fmaf(S[2 * ks + 1], LOG2E, nm));
             }
             __builtin_amdgcn_sched_barrier(0);
             Sn = mfma_bf16(A_[0], rl[ks], Sn);
@@ -591,8 +566,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
                 O[r] = mfma_bf16(pl0, v0, O[r]);
                 __builtin_amdgcn_sched_barrier(0);
                 {   const int p_ = qb + 8 * r;                  // pieces 38, 39 = channels 152..159: zeros (no branch)
-                    x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[r][0] * X3_SE; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[r][1] * X3_SE;
-                    x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[r][2] * X3_SE; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[r][3] * X3_SE;
+                    x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[r][0]; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[r][1];
+                    x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[r][2]; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[r][3];
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 O[r] = mfma_bf16(pl1, v1, O[r]);
@@ -671,13 +646,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     if (hh == 0) {
         a.pm[(size_t)range * a.Bp + b0 + r32] = m_run;
-        a.pl[(size_t)range * a.Bp + b0 + r32] = l_tot * X3_INV_P;
+        a.pl[(size_t)range * a.Bp + b0 + r32] = l_tot;
     }
     float* o = a.pO + ((size_t)range * a.Bp + b0) * HP;
 #pragma unroll
     for (int nb = 0; nb < 5; ++nb)
 #pragma unroll
-        for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r32] = O[nb][j] * X3_INV_PE;
+        for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r32] = O[nb][j];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -17,24 +17,6 @@
 // heads == 1, T <= 64, H even and <= 150.  gfx950 only.
 #include "seqp_common.h"
 
-#ifdef SFP_STAMP     // diagnostic build only (tools/build_variant.sh ... -DSFP_STAMP): clocks per phase of waves 0 and 4 of each workgroup
-__device__ unsigned long long sfp_dbg[2 * 40 * 1024];
-#define SFS_INIT unsigned long long seg[40], tprev; for (int i_ = 0; i_ < 40; ++i_) seg[i_] = 0; \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev) :: "memory");
-#define SFS(k_) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                  __builtin_amdgcn_sched_barrier(0); seg[k_] += t_ - tprev; tprev = t_; }
-#define SFB(k_) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                  __builtin_amdgcn_sched_barrier(0); if (l == 0) seg[1 + k_] += t_ - tprev; else seg[17 + k_] += t_ - tprev; tprev = t_; }
-#define SFS_DUMP { if (lane == 0 && (wave == 0 || wave == 4) && blockIdx.x < 1024) for (int k_ = 0; k_ < 40; ++k_) \
-                       sfp_dbg[(blockIdx.x * 2 + (wave == 4)) * 40 + k_] = seg[k_]; }
-extern "C" int ader_dbg_read_sfp(void* dst, int n) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sfp_dbg), (size_t)n * 8); }
-#else
-#define SFS_INIT
-#define SFS(k_)
-#define SFB(k_)
-#define SFS_DUMP {}
-#endif
-
 struct SeqpCtx {
     bf16 *R0, *R1, *R2;
     float *km_l, *qm_l, *red_l;
@@ -42,10 +24,6 @@ struct SeqpCtx {
     uint32_t *gph_l, *gpt_l;
     int nrows, nrb;
     size_t prow0;
-#ifdef SFP_STAMP
-    unsigned long long* seg;
-    unsigned long long* tprev;
-#endif
 };
 
 // The blocks of the stack on one tile.  SMALL: the 16-column mapping of tiles with at most 32 rows; otherwise the 32x32 mapping of k_seq_fwd.
@@ -65,10 +43,6 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
     const bool skipw = mh == 1 && nrows <= 32;        // this wave's 32 rows hold no position (32x32 mapping)
     const int npass = nrows > 40 ? 2 : 1;             // row-layout phases: rows 40 pass + 4 wave + rsub
     (void)tp_l; (void)gpt_l; (void)red_l; (void)nrb; (void)skipw; (void)T;
-#ifdef SFP_STAMP
-    unsigned long long* seg = cx.seg;
-    unsigned long long& tprev = *cx.tprev;
-#endif
     typedef const AderSeqBlock __attribute__((address_space(4))) * BlkPtr;
     const BlkPtr blks = (BlkPtr)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() +
                                  offsetof(AderSeqFwd, blk));
@@ -145,9 +119,7 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
             }
             if (npass == 1 && tid < TR - 40) { km_l[40 + tid] = 0.0f; qm_l[40 + tid] = 0.0f; }
         }
-        SFB(0)
         lds_barrier();
-        SFB(1)
         float g2[10], be2[10];                  // LayerNorm 2 parameters: requested after the V phase, consumed after the attention
         if (SMALL) {
             // ======== tiles of at most 32 rows: ten waves x 16 output columns on v_mfma_f32_16x16x32_bf16 (header comment) ========
@@ -342,7 +314,6 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
             PHASE_IDS;
             f32x16 acc = tile_mma(R1, mh, r, hh, bh, bl, skipw);
             load_bfrags((const bf16*)k.w[1], nb, r, hh, bh, bl);
-            SFB(2)
             const Out o = make_rows(k.Q, mrow0, mrows, H);
             const int t0 = 32 * mh + 4 * hh;
             const uint32_t n4 = (n < H) ? (uint32_t)n * 4u : OOBH;
@@ -357,13 +328,11 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
                 }
             }
         }
-        SFB(3)
         // ---- K = x.Wk + bk (modules.py:173) -> memory, hi/lo -> R2 (the fp32 tile is dead)
         {
             PHASE_IDS;
             f32x16 acc = tile_mma(R0, mh, r, hh, bh, bl, skipw);
             load_bfrags((const bf16*)k.w[2], nb, r, hh, bh, bl);
-            SFB(4)
             const Out o = make_rows(k.K, prow0, nrows, H);
             const int t0 = 32 * mh + 4 * hh;
             const uint32_t boff0 = (n < H) ? (uint32_t)(t0 * H + n) * 4u : OOB;
@@ -377,12 +346,10 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
                 }
             }
         }
-        SFB(5)
         // ---- V = x.Wv + bv (modules.py:174) -> memory, hi/lo -> R0 (in place)
         {
             PHASE_IDS;
             f32x16 acc = tile_mma(R0, mh, r, hh, bh, bl, skipw);
-            SFB(6)
             const Out o = make_rows(k.V, prow0, nrows, H);
             const int t0 = 32 * mh + 4 * hh;
             const uint32_t boff0 = (n < H) ? (uint32_t)(t0 * H + n) * 4u : OOB;
@@ -397,9 +364,7 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
                 }
             }
         }
-        SFB(7)
         __syncthreads();        // full barrier: LN(x) rows written to memory by other waves are re-read after the attention
-        SFB(8)
         // ---- attention (modules.py:177-223), block-diagonal over the sessions of the tile.  Wave (mq, kb) of the first four owns
         //      the 32x32 block S^T[keys 32kb..][queries 32mq..]; block (0, 1) is above the diagonal: nothing to do.
         float qres[16];
@@ -412,7 +377,6 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
 #pragma unroll
             for (int j = 0; j < 16; ++j) qres[j] = bload(oq, row_base(pruned, t0 + ROWJ(j), H4, info_l) + n4);    // residual rows, added after P.V
         }
-        SFB(9)
         bf16* Ph = R1;                                   // [64 queries][LDP] hi, then lo: overlays the Q tile once S is done
         bf16* Pl = R1 + TR * LDP;
         {
@@ -498,12 +462,10 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
                 }
             }
         }
-        SFB(10)
         lds_barrier();
         {
             PHASE_IDS;
             f32x16 O;
-            SFB(11)
 #pragma unroll
             for (int j = 0; j < 16; ++j) O[j] = 0.0f;
             const int q4 = (lane_p & 15) >> 2, p4 = lane_p & 3, g1_ = (lane_p >> 4) & 1;
@@ -538,7 +500,6 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
             }
         }
         }
-        SFB(12)
         lds_barrier();
         // ---- LN2 (ADER.py:75): y -> memory, Xf (fp32, the FFN residual) and hi/lo -> R0
         {
@@ -583,7 +544,6 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
                 }
             }
         }
-        SFB(13)
         lds_barrier();
         if (SMALL) {
             const int lane_s = opaque(lane);
@@ -661,7 +621,6 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
             } else if (thr) { F1_EPI(true) } else { F1_EPI(false) }
 #undef F1_EPI
         }
-        SFB(14)
         lds_barrier();
         // ---- x2 = (dropout(h1.W2 + b2) + y) * (id != 0) (modules.py:258-266, ADER.py:80)
         {
@@ -689,7 +648,6 @@ __device__ __forceinline__ void seqp_blocks(const AderSeqFwd& a, const SeqpCtx& 
 #undef F2_EPI
         }
         }
-        SFB(15)
         lds_barrier();
 #undef k
     }
@@ -717,7 +675,6 @@ __global__ __launch_bounds__(640) void k_seqp_fwd(AderSeqFwd a, AderSeqPack pk) 
     const int nb = wave % 5, mh = wave / 5;
     const int T = a.T, H = a.H;
     const uint32_t H4 = (uint32_t)H * 4u;
-    SFS_INIT
 
     for (int i = tid; i < 2 * RSZ * (int)sizeof(bf16) / 16; i += 640) ((uint4*)R0)[i] = make_uint4(0u, 0u, 0u, 0u);   // R0, R1
     // ---- prologue (modules.py:118-130, ADER.py:41-60): x0 = dropout(E[id]*sqrt(H) + P[t]) * (id != 0)
@@ -780,20 +737,15 @@ __global__ __launch_bounds__(640) void k_seqp_fwd(AderSeqFwd a, AderSeqPack pk) 
     const bool small = nrows <= 32;
     const int nrb = nrows > 16 ? 2 : 1;               // 16-row blocks of the small path that hold rows
     lds_barrier();
-    SFS(0)
     {
         SeqpCtx cx;
         cx.R0 = R0; cx.R1 = R1; cx.R2 = R2; cx.km_l = km_l; cx.qm_l = qm_l; cx.sq_l = sq_l; cx.red_l = red_l; cx.info_l = info_l;
         cx.gph_l = gph_l; cx.gpt_l = gpt_l; cx.tp_l = tp_l; cx.nrows = nrows; cx.prow0 = prow0; cx.nrb = nrb;
-#ifdef SFP_STAMP
-        cx.seg = seg; cx.tprev = &tprev;
-#endif
         // (two instantiations of the block loop, not one loop with a branch per phase: with both mappings in one body hipcc spilled
         //  ~300 registers)
         if (small) seqp_blocks<true>(a, cx);
         else seqp_blocks<false>(a, cx);
     }
-    SFS(33)
     // ---- final LayerNorm of every session's last position (ADER.py:83-85) -> rep[b]
     {
         float gf[3], bf_[3];
@@ -814,8 +766,6 @@ __global__ __launch_bounds__(640) void k_seqp_fwd(AderSeqFwd a, AderSeqPack pk) 
             if (lane == 0) { a.meanf[b] = mean; a.stdf[b] = sd; }
         }
     }
-    SFS(34)
-    SFS_DUMP
 }
 
 static const size_t kSeqpFwdLds = (size_t)3 * RSZ * sizeof(bf16) + (size_t)11 * TR * sizeof(float);

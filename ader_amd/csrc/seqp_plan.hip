@@ -35,17 +35,6 @@
 #define PLAN_THREADS 256
 #define PLAN_SPW 64                 // sessions per workgroup of the length pass
 
-#ifdef PLAN_STAMP     // diagnostic build only (tools/build_variant.sh ... -DPLAN_STAMP): clocks per phase of thread 0 of the last workgroup
-__device__ unsigned long long plan_dbg[16];
-#define PST_INIT unsigned long long tprev_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev_) :: "memory");
-#define PST(k_) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                  if (threadIdx.x == 0) plan_dbg[k_] = t_ - tprev_; tprev_ = t_; }
-extern "C" int ader_dbg_read_plan(void* dst, int n) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(plan_dbg), (size_t)n * 8); }
-#else
-#define PST_INIT
-#define PST(k_)
-#endif
-
 __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -83,7 +72,6 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_len(const int* __restrict
     __shared__ int off_l[PLAN_MAXB];
     __shared__ int tmp[PLAN_THREADS / 64];
     const int tid = threadIdx.x;
-    PST_INIT
     // ---- lengths of this workgroup's sessions
     const int sb = blockIdx.x * PLAN_SPW, ns = min(PLAN_SPW, B - sb);
     const int n = ns * T;                                        // <= 4096 ids: sixteen loads per thread, all in flight
@@ -117,7 +105,6 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_len(const int* __restrict
     __syncthreads();
     if (!last_l) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    PST(0)
     // ================= the last workgroup: scans over all sessions
     for (int i = tid; i < B; i += PLAN_THREADS) len_l[i] = (unsigned char)__hip_atomic_load(o.slen + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int i = tid; i < B; i += PLAN_THREADS) { first_l[i] = 0x7fffffff; end_l[i] = 0; }
@@ -131,7 +118,6 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_len(const int* __restrict
         tot += ln;
         if (ln <= 16) a1 += ln; else a3 += 1;
     }
-    PST(1)
     int P1, C3, TOT;
     int e1 = block_excl_scan(a1, tmp, &P1);
     int e3 = block_excl_scan(a3, tmp, &C3);
@@ -139,7 +125,6 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_len(const int* __restrict
     int w1 = w1_max;
     if (target > 0) w1 = max(w1_min, min(w1_max, (P1 + target - 1) / target));
     w1 = max(16, min(49, w1));          // (>= 16: every window then holds a session start, so the raw tile count never exceeds B)
-    PST(2)
     const int n1 = P1 > 0 ? (P1 - 1) / w1 + 1 : 0;
     // (every window [k w, (k+1) w) below the stream's last start holds at least one session start, because no session is longer than w;
     //  the window that holds the stream's end may hold none: the tile numbering is compacted below)
@@ -153,7 +138,6 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_len(const int* __restrict
         atomicMax(&end_l[tile], st + ln);
     }
     __syncthreads();
-    PST(3)
     // ---- compact the tile numbering (a window without a session start is no tile)
     const int nt_raw = n1 + C3;
     int cnt = 0;
@@ -171,14 +155,12 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_len(const int* __restrict
         } else end_l[t] = -1;
     }
     __syncthreads();
-    PST(4)
     // ---- per session: first packed row
     for (int sx = s0; sx < s1; ++sx) {
         const int raw = tile_l[sx];
         o.srow0[sx] = end_l[raw] * 64 + off_l[sx] - first_l[raw];
     }
     if (tid == 0) { o.hdr[0] = ntiles; o.hdr[1] = ntiles * 64; o.hdr[2] = TOT; o.hdr[3] = w1; o.hdr[7] = 0; }     // (ticket re-armed for the next launch)
-    PST(5)
 }
 
 // position t of session s is packed row srow0[s] + t - (T - slen[s]) when t >= T - slen[s]

@@ -577,15 +577,15 @@ int ader_tab_grad_kd(const void* rep_hi, const void* rep_lo, const float* emb, i
     return 0;
 }
 
-#ifdef ADER_XCHECK   // the round-2 fused update (64-row tiles): cross-check kernels of the test build only (libader_xcheck.so)
+#ifdef ADER_XCHECK   // the round-2 fused update (64-row tiles), bf16 "resident" form: test build only (libader_xcheck.so)
 // Fused: table-gradient GEMM + sparse terms + TF-Adam on table rows 1..N (+ bf16 shadow rows), in one pass.
 // sp_ids/sp_rows: the B*T input positions sorted by item id (pads = id 0 first) and their row index into sp_src [B*T,H]
 // (the masked/dropout-scaled gradient rows left by ader_embed_bwd_rows); sp_scale = sqrt(H).  tg_ids/tg_rows: the labels
 // sorted by id and their batch row.  tile_meta: per-tile list records built by ader_tab_tile_meta from the bucket offsets.
 // emb/adam_m/adam_v: fp32 [item_num+1, H], same 16-byte phase.  shadow: bf16 [item_num+1, 168] rewritten for the updated rows
-// (NULL: none; always none in x3 mode).  tile_begin/tile_count: range of 128-item tiles (count < 0: all) for row-sharded
-// updates.  extra_grad: dense fp32 gradient [item_num+1, H] added row by row before the update, or NULL.
-int ader_tab_update(const void* rep_hi, const void* rep_lo, void* shadow, int item_num, int B, int Bp, int H, int N, const float* off,
+// (NULL: none).  tile_begin/tile_count: range of 128-item tiles (count < 0: all) for row-sharded updates.  extra_grad: dense
+// fp32 gradient [item_num+1, H] added row by row before the update, or NULL.
+int ader_tab_update(const void* rep_hi, void* shadow, int item_num, int B, int Bp, int H, int N, const float* off,
                     const int* sp_ids, const int* sp_rows, int n_sp, const float* sp_src, float sp_scale,
                     const int* tg_ids, const int* tg_rows, int n_tg, const int* tile_meta, const float* wrow, float* emb,
                     float* adam_m, float* adam_v, float lr_t, float beta1, float beta2, float eps, int tile_begin,
@@ -596,7 +596,7 @@ int ader_tab_update(const void* rep_hi, const void* rep_lo, void* shadow, int it
     if ((ph & 7) || ((uintptr_t)adam_m & 15) != ph || ((uintptr_t)adam_v & 15) != ph) return -2;
     if (extra_grad && ((uintptr_t)extra_grad & 15) != ph) return -2;
     TabArgs a;
-    a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo; a.off = off;
+    a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = nullptr; a.off = off;
     a.Bp = Bp; a.H = H; a.N = N; a.tile_off = 0; a.rep_img = nullptr; a.demb1 = nullptr;
     a.kd_row0 = Bp; a.Np = 0; a.teacher = nullptr; a.ldt = 0; a.trow = nullptr; a.tlse2 = nullptr;
     FuseArgs fa;
@@ -604,7 +604,7 @@ int ader_tab_update(const void* rep_hi, const void* rep_lo, void* shadow, int it
     fa.tg_ids = tg_ids; fa.tg_rows = tg_rows; fa.n_tg = n_tg; fa.wrow = wrow;
     fa.tile_meta = tile_meta;
     fa.emb1 = emb + H; fa.m1 = adam_m + H; fa.v1 = adam_v + H;
-    fa.sh1w = (shadow && !rep_lo) ? (bf16*)shadow + LDR : nullptr;
+    fa.sh1w = shadow ? (bf16*)shadow + LDR : nullptr;
     fa.lr_t = lr_t; fa.omb1 = 1.0f - beta1; fa.omb2 = 1.0f - beta2; fa.eps = eps;
     fa.extra1 = extra_grad ? extra_grad + H : nullptr;
     // tiles [tile_begin, tile_begin + tile_count) of the ceil(N/128) 128-item tiles (tile_count < 0: all) = two 64-row tiles each
@@ -615,40 +615,8 @@ int ader_tab_update(const void* rep_hi, const void* rep_lo, void* shadow, int it
     if (te <= tb) return 0;
     a.tile_off = tb;
     hipStream_t st = (hipStream_t)stream;
-    const bool x3 = rep_lo != nullptr;
-    const size_t lds = tab_lds(Bp, H, x3, true);
-    int rc;
-    if (x3) rc = extra_grad ? tab_launch<true, true, true>(a, fa, te - tb, lds, st) : tab_launch<true, true, false>(a, fa, te - tb, lds, st);
-    else rc = extra_grad ? tab_launch<false, true, true>(a, fa, te - tb, lds, st) : tab_launch<false, true, false>(a, fa, te - tb, lds, st);
-    if (rc) return rc;
-    HIP_LAUNCH_CHECK();
-    return 0;
-}
-
-// The x3-mode update of a DISTILLED step (ADER.py:132-137): batch rows [kd_row0, Bp) of the padded layout of ader_lx3_fwd_kd are
-// exemplar rows whose dlogit is w (softmax(s[:Np]) - softmax(teacher row)); wrow / off / trow / tlse2 as that call left them.
-int ader_tab_update_kd(const void* rep_hi, const void* rep_lo, int item_num, int Bp, int kd_row0, int H, int N, int Np, const float* off,
-                       const int* sp_ids, const int* sp_rows, int n_sp, const float* sp_src, float sp_scale, const int* tg_ids,
-                       const int* tg_rows, int n_tg, const int* tile_meta, const float* wrow, const float* teacher, long ldt,
-                       const int* trow, const float* tlse2, float* emb, float* adam_m, float* adam_v, float lr_t, float beta1,
-                       float beta2, float eps, void* stream) {
-    if (Bp <= 0) return 0;
-    if (Bp % 128 != 0 || kd_row0 % 128 != 0 || kd_row0 >= Bp || H > HP || (H & 1) || H < 2 || N > item_num || !rep_lo || !teacher ||
-        !trow || !tlse2 || Np < 1 || Np > N) return -2;
-    const uintptr_t ph = (uintptr_t)emb & 15;
-    if ((ph & 7) || ((uintptr_t)adam_m & 15) != ph || ((uintptr_t)adam_v & 15) != ph) return -2;
-    TabArgs a;
-    a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo; a.off = off;
-    a.Bp = Bp; a.H = H; a.N = N; a.tile_off = 0; a.rep_img = nullptr; a.demb1 = nullptr;
-    a.kd_row0 = kd_row0; a.Np = Np; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
-    FuseArgs fa;
-    fa.sp_ids = sp_ids; fa.sp_rows = sp_rows; fa.n_sp = n_sp; fa.sp_src = sp_src; fa.sp_scale = sp_scale;
-    fa.tg_ids = tg_ids; fa.tg_rows = tg_rows; fa.n_tg = n_tg; fa.wrow = wrow;
-    fa.tile_meta = tile_meta;
-    fa.emb1 = emb + H; fa.m1 = adam_m + H; fa.v1 = adam_v + H; fa.sh1w = nullptr;
-    fa.lr_t = lr_t; fa.omb1 = 1.0f - beta1; fa.omb2 = 1.0f - beta2; fa.eps = eps;
-    fa.extra1 = nullptr;
-    int rc = tab_launch<true, true, false, true>(a, fa, (N + TI - 1) / TI, tab_lds(Bp, H, true, true), (hipStream_t)stream);
+    const size_t lds = tab_lds(Bp, H, false, true);
+    int rc = extra_grad ? tab_launch<false, true, true>(a, fa, te - tb, lds, st) : tab_launch<false, true, false>(a, fa, te - tb, lds, st);
     if (rc) return rc;
     HIP_LAUNCH_CHECK();
     return 0;

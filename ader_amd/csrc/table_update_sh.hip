@@ -2,7 +2,7 @@
 // The GEMM operand E is the tile's bf16 SHADOW rows (336 B per row, read once), theta / m / v are streamed in rounds of 16-byte
 // vectors.  64-row tiles on v_mfma_f32_16x16x32_bf16, three workgroups per CU (k_tab16 below).  This form reads 8 % more bytes
 // than table_update.hip's theta-resident kernel (the shadow rows) but is 10 % faster: both are bound by the per-workgroup
-// latency chain and the HBM queue, and resident waves per CU are what buys time (round-2 measurements in DESIGN.md section 6;
+// latency chain and the HBM queue, and resident waves per CU are what buys time (round-2 measurements in NOTEBOOK.md;
 // the 128-row 32x32x16 predecessor of this kernel fitted two workgroups per CU: 0.95 ms against 0.90 ms per 10^6 rows).
 // table_update.hip serves the x3 mode and the gradient-only entry point.
 #include "lbf_common.h"

@@ -21,7 +21,6 @@
 //     ds_read_b64_tr_b16.
 // The optimiser phase (dE staging tile, sparse terms from the bucketed lists in list order -- no atomics, bit-reproducible --, TF-Adam
 // over the tile's flat [64*H] block of theta/m/v in 16-byte vectors) is the one of k_tab16 without the shadow rows.  gfx950 only.
-#include <stdlib.h>
 #include "lbf_common.h"
 #include "x3_image.h"
 #include "../../include/ader_hip.h"
@@ -36,24 +35,11 @@
 #define HVB 32                     // gradient rows in flight per thread on the heavy path (k_tab32x3)
 #define HVB1 16                    // ... of k_tab16x3 (168 registers: three workgroups per CU)
 #define SPB 4                      // sparse-list entries per batch of the optimiser phase (loads of a batch are independent)
-#ifndef AV
-#define AV 6                       // 16-byte vectors per thread and load round of the optimiser phase (x theta, m, v)
-#endif
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(8))) F16B { f32x4_t v; };       // 16-byte vector at an 8-byte aligned address
-
-__device__ int x3_cu_arrivals[4096];
-#ifdef T3_STAMP     // diagnostic build only (tools/build_variant.sh ... -DT3_STAMP): per-segment clocks of wave 0 of every workgroup
-__device__ unsigned long long t3_dbg[12 * 1024];
-#define STAMP(k_) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                    __builtin_amdgcn_sched_barrier(0); seg[k_] += t_ - tprev; tprev = t_; }
-extern "C" int ader_dbg_read(void* dst, int n) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(t3_dbg), (size_t)n * 8); }
-#else
-#define STAMP(k_)
-#endif
 
 // One chunk image (22 KiB, contiguous in memory) -> LDS buffer, as 22 LDS-DMA pieces of 1 KiB.
 // The DMA is issued from inline asm ON PURPOSE: hipcc counts a __builtin_amdgcn_global_load_lds as a pending LDS write and puts
@@ -110,40 +96,10 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
     const int rows_avail = min(TI, a.vrows - tile0);
     const int n_av = rows_avail > 0 ? rows_avail * H : 0;
     const float* __restrict__ gsrc = a.emb1 + (size_t)tile0 * H;
-#ifdef T3_STAMP
-    unsigned long long seg[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev) :: "memory");
-#endif
-    // ---- phase stagger of the first generation of workgroups (speed only): all tiles cost the same, so the three
-    // workgroups of a CU would run their matrix phases together and their HBM phases together for the whole launch
-    if ((a.ko >> 16) && blockIdx.x < 768) {
-        const int mode = (a.ko >> 8) & 15;
-        int k;
-        if (mode == 3) {        // arrival order on this CU (HW_ID: cu 11:8, sh 12, se 15:13; XCC_ID 3:0)
-            int kk = 0;
-            if (tid == 0) {
-                const unsigned hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));     // HW_REG_HW_ID
-                const unsigned xcc = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));    // HW_REG_XCC_ID
-                const unsigned cu = ((hw >> 8) & 0xff) | ((xcc & 15) << 8);
-                kk = atomicAdd(&x3_cu_arrivals[cu & 4095], 1) % 3;
-            }
-            k = __shfl(kk, 0, 64);
-            k = __builtin_amdgcn_readfirstlane(k);
-            __shared__ int k_sh;
-            if (tid == 0) k_sh = k;
-            __syncthreads();
-            k = k_sh;
-        } else k = mode == 0 ? (int)(blockIdx.x >> 8) : (mode == 1 ? (int)((blockIdx.x >> 3) % 3) : (int)(blockIdx.x % 3));
-        if (k) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            const unsigned long long dt = (unsigned long long)k * (a.ko >> 16) * 100ull;      // 100 MHz ticks
-            while (__builtin_amdgcn_s_memrealtime() - t0 < dt) __builtin_amdgcn_s_sleep(64);
-        }
-    }
     // ---- the first rep chunk is requested before anything else; the per-row constants and the tile's list record go to LDS
     const char* img = (const char*)a.rep_img;
     const int nch = a.Bp / X3_CH;
-    if (!(a.ko & 2)) x3_dma_chunk(img, 0, R_l, wave, lane);
+    x3_dma_chunk(img, 0, R_l, wave, lane);
     // ---- operand fragments straight from memory: lane (item c16 of this wave's 16, k-group g) holds E[item][32 ks + 8 g + 0..7] as
     // hi + lo.  Two 16-byte loads per k-step at 8-byte aligned addresses; rows beyond the table's last one read zeros (range check);
     // channels >= H of the last k-step read what follows the row -- finite parameters that only ever meet the zero K-padding of rep.
@@ -185,9 +141,7 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
             }
         }
     }
-    STAMP(0)
     __syncthreads();                                            // off_l / meta_l are in LDS
-    STAMP(1)
     // the first input-embedding gradient rows of the tile (thread c holds column c), requested now, used after the GEMM
     float spv[SPV];
     // (every sparse-row product / sum below is kept as two rounded operations -- "#pragma clang fp contract(off)" -- so that the x3
@@ -197,8 +151,6 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
         const bool on = tid < H && meta_l[0] + i < meta_l[1];        // for at the end of its branch -- three round trips in a row
         { _Pragma("clang fp contract(off)") spv[i] = f.sp_src[on ? (size_t)meta_l[3 + 2 * i] * H + tid : 0] * (on ? f.sp_scale : 0.0f); }
     }
-    STAMP(2)
-    STAMP(3)
     f32x4v dE[10];
 #pragma unroll
     for (int cb = 0; cb < 10; ++cb) dE[cb] = (f32x4v){0.f, 0.f, 0.f, 0.f};
@@ -208,12 +160,10 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
     const int t_off = 1152 * (p4 >> 1) + 16 * (4 * g + q4) + 8 * (p4 & 1);
     // (s_setprio 2 around this loop -- matrix phases ahead of the other workgroups' vector phases -- measured 2-3 % SLOWER: it starves
     //  the phases that request the next tile's memory)
-    for (int c = 0; c < ((a.ko & 2) ? 0 : nch); ++c) {
+    for (int c = 0; c < nch; ++c) {
         // this wave's pieces of chunk c have landed and its LDS reads of chunk c-1 are done; after the barrier that holds for every
         // wave, so chunk c can be read and the other buffer (chunk c-1's) can be refilled
-        STAMP(4)
-        if (!(a.ko & 8)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        STAMP(5)
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         const char* Bh = (const char*)(R_l + (c & 1) * X3_BUF);
         const int b0 = c * X3_CH;
         // KD rows: this lane's 8 teacher logits (item it0 + c16, batch rows b0 + 16 rb + 4 g + j), requested ahead of the MFMAs
@@ -244,7 +194,7 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
         X3_LOADA(fa[1], 1);
         __builtin_amdgcn_sched_barrier(0);
         // (the next chunk's DMA is issued behind the first operand reads: its scalar issue sequence runs under their latency)
-        if (c + 1 < nch && !(a.ko & 4)) x3_dma_chunk(img, c + 1, R_l + ((c + 1) & 1) * X3_BUF, wave, lane);
+        if (c + 1 < nch) x3_dma_chunk(img, c + 1, R_l + ((c + 1) & 1) * X3_BUF, wave, lane);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < 5; ++ks) {
@@ -258,7 +208,6 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
             if (ks + 2 < 5) X3_LOADA(fa[ks & 1], ks + 2);
             __builtin_amdgcn_sched_barrier(0);
         }
-        STAMP(6)
         // the first transposed reads of the P^T.rep phase do not depend on S: in flight under the exp2 section
         bf16x4 ft[3][4];
         X3_LOADT(ft[0], 0);
@@ -293,7 +242,6 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
             pl_[j] = (bf16)(S0[j] - (float)h0); pl_[4 + j] = (bf16)(S1[j] - (float)h1);
         }
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(7)
 #pragma unroll
         for (int cb = 0; cb < 10; ++cb) {
             bf16x4* T_ = ft[cb % 3];
@@ -312,18 +260,17 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
     // ---- optimiser phase: the tile's rows are ONE contiguous block of 64*H floats in theta / m / v (and in F_l)
     float* F_l = (float*)smem_raw;
     const int rows_valid = min(TI, N - tile0);
-    const int n_el = (rows_valid > 0 && !(a.ko & 1)) ? rows_valid * H : 0;
-    const size_t tq = (a.ko & 16) ? (size_t)(tile & 63) * TI : (size_t)tile0;    // ko 16: optimiser traffic served by L2 (timing only)
-    float* __restrict__ gp = f.emb1 + tq * H;
-    float* __restrict__ gm = f.m1 + tq * H;
-    float* __restrict__ gv = f.v1 + tq * H;
+    const int n_el = rows_valid > 0 ? rows_valid * H : 0;
+    float* __restrict__ gp = f.emb1 + (size_t)tile0 * H;
+    float* __restrict__ gm = f.m1 + (size_t)tile0 * H;
+    float* __restrict__ gv = f.v1 + (size_t)tile0 * H;
     const float* __restrict__ gx = EXTRA ? f.extra1 + (size_t)tile0 * H : nullptr;
     // theta / m / v of the tile through buffer descriptors (base and size in scalar registers, one 32-bit per-lane offset, the
     // vector index as the scalar offset): vector u of thread t = floats 4 t + 1024 u of the block; floats >= n_el (the table's last,
     // partial tile; vectors 9.375.. of a full one) are range-checked away by the hardware, loads AND stores -- no per-vector branch.
     // ALL loads of the tile are in flight at once (m, v requested before the dE staging and the sparse terms, theta right behind
     // the staging, when the accumulators have left their registers): the phase waits out ONE memory latency instead of one per
-    // round (stamps: 4-5 us each under load).
+    // round (stamps: 4-5 us each under load, NOTEBOOK.md).
     const unsigned nbytes = (unsigned)n_el * 4u;
     const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)gp, 0, nbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc((void*)gm, 0, nbytes, 0x00020000);
@@ -342,7 +289,6 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
     // cooperatively, 256 entries per round trip, and the gradient rows HVB at a time -- with the optimiser loads requested AFTER
     // the sparse terms, so that the registers are free for the deeper batches (a workgroup-uniform choice; rare tiles).
     const bool heavy = (meta_l[1] - meta_l[0] > HEAVY_N) || (meta_l[TM_LIST + 1] - meta_l[TM_LIST] > HEAVY_N);
-    STAMP(4)
     if (!heavy) { LOAD_MV(); }
     lds_only_barrier();             // every wave is done with the last rep chunk
 #pragma unroll
@@ -354,7 +300,6 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
         }
     }
     lds_only_barrier();
-    STAMP(8)
     {
     #pragma clang fp contract(off)
         // sparse terms of the tile: item ids [tile0+1, tile0+65).  Thread c owns column c of every row.
@@ -469,20 +414,14 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
     if (heavy) { LOAD_MV(); }
     LOAD_P();
     lds_only_barrier();
-    STAMP(9)
     // TF ApplyAdam (ADER.py:96): m += (g-m)(1-b1); v += (g*g-v)(1-b2); theta -= lr_t*m/(sqrt(v)+eps).  The square root and the
     // division use the hardware's v_sqrt_f32 / v_rcp_f32 (<= 1 ulp each; the update differs from the correctly rounded one by
     // < 4e-7 of ITSELF): the IEEE sequences cost ~27 vector instructions per element -- 1,300 of the 3,900 a wave issues per
     // tile, and it is vector ISSUE (matrix + vector instructions of three waves on one SIMD) that bounds this kernel (stamps and
-    // counters: DESIGN.md section 6).  ADER_EXACT_DIV restores the correctly rounded forms.
-#ifdef ADER_EXACT_DIV
-#define ADAM1(p_, m_, v_, g_)                                                                              \
-    { m_ += ((g_) - m_) * f.omb1; v_ += ((g_) * (g_) - v_) * f.omb2; p_ -= (m_ * f.lr_t) / (sqrtf(v_) + f.eps); }
-#else
+    // counters: NOTEBOOK.md).
 #define ADAM1(p_, m_, v_, g_)                                                                              \
     { m_ += ((g_) - m_) * f.omb1; v_ += ((g_) * (g_) - v_) * f.omb2;                                       \
       p_ -= (m_ * f.lr_t) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v_) + f.eps); }
-#endif
 #pragma unroll
     for (int u = 0; u < NVEC; ++u) {
         const int e = 4 * tid + 1024 * u;
@@ -502,11 +441,6 @@ __global__ __launch_bounds__(256, 3) void k_tab16x3(TabArgs a, FuseArgs f) {
         }
     }
 #undef ADAM1
-#ifdef T3_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    STAMP(10)
-    if (tid == 0 && blockIdx.x % 16 == 5 && blockIdx.x / 16 < 1024) for (int k_ = 0; k_ < 12; ++k_) t3_dbg[(blockIdx.x / 16) * 12 + k_] = seg[k_];
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -531,10 +465,6 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
     const int tileA = 2 * blockIdx.x + a.tile_off;              // tiles tileA, tileA + 1 (the second may lie beyond the launch)
     const char* img = (const char*)a.rep_img;
     const int nch = a.Bp / X3_CH;
-#ifdef T3_STAMP
-    unsigned long long seg[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev) :: "memory");
-#endif
     x3_dma_chunk(img, 0, R_l, wave, lane);
     bf16x8 e_hi[2][5], e_lo[2][5];
 #pragma unroll
@@ -542,8 +472,7 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
         const int tile0 = (tileA + h) * TI;
         const int rows_avail = (tileA + h < a.tile_end) ? min(TI, a.vrows - tile0) : 0;
         const int n_av = rows_avail > 0 ? rows_avail * H : 0;
-        const size_t tqe = (a.ko & 256) ? (size_t)((tileA + h) & 63) * TI : (size_t)tile0;   // ko 256: operand rows served by L2 (timing only)
-        const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.emb1 + tqe * H), 0, (unsigned)n_av * 4u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.emb1 + (size_t)tile0 * H), 0, (unsigned)n_av * 4u, 0x00020000);
         const int vt = 4 * ((wave * 16 + c16) * H + 8 * g);
         f32x4_t x0[5], x1[5];
 #pragma unroll
@@ -578,9 +507,7 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
             }
         }
     }
-    STAMP(0)
     __syncthreads();                                            // off_l / meta_l are in LDS
-    STAMP(1)
     float spv[2][SPV];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -600,11 +527,8 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
     const int a_off = 1152 * (g >> 1) + 512 * (g & 1) + 16 * c16;
     const int t_off = 1152 * (p4 >> 1) + 16 * (4 * g + q4) + 8 * (p4 & 1);
     const int itA = tileA * TI + wave * 16;                     // this wave's first item of half 0 (half 1: + TI)
-    STAMP(2)
     for (int c = 0; c < nch; ++c) {
-        STAMP(4)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        STAMP(5)
         const char* Bh = (const char*)(R_l + (c & 1) * X3_BUF);
         const int b0 = c * X3_CH;
         float tv[KD ? 16 : 1];
@@ -651,7 +575,6 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
             if (ks + 2 < 5) X3_LOADA(fa[ks & 1], ks + 2);
             __builtin_amdgcn_sched_barrier(0);
         }
-        STAMP(6)
         bf16x4 ft[3][4];
         X3_LOADT(ft[0], 0);
         X3_LOADT(ft[1], 1);
@@ -689,7 +612,6 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(7)
 #pragma unroll
         for (int cb = 0; cb < 10; ++cb) {
             bf16x4* T_ = ft[cb % 3];
@@ -711,7 +633,6 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
     // ---- optimiser phase, once per tile of the pair (k_tab16x3's: comments there)
     float* F_l = (float*)smem_raw;
     const int vo = 16 * tid;
-    STAMP(4)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int tile = tileA + h;
@@ -743,7 +664,6 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
             }
         }
         lds_only_barrier();
-        STAMP(8)
         {
         #pragma clang fp contract(off)
             const int id_lo = tile0 + 1, id_hi = (tile < a.tile_end ? min(tile0 + TI, N) : tile0) + 1;
@@ -850,7 +770,6 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
         if (heavy) { LOAD_MV(); }
         LOAD_P();
         lds_only_barrier();
-        STAMP(9)
 #define ADAM1(p_, m_, v_, g_)                                                                              \
         { m_ += ((g_) - m_) * f.omb1; v_ += ((g_) * (g_) - v_) * f.omb2;                                   \
           p_ -= (m_ * f.lr_t) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v_) + f.eps); }
@@ -872,37 +791,13 @@ __global__ __launch_bounds__(256, 2) void k_tab32x3(TabArgs a, FuseArgs f) {
             }
         }
 #undef ADAM1
-#ifdef T3_STAMP
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP(10)
-#endif
     }
-#ifdef T3_STAMP
-    if (tid == 0 && blockIdx.x % 8 == 5 && blockIdx.x / 8 < 1024) for (int k_ = 0; k_ < 12; ++k_) t3_dbg[(blockIdx.x / 8) * 12 + k_] = seg[k_];
-#endif
 }
 
 // ============================================================================================= launch (C ABI: table_update.hip)
-// Timing-only knobs of the diagnostic builds (tools/build_variant.sh ... -DADER_DIAG): knock-outs, staggers, an LDS pad and the
-// one-tile kernel.  A production build reads NO environment variable here: a stray one must not be able to corrupt a training run.
 static size_t tab16x3_lds(int Bp, int Bk) {
-    int pad = 0;
-#ifdef ADER_DIAG
-    { static int pad_ = -1; if (pad_ < 0) { const char* e = getenv("ADER_X3_LDSPAD"); pad_ = e ? atoi(e) : 0; } pad = pad_; }
-#endif
-    return (size_t)2 * X3_IMG_B + (size_t)Bp * sizeof(float) + 4 * TM_LIST * sizeof(int) + (size_t)Bk * 8 + pad;
+    return (size_t)2 * X3_IMG_B + (size_t)Bp * sizeof(float) + 4 * TM_LIST * sizeof(int) + (size_t)Bk * 8;
 }
-static bool tab_pairs() {                 // (ADER_DIAG, ADER_X3_TILE=64: k_tab16x3 -- one 64-row tile per workgroup -- instead of k_tab32x3)
-#ifdef ADER_DIAG
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ADER_X3_TILE"); v = (e && atoi(e) == 64) ? 0 : 1; }
-    return v == 1;
-#else
-    return true;
-#endif
-}
-
-static int g_x3_pair_min_tiles = 0;       // ader_x3_update_pair_min_tiles(): 0 = pairs always (measured: no difference on the shipped catalogs)
 
 template <bool EXTRA, bool KD>
 static int tab16x3_launch_t(const TabArgs& a, const FuseArgs& fa, int tiles, size_t lds, hipStream_t st) {
@@ -930,17 +825,13 @@ static int tab32x3_launch_t(const TabArgs& a, const FuseArgs& fa, int tiles, siz
 }
 
 static int tab16x3_launch(TabArgs a, const FuseArgs& fa, int tiles, bool extra, bool kd, void* stream) {
-    a.ko = 0;
-#ifdef ADER_DIAG
-    { static int ko = -1; if (ko < 0) { const char* e = getenv("ADER_X3_KO"); ko = e ? atoi(e) : 0; const char* s_ = getenv("ADER_X3_STAGGER"); ko |= (s_ ? atoi(s_) : 0) << 16; } a.ko = ko; }
-#endif
     if (a.Bp % X3_CH != 0 || (kd && a.kd_row0 % X3_CH != 0) || !a.rep_img || ((uintptr_t)a.rep_img & 15)) return -2;
     const size_t lds = tab16x3_lds(a.Bp, kd ? a.Bp - a.kd_row0 : 0);
     hipStream_t st = (hipStream_t)stream;
     a.tile_end = a.tile_off + tiles;
-    // (A/B knob: below g_x3_pair_min_tiles tiles, one tile per workgroup.  Measured on the shipped catalogs, 400-700 tiles, distilled step:
-    //  k_tab16x3 107.6 us against k_tab32x3 112.1 us, step 0.4594 against 0.4575 ms -- no difference, the default stays pairs)
-    if (tab_pairs() && tiles > g_x3_pair_min_tiles && (a.tile_off & 1) == 0 && !(a.ko & 0xff)) {
+    // a PAIR of tiles per workgroup whenever the launch starts on an even tile.  (Measured on the shipped catalogs, 400-700 tiles,
+    //  distilled step: k_tab16x3 107.6 us against k_tab32x3 112.1 us, step 0.4594 against 0.4575 ms -- no difference; NOTEBOOK.md)
+    if (tiles > 0 && (a.tile_off & 1) == 0) {
         if (kd) return tab32x3_launch_t<false, true>(a, fa, tiles, lds, st);
         if (extra) return tab32x3_launch_t<true, false>(a, fa, tiles, lds, st);
         return tab32x3_launch_t<false, false>(a, fa, tiles, lds, st);
@@ -951,17 +842,6 @@ static int tab16x3_launch(TabArgs a, const FuseArgs& fa, int tiles, bool extra, 
 }
 
 extern "C" {
-
-// (The role-split producer / consumer form of this update -- k_tabp, rounds 4-5, opt-in -- was removed in round 5: it never won in the
-//  step and the full-size bit-identity test caught it writing a few wrong vectors in one launch out of several on a
-//  cold process: a kernel with a rare race has no place behind the ABI.)
-// tiles (64 table rows each) above which the update takes a PAIR of tiles per workgroup (k_tab32x3) instead of one (k_tab16x3):
-// tuning / A-B knob, bit-identical results either way; negative: query.  Returns the previous setting.
-int ader_x3_update_pair_min_tiles(int tiles) {
-    const int prev = g_x3_pair_min_tiles;
-    if (tiles >= 0) g_x3_pair_min_tiles = tiles;
-    return prev;
-}
 
 // LDS image of the x3 operand rows for ader_tab_update_x3[_kd]: img = ader_x3_rep_image_bytes(Bp) bytes, 16-byte aligned, built from
 // the two planes rep_hi / rep_lo [Bp,168] that ader_lx3_prep / ader_lx3_fwd[_kd] leave (Bp % 32 == 0).

@@ -14,13 +14,12 @@ class _Backward:
         """dW = A^T.G, db = colsum(G).  In x3 mode the products are queued (A and G stay untouched until the end of the
         backward pass) and issued as one batched launch by _atb_flush.  pack: the operands are in tile order (packed session
         kernels): the plan tells the product which rows exist."""
-        if self.gemm_x3 and self.atb_batch:
+        if self.gemm_x3:
             self._atb_q.append((A, G, self._gp[wname], self._gp[bname], M, pack))
             if len(self._atb_q) == 16:
                 self._atb_flush()
             return
-        fn = "ader_gemm_atb_x3" if self.gemm_x3 else "ader_gemm_atb"
-        call(fn, ptr(A), ptr(G), ptr(slab), self._gp[wname], self._gp[bname], M, self.H, self._stream())
+        call("ader_gemm_atb", ptr(A), ptr(G), ptr(slab), self._gp[wname], self._gp[bname], M, self.H, self._stream())
 
     def _late_call(self, name, *args):
         """A launch whose result only feeds the small-parameter update: issued now, or queued for the side stream that runs
@@ -208,7 +207,7 @@ class _Backward:
                     late_loss = bool(defer and self.dp_world == 1 and not split_kd and self.late_side_stream and self.seq_fused)
                     # (the operand images of the fused update are cut by the same launch as the operand planes)
                     img = (self.buf("lbf_rep_img", (call("ader_x3_rep_image_bytes", Bp),), torch.uint8, zero=True)
-                           if (defer and self.x3_update == "tab16" and not split_kd) else None)
+                           if (defer and not split_kd) else None)
                     lnf = self._lnf_desc(B) if (Bb == B) else None      # (split_kd: the exemplar rows' dRep comes from other kernels)
                     call("ader_lx3_fwd_img_lnf", ptr(rep), emb, self.item_num, Bb, Bp, H, N, ptr(lab), ptr(wrow), ptr(rep_bf), ptr(rep_lo),
                          ptr(pm), ptr(pl), ptr(pO), ptr(lse), ptr(off), ptr(rowloss), None if late_loss else ptr(self.loss), ptr(drep),
@@ -293,7 +292,7 @@ class _Backward:
                 late_loss = bool(fused and self.dp_world == 1 and self.late_side_stream and self.seq_fused)
                 # (... and the operand images of the fused update are cut by the launch that cuts the operand planes)
                 img = (self.buf("lbf_rep_img", (call("ader_x3_rep_image_bytes", Bp),), torch.uint8, zero=True)
-                       if (fused and self.x3_update == "tab16") else None)
+                       if fused else None)
                 call("ader_lx3_fwd_kd_lnf", ptr(rep), self._pp["emb"], self.item_num, n_train, n_ex, Bt, Bp, H, N, Np, ptr(pos),
                      ptr(ex_trow), ptr(teacher), teacher.stride(0), ptr(tlse_all), float(w_train), float(w_ex), ptr(lab), ptr(wrow),
                      ptr(trow), ptr(tlse2), ptr(rep_bf), ptr(rep_lo), ptr(pm), ptr(pl), ptr(pO), ptr(pO2), ptr(lse), ptr(off),
@@ -523,7 +522,7 @@ class _Backward:
         M = B if pruned else rows
         mpk = None if pruned else pk           # the compact tensors of a pruned block are plain [B, H]
         # (cached only on the default training path: small launches queued for the side stream, weight gradients batched)
-        cacheable = bool(self.cache_descriptors and self._late_on and self.gemm_x3 and self.atb_batch)
+        cacheable = bool(self.cache_descriptors and self._late_on and self.gemm_x3)
         ck = ("bwdp", l, B, ptr(dxo), ptr(dxn), bool(emb_bwd))
         ent = self._dc(ck) if cacheable else None
         if ent is not None and ent[0] is S and ent[1] is pk and ent[2] is d_emb:

@@ -355,7 +355,7 @@ class _Forward:
     def _lnf_desc(self, B):
         """AderLnfBwd of the forward just saved (prune_last: xL / meanf / stdf are compact [B, ..]), or None when not fused."""
         A = self._act
-        if not (self.fuse_final_ln and self.prune_last and self.lx3):
+        if not (self.prune_last and self.lx3):
             self._lnf_done = None
             return None
         H = self.H

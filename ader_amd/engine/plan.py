@@ -223,15 +223,15 @@ class _Native:
     def _native_ok(self, kw):
         """The step forms whose launch sequence is pure launcher calls + stream edges (no torch kernel, no collective, no host read)."""
         return (self.native_step and self.dp_world == 1 and self.lx3 and self.lfast and self.seq_fused and self.fuse_adam
-                and self.x3_update == "tab16" and self.kd_fast and self.grad_hook is None and self.grad_early_hook is None
+                and self.kd_fast and self.grad_hook is None and self.grad_early_hook is None
                 and self.timer is None and (self.ewc is None or self.ewc["lam"] == 0.0) and self._pending_loss is None
                 and not (kw.get("teacher") is not None and kw.get("ex_pos") is not None))
 
     def _plan_key(self, tag, B_all, n_train, N, lr, rate, lambda_, teacher, has_expos, n_tg, n_eg, pack, extra=()):
         tk = None if teacher is None else (teacher.data_ptr(), tuple(teacher.shape), teacher.stride(0))
         return (tag, B_all, n_train, N, float(rate), float(lambda_), tk, has_expos, n_tg, n_eg, pack, self.row0, self.row0_ex,
-                getattr(self, "_ex_row0_set", False), self.seed, self.prune_last, self.fuse_final_ln, self.late_side_stream,
-                self.lists_side_stream, self.atb_batch, self.cache_descriptors, self.pack_window, self.pack_density, self._grad_hi <= N,
+                getattr(self, "_ex_row0_set", False), self.seed, self.prune_last, self.late_side_stream, self.cache_descriptors,
+                self.pack_window, self.pack_density, self._grad_hi <= N,
                 self.beta1, self.beta2, self.eps, extra)
 
     def _native_step(self, seq, pos, max_item, lr, kw):

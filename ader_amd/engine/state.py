@@ -63,7 +63,6 @@ class _State:
         self.pack_density = None
         self.pack_window = (17, 49, 224)   # stream window of the short class: at least / at most / tile count aimed at (seqp_plan.hip)
         self._pack_now = False
-        self.lists_side_stream = True      # build the sparse lists under the block kernels
         self.late_side_stream = True       # small-parameter gradients / Adam run beside the (HBM-bound) fused table update
         self._late, self._late_on, self._late_force = [], False, False
         self._st_ptr, self._main, self._in_step = None, None, False
@@ -75,8 +74,7 @@ class _State:
         self.plan_errors = []
         self._plans, self._plans_gen, self._keep_density, self._held, self._density_now = None, -1, False, None, None
         self._pin = {}
-        self.atb_batch = True          # x3 mode: all weight-gradient products of a backward pass in one launch
-        self._atb_q = []
+        self._atb_q = []               # x3 mode: the weight-gradient products of a backward pass, issued as one launch
         self.attn_x3 = gemm == "x3" and (hidden_units // num_heads) % 2 == 0      # bf16x3 attention core (attn_x3.hip)
         self._wnames = ["b%d.%s" % (l, w) for l in range(num_blocks) for w in ("wq", "wk", "wv", "w1", "w2")]
         self._widx = {k: i for i, k in enumerate(self._wnames)}
@@ -105,9 +103,6 @@ class _State:
         self.ewc = None          # EWC baseline (EWC.py): dict(F=, prev=, lam=) -> quadratic penalty added between backward and Adam
         self.timer = None        # optional SectionTimer
         self.prune_last = True   # final block: query/FFN path only for position T-1 (exact; see forward())
-        # float32-grade flash forward: the backward of the final LayerNorm runs inside the merge launch of the logit forward (the
-        # workgroup that forms a row of dRep also forms LN_f'(dRep)): k_ln_bwd and its kernel boundary leave the critical path
-        self.fuse_final_ln = True
         self._lnf_done = None
         # single-GPU bf16-logits steps: apply Adam to the item table inside the table-gradient GEMM (the table gradient
         # is never written to memory); needs the complete gradient locally, so it is off whenever a grad_hook is set
@@ -130,11 +125,8 @@ class _State:
         self.kd_split = True     # distilled steps: train rows on the bf16 / fused path, exemplar rows on the exact-f32 kernels
         self.kd_fast = True      # ... exemplar rows on the flash path too (teacher readout + fused KD update)
         # bf16 mode, fused table update: "sh" = k_tab16 (operand from the shadow rows, three workgroups per CU: the faster form),
-        # "resident" = k_tab_upd (theta tile read once and kept in LDS, no shadow read: 8 % fewer bytes, 10 % slower)
+        # "resident" = k_tab_upd (theta tile read once and kept in LDS, no shadow read: 8 % fewer bytes, 10 % slower; NOTEBOOK.md)
         self.bf16_update = "sh"
-        # x3 mode, fused table update: "tab16" = k_tab16x3 (16x16x32 tiles, three workgroups per CU, rep chunks by LDS-DMA as
-        # conflict-free LDS images: the faster form), "tab32" = the round-2 kernel k_tab_upd<X3> (kept for kernel-vs-kernel tests)
-        self.x3_update = "tab16"     # (an attribute, not an environment variable: a stray setting must not switch kernels)
         self._table_stale = False
         self._pending_loss, self._img_ready = None, False     # late loss sum / operand images of a deferred fused update
         self._mv_sharded = False   # dp: Adam m/v of the table are current only for the rank's own rows (see _gather_if_sharded)

@@ -58,9 +58,6 @@ class _Update:
         # a strided view (the catalog-sharded step passes ids_g[:, :n_pos]) would otherwise be materialised inside _sparse_lists --
         # a torch kernel on the main stream that the list kernels on the side stream do not wait for
         seq, lab = seq.reshape(-1).to(torch.int32).contiguous(), lab.reshape(-1).to(torch.int32).contiguous()
-        if not self.lists_side_stream:
-            self._lists = self._sparse_lists(seq, lab, N)
-            return
         self._edge(self._side_lane(), main)      # inputs ready; also orders reuse of last step's list memory after its reader
         with self._OnStream(self, self._side):
             self._lists = self._sparse_lists(seq, lab, N)
@@ -75,8 +72,7 @@ class _Update:
 
     def _lists_wait(self):
         out, self._lists = self._lists, None
-        if self.lists_side_stream:
-            self._edge(self._main, self._side)       # (the lists live in persistent workspace buffers: no record_stream needed)
+        self._edge(self._main, self._side)       # (the lists live in persistent workspace buffers: no record_stream needed)
         return out
 
     def _fused_table_adam(self, lr):
@@ -121,18 +117,17 @@ class _Update:
                 self._img_ready = False
             if self.lx3 and D.get("kd"):
                 K = D["kd"]
-                call("ader_tab_update_x3_kd" if self.x3_update == "tab16" else "ader_tab_update_kd", ptr(D["rep_bf"]), ptr(D["rep_lo"]),
-                     *((ptr(img),) if self.x3_update == "tab16" else ()), self.item_num, D["Bp"], K["row0"], H, D["N"], K["Np"],
-                     ptr(D["off"]), ptr(ids), ptr(order), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))), ptr(tids),
+                call("ader_tab_update_x3_kd", ptr(D["rep_bf"]), ptr(D["rep_lo"]), ptr(img), self.item_num, D["Bp"], K["row0"], H, D["N"],
+                     K["Np"], ptr(D["off"]), ptr(ids), ptr(order), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))), ptr(tids),
                      ptr(torder), tids.numel(), ptr(tmeta), ptr(D["wrow"]), ptr(K["teacher"]), K["teacher"].stride(0), ptr(K["trow"]),
                      ptr(K["tlse2"]), ptr(self.theta), ptr(self.adam_m), ptr(self.adam_v), lr_t, self.beta1, self.beta2, self.eps, st)
-            elif self.lx3 and self.x3_update == "tab16":
+            elif self.lx3:
                 call("ader_tab_update_x3", ptr(D["rep_bf"]), ptr(D["rep_lo"]), ptr(img), self.item_num, D["B"], D["Bp"], H, D["N"],
                      ptr(D["off"]), ptr(ids), ptr(order), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))), ptr(tids),
                      ptr(torder), tids.numel(), ptr(tmeta), ptr(D["wrow"]), ptr(self.theta), ptr(self.adam_m), ptr(self.adam_v), lr_t,
                      self.beta1, self.beta2, self.eps, 0, -1, ptr(D.get("extra")), st)
-            elif self.lx3 or (self.bf16_update == "resident" and not D.get("kd")):
-                call("ader_tab_update", ptr(D["rep_bf"]), ptr(D["rep_lo"]), ptr(self.shadow), self.item_num, D["B"], D["Bp"], H, D["N"],
+            elif self.bf16_update == "resident" and not D.get("kd"):
+                call("ader_tab_update", ptr(D["rep_bf"]), ptr(self.shadow), self.item_num, D["B"], D["Bp"], H, D["N"],
                      ptr(D["off"]), ptr(ids), ptr(order), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))), ptr(tids),
                      ptr(torder), tids.numel(), ptr(tmeta), ptr(D["wrow"]), ptr(self.theta), ptr(self.adam_m), ptr(self.adam_v), lr_t,
                      self.beta1, self.beta2, self.eps, 0, -1, ptr(D.get("extra")), st)

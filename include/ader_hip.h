@@ -355,9 +355,6 @@ int ader_tab_grad_kd(const void* rep_hi, const void* rep_lo, const float* emb, i
  * [Bp,168]; ader_x3_rep_image_bytes(Bp) bytes, 16-byte aligned; Bp % 32 == 0).  Replaces the dense-Adam + table-gradient op
  * sites ADER.py:91-96 for the item table. */
 int ader_x3_rep_image_bytes(int Bp);
-/* kernel choice between the update's two kernels: catalogs of more than `tiles` 64-row tiles take a pair of tiles per workgroup (k_tab32x3),
- * smaller ones a single tile (k_tab16x3); default 0 = pairs always; negative: query only.  Returns the previous value. */
-int ader_x3_update_pair_min_tiles(int tiles);
 int ader_x3_rep_image(const void* rep_hi, const void* rep_lo, int Bp, void* img, void* stream);
 int ader_tab_update_x3(const void* rep_hi, const void* rep_lo, const void* rep_img, int item_num, int B, int Bp, int H, int N,
                        const float* off, const int* sp_ids, const int* sp_rows, int n_sp, const float* sp_src, float sp_scale,
@@ -378,7 +375,7 @@ int ader_tab_update_x3_kd_range(const void* rep_hi, const void* rep_lo, const vo
                           float* adam_m, float* adam_v, float lr_t, float beta1, float beta2, float eps, int tile_begin,
                                 int tile_count, void* stream);
 /* The bf16-mode form over 128-row tiles: the GEMM operand is the tile's bf16 shadow rows (`shadow` is read AND rewritten) and the
- * sorted lists are addressed through their 64-id bucket offsets sp_start / tg_start.  Faster than ader_tab_update(rep_lo = NULL) at
+ * sorted lists are addressed through their 64-id bucket offsets sp_start / tg_start.  Faster than ader_tab_update at
  * H = 150 on MI355X although it reads 336 B more per row (measurements: DESIGN.md). */
 int ader_tab_update_sh(const void* rep_bf, void* shadow, int item_num, int B, int Bp, int H, int N, const float* off,
                        const int* sp_ids, const int* sp_rows, const int* sp_start, int n_sp, const float* sp_src,
@@ -497,30 +494,23 @@ int ader_step_plan_failed_op(const AderStepPlan* plan);
 
 /* ---- cross-check kernels: NOT part of the product library.  Built only into libader_xcheck.so (ader_amd/build.py compiles
  *      table_update.hip and herding.hip a second time with -DADER_XCHECK) and loaded only by the tests that compare kernel against
- *      kernel: the round-2 fused table update on 64-row tiles (x3 with rep_lo != NULL, bf16 "resident" form with rep_lo == NULL) and
- *      the generic herding kernel under its own name. ------------------------------------------------------------------------------- */
+ *      kernel: the round-2 fused table update on 64-row tiles in its bf16 "resident" form and the generic herding kernel under
+ *      its own name. -------------------------------------------------------------------------------------------------------- */
 #ifdef ADER_XCHECK
 /* Fused table update: table-gradient GEMM + sparse terms (input-embedding rows sp_*, one-hot targets tg_*, both sorted by
  * item id) + tf.train.AdamOptimizer (ADER.py:96) on table rows 1..N of emb/adam_m/adam_v, one workgroup per 64-row tile.
  * The table gradient is never written to memory and the item parameters are read ONCE (GEMM operand and Adam input come
- * from the same LDS-resident tile in bf16 mode).  lr_t = lr*sqrt(1-beta2^t)/(1-beta1^t).
- * rep_lo != NULL selects x3 mode.  shadow: bf16 [item_num+1][168] copy of the table, rows rewritten after the update
- * (NULL: none; never written in x3 mode).  extra_grad: dense fp32 gradient [item_num+1, H] (table layout) added row by row
- * before the update, or NULL -- the table gradient of rows that did not go through this path (distilled exemplar rows,
- * ADER.py:132-137).
+ * from the same LDS-resident tile).  lr_t = lr*sqrt(1-beta2^t)/(1-beta1^t).
+ * shadow: bf16 [item_num+1][168] copy of the table, rows rewritten after the update (NULL: none).  extra_grad: dense fp32
+ * gradient [item_num+1, H] (table layout) added row by row before the update, or NULL -- the table gradient of rows that did
+ * not go through this path (distilled exemplar rows, ADER.py:132-137).
  * Bucket layout of the sorted lists: bucket j covers ids [g*j + id0, g*(j+1) + id0) with g = ader_fused_bucket_gran(),
  * id0 = ader_fused_bucket_id0(). */
-int ader_tab_update(const void* rep_hi, const void* rep_lo, void* shadow, int item_num, int B, int Bp, int H, int N,
-                    const float* off, const int* sp_ids, const int* sp_rows, int n_sp, const float* sp_src, float sp_scale,
-                    const int* tg_ids, const int* tg_rows, int n_tg, const int* tile_meta, const float* wrow, float* emb,
-                    float* adam_m, float* adam_v, float lr_t, float beta1, float beta2, float eps, int tile_begin,
-                    int tile_count, const float* extra_grad, void* stream);
-/* ... and for a DISTILLED step at float32 grade (x3; layout and arguments as ader_lx3_fwd_kd left them; ADER.py:132-137) */
-int ader_tab_update_kd(const void* rep_hi, const void* rep_lo, int item_num, int Bp, int kd_row0, int H, int N, int Np,
-                       const float* off, const int* sp_ids, const int* sp_rows, int n_sp, const float* sp_src, float sp_scale,
-                       const int* tg_ids, const int* tg_rows, int n_tg, const int* tile_meta, const float* wrow,
-                       const float* teacher, long ldt, const int* trow, const float* tlse2, float* emb, float* adam_m,
-                       float* adam_v, float lr_t, float beta1, float beta2, float eps, void* stream);
+int ader_tab_update(const void* rep_hi, void* shadow, int item_num, int B, int Bp, int H, int N, const float* off,
+                    const int* sp_ids, const int* sp_rows, int n_sp, const float* sp_src, float sp_scale, const int* tg_ids,
+                    const int* tg_rows, int n_tg, const int* tile_meta, const float* wrow, float* emb, float* adam_m,
+                    float* adam_v, float lr_t, float beta1, float beta2, float eps, int tile_begin, int tile_count,
+                    const float* extra_grad, void* stream);
 /* the generic kernel for any H <= 256 (one 256-thread workgroup per group, D streamed from L2 every iteration; D needs only
  * n_total*H floats): what ader_herding_select runs for H != 150, exported for kernel-vs-kernel checks and A/B timing */
 int ader_herding_select_generic(const float* rep, const long* seg, const int* quota, const int* max_steps, int G, long n_total,

@@ -124,7 +124,7 @@ LSE_BOUND, LOSS_BOUND, DREP_BOUND, M_BOUND, V_BOUND, THETA_BOUND = 1e-6, 5e-7, 1
 
 
 @pytest.mark.parametrize("n_items", [N, N - 75])
-def test_x3_headline_kernels_against_float64_at_full_size(batch, n_items):
+def test_x3_fused_step_against_float64_at_full_size(batch, n_items):
     """The credited kernels AT the credited size (B = 512, N = 10^6: k_lx3p's 31,250 table blocks, k_tab32x3's 7,813 tile
     pairs, the last one half a pair; N - 75: a ragged tail tile): one fused train step of the float32-grade path against a
     float64 restatement computed from the same parameters and the device's own representation / input-gradient rows --
@@ -137,7 +137,7 @@ def test_x3_headline_kernels_against_float64_at_full_size(batch, n_items):
     pos[0] = n_items                                  # a label and an input position in the tail tile
     seq[7, -1] = n_items
     eng = _engine("x3")
-    assert eng.lx3 and eng.x3_update == "tab16"
+    assert eng.lx3 and eng.fuse_adam                  # the fused x3 update (k_tab32x3): its only route
     E0 = eng.param("emb").detach().clone()            # [N+1, H] before the step
     lr = 5e-4
     loss = eng.train_step(seq, pos, n_items, lr, rate=0.3)

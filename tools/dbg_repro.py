@@ -1,5 +1,5 @@
 """Is the headline step bitwise reproducible between two engines of one process?  (dev tool)  usage: dbg_repro.py [flags...]
-flags: nolists (lists on the main stream), nolate (small launches on the main stream), nocache.  (This tool found the rare wrong
+flags: nolate (small launches on the main stream), nocache, many (eight engines instead of four).  (This tool found the rare wrong
 vectors of the removed k_tabp kernel: the first engine of a cold process differed from the next three in 3-8 table rows.)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,8 +21,6 @@ outs = []
 NE = 8 if "many" in flags else 4
 for rep in range(NE):
     eng = Engine(N + 50, maxlen=T, hidden_units=H, num_blocks=2, num_heads=1, seed=0, logits_dtype="x3")
-    if "nolists" in flags:
-        eng.lists_side_stream = False
     if "nolate" in flags:
         eng.late_side_stream = False
     if "nocache" in flags:

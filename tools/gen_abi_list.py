@@ -21,8 +21,8 @@ if cur:
 n = sum(len(c) for _, c in out)
 print("## Exported symbols\n")
 print("`nm -D ader_amd/libader_hip.so` == the declarations of `include/ader_hip.h` == this list (%d functions; held equal by\n"
-      "`tests/test_abi_exports.py`).  The cross-check kernels of the tests (`ader_tab_update`, `ader_tab_update_kd`,\n"
-      "`ader_herding_select_generic`) are NOT here: they are built into `libader_xcheck.so` only (`-DADER_XCHECK`).\n" % n)
+      "`tests/test_abi_exports.py`).  The cross-check kernels of the tests (`ader_tab_update`, `ader_herding_select_generic`)\n"
+      "are NOT here: they are built into `libader_xcheck.so` only (`-DADER_XCHECK`).\n" % n)
 for t, c in out:
     if c:
         print("* **%s** — %s" % (t, ", ".join("`%s`" % x for x in dict.fromkeys(c))))
