@@ -262,12 +262,12 @@ class DataParallel:
         dist.all_reduce(eng.loss, group=self.group)
         H = eng.H
         table_span = eng.layout["pos"][0]
-        works, eng._early = eng._early, None
+        sx = eng._step
+        works, sx.early = sx.early, None
         if works is None:
             allreduce_flat(eng.grad, (self.max_item + 1) * H, table_span, group=self.group)
             return
-        seq, dx = eng._dp_rows
-        eng._dp_rows = None
+        (seq, dx), sx.dp_rows = sx.dp_rows, None
         W = self.world
         ids_g = torch.empty(W * seq.numel(), dtype=seq.dtype, device=seq.device)
         rows_g = torch.empty(W * dx.numel(), dtype=dx.dtype, device=dx.device)

@@ -15,23 +15,32 @@ class _Backward:
         backward pass) and issued as one batched launch by _atb_flush.  pack: the operands are in tile order (packed session
         kernels): the plan tells the product which rows exist."""
         if self.gemm_x3:
-            self._atb_q.append((A, G, self._gp[wname], self._gp[bname], M, pack))
-            if len(self._atb_q) == 16:
-                self._atb_flush()
+            self._atb_put((A, G, self._gp[wname], self._gp[bname], M, pack))
             return
         call("ader_gemm_atb", ptr(A), ptr(G), ptr(slab), self._gp[wname], self._gp[bname], M, self.H, self._stream())
+
+    def _settle_loss(self):
+        """The loss sum a deferred step still owes (StepState.pending_loss), on the current stream."""
+        pl_, self._step.pending_loss = self._step.pending_loss, None
+        call("ader_lbf_sum", ptr(pl_[0]), pl_[1], ptr(self.loss), self._stream())
+
+    def _atb_put(self, item):
+        q = self._step.atb_q
+        q.append(item)
+        if len(q) == 16:
+            self._atb_flush()
 
     def _late_call(self, name, *args):
         """A launch whose result only feeds the small-parameter update: issued now, or queued for the side stream that runs
         beside the fused table update (_fused_table_adam)."""
-        if self._late_on:
-            self._late.append((name, args))
+        if self._step.late_on:
+            self._step.late.append((name, args))
         else:
             call(name, *args, self._stream())
 
     def _flush_late(self):
         """Issue the queued small launches; the LayerNorm partial reductions of all blocks go out as ONE batched launch."""
-        late, self._late = self._late, []
+        late, self._step.late = self._step.late, []
         red = [a for n, a in late if n == "ader_reduce_slabs"]
         if len(red) > 1:
             for i0 in range(0, len(red), 8):        # (a launch takes up to 8 jobs: 2 per block + the final LayerNorm)
@@ -46,7 +55,7 @@ class _Backward:
             call(name, *args, self._stream())
 
     def _atb_flush(self):
-        q, self._atb_q = self._atb_q, []
+        q, self._step.atb_q = self._step.atb_q, []
         if not q:
             return
         n = len(q)
@@ -81,9 +90,9 @@ class _Backward:
         call("ader_build_rowinfo", ptr(pos), n_train, ptr(ex_pos), ptr(ex_trow), n_ex, N, Np, float(w_train), float(w_ex), Bp,
              ptr(lab), ptr(ncol), ptr(wrow), ptr(trow), st)
         if teacher is not None and n_ex > 0:
-            self._teacher_lse(teacher, Np)
+            tlse_all = self._teacher_lse(teacher, Np)
             tlse.zero_()
-            tlse[n_train:n_train + n_ex] = self._tlse_all[trow[n_train:n_train + n_ex].long()]
+            tlse[n_train:n_train + n_ex] = tlse_all[trow[n_train:n_train + n_ex].long()]
             tptr, ldt = ptr(teacher), teacher.stride(0)
         else:
             tlse.zero_()
@@ -91,16 +100,26 @@ class _Backward:
         return Bp, (ptr(lab), ptr(ncol), ptr(wrow), ptr(trow), ptr(tlse), tptr, ldt)
 
     def _teacher_lse(self, teacher, Np):
-        """Natural log-sum-exp of every stored teacher row over its Np columns (self._tlse_all [E_all]).  The teacher logits of an
-        exemplar are fixed for a whole period, so this runs once per teacher tensor and is gathered per step."""
+        """Natural log-sum-exp of every stored teacher row over its Np columns ([E_all]).  The teacher logits of an exemplar are
+        fixed for a whole period: computed once per teacher tensor (Engine._tlse_key outlives the steps), gathered per step.  The result
+        is WORKSPACE: plans hold its address, so an equal-size teacher lands in the same memory and a new size retires them (_ws_gen)."""
         key = (teacher.data_ptr(), tuple(teacher.shape), teacher._version)
-        if getattr(self, "_tlse_key", None) != key:
-            E_all = teacher.shape[0]
+        E_all = teacher.shape[0]
+        tlse_all = self.buf("tlse_all", (E_all,))
+        if self._tlse_key != key:
             allrows = torch.arange(E_all, dtype=torch.int32, device=self.device)
-            self._tlse_all = torch.empty(E_all, dtype=torch.float32, device=self.device)
-            call("ader_row_lse", ptr(teacher), teacher.stride(0), Np, ptr(allrows), E_all, ptr(self._tlse_all), self._stream())
+            call("ader_row_lse", ptr(teacher), teacher.stride(0), Np, ptr(allrows), E_all, ptr(tlse_all), self._stream())
             self._tlse_key = key
-        return self._tlse_all
+        return tlse_all
+
+    def _kd_form(self, teacher, ex_trow, n_train, n_ex, N):
+        """The form of a distilled batch: (ex_trow as an int32 device tensor, default one teacher row per exemplar row in order; the
+        complaint about a teacher the kernels cannot read, or None; whether ALL rows fit the flash path and the catalog has not shrunk)."""
+        ex_trow = self._dev_i32(ex_trow if ex_trow is not None else np.arange(n_ex))
+        err = (None if teacher.dtype == torch.float32 and teacher.stride(1) == 1 and teacher.shape[1] <= N else
+               "exemplar_logits must be float32 [*, Np <= max_item], unit stride along the items")
+        cap = self.MAX_ROWS_FAST if self.lfast else self.MAX_ROWS
+        return ex_trow, err, err is None and ((n_train + 127) // 128 + (n_ex + 127) // 128) * 128 <= cap and N >= self._grad_hi
 
     # ---------------------------------------------------------------------------------------- train step
     def loss_and_grad(self, seq, pos, max_item, *, ex_pos=None, teacher=None, ex_trow=None, lambda_=0.0, rate=0.0,
@@ -111,11 +130,11 @@ class _Backward:
         the gradient of every parameter in self.grad.  (_defer_table, the fused-update form train_step uses: the loss scalar is
         summed beside the table update, so self.loss is final only after _fused_table_adam -- or the next call here.)"""
         self._refresh_stream()
-        if self._pending_loss is not None:
+        sx = self._step if self._in_step else self._begin_step()
+        if sx.pending_loss is not None:
             # a deferred step whose fused update never ran (an exception between the two calls, or loss_and_grad(_defer_table=True)
             # used on its own): its loss sum is still owed -- settle it before the row losses are overwritten
-            call("ader_lbf_sum", ptr(self._pending_loss[0]), self._pending_loss[1], ptr(self.loss), self._stream())
-            self._pending_loss = None
+            self._settle_loss()
         seq = self._seq_in(seq)
         pos = self._dev_i32(pos)
         B, T, H, L = seq.shape[0], self.T, self.H, self.L
@@ -127,13 +146,12 @@ class _Backward:
         N = int(max_item)
         _check(1 <= N <= self.item_num, "max_item must be in [1, item_num = %d] (got %d)" % (self.item_num, N))
         _check(0 <= n_train <= B, "pos has %d rows but input_seq only %d" % (n_train, B))
-        Np = 0
+        Np, kd_flash = 0, False
         if n_ex > 0:
             if teacher is not None:
-                ex_trow = self._dev_i32(ex_trow if ex_trow is not None else np.arange(n_ex))
+                ex_trow, err, kd_flash = self._kd_form(teacher, ex_trow, n_train, n_ex, N)
+                _check(err is None, err)
                 Np = teacher.shape[1]
-                _check(teacher.dtype == torch.float32 and teacher.stride(1) == 1 and Np <= N,
-                       "exemplar_logits must be float32 [*, Np <= max_item], unit stride along the items")
             else:
                 ex_pos = self._dev_i32(ex_pos)
                 _check(ex_pos.shape[0] == n_ex, "exemplar_pos has %d rows, the batch %d exemplar rows" % (ex_pos.shape[0], n_ex))
@@ -148,19 +166,18 @@ class _Backward:
                         and N >= self._grad_hi and self.dp_world == 1 and self.kd_split)
         # ... or (default, bf16 and x3 modes): ALL rows on the flash path -- the exemplar rows as their own 128-row chunks whose softmax runs
         # over the first Np items, with the teacher term as a second readout (forward) and a subtraction inside the fused update
-        kd_rows_fit = ((n_train + 127) // 128 + (n_ex + 127) // 128) * 128 <= cap
-        kd_fast = bool(split_kd and self.kd_fast and kd_rows_fit)
+        kd_fast = bool(split_kd and self.kd_fast and kd_flash)
         # the same forward without the fused update (data-parallel ranks, or no optimiser step): the table gradient is written
         # out (ader_tab_grad_kd) and takes the dense exchange
-        kd_fast_unfused = bool(not kd_fast and self.lfast and teacher is not None and n_ex > 0 and n_train > 0 and self.kd_fast
-                               and kd_rows_fit and N >= self._grad_hi and (self.dp_world > 1 or not _defer_table))
+        kd_fast_unfused = bool(not kd_fast and self.lfast and n_train > 0 and self.kd_fast and kd_flash
+                               and (self.dp_world > 1 or not _defer_table))
         if kd_fast or kd_fast_unfused:
             split_kd = False
         use_bf16 = self.lfast and (teacher is None or split_kd or kd_fast)
         defer = bool(_defer_table and use_bf16 and N >= self._grad_hi)
-        self._deferred = None
+        sx.deferred = None
         # data-parallel shard with exemplar rows: its train rows and its exemplar rows sit at different global positions
-        self.split_rows = n_train if (n_ex > 0 and getattr(self, "_ex_row0_set", False)) else None
+        self.split_rows = n_train if (n_ex > 0 and self._ex_row0_set) else None
         if use_bf16 and not (kd_fast or kd_fast_unfused):
             # the row descriptors of the flash logit kernels depend on the labels only: built BEFORE the forward stack (round 3: a
             # 5 us launch + a launch gap between k_seq_fwd and the logit forward, on the critical path of every step)
@@ -212,8 +229,8 @@ class _Backward:
                     call("ader_lx3_fwd_img_lnf", ptr(rep), emb, self.item_num, Bb, Bp, H, N, ptr(lab), ptr(wrow), ptr(rep_bf), ptr(rep_lo),
                          ptr(pm), ptr(pl), ptr(pO), ptr(lse), ptr(off), ptr(rowloss), None if late_loss else ptr(self.loss), ptr(drep),
                          ptr(img), lnf, st)
-                    self._img_ready = img is not None
-                    self._pending_loss = (rowloss, Bb) if late_loss else None
+                    sx.img_ready = img is not None
+                    sx.pending_loss = (rowloss, Bb) if late_loss else None
                 else:
                     call("ader_lbf_fwd", ptr(rep), ptr(self.shadow), self.item_num, Bb, Bp, H, N, ptr(lab), ptr(wrow), ptr(rep_bf),
                          ptr(pm), ptr(pl), ptr(pO), ptr(lse), ptr(off), ptr(rowloss), ptr(self.loss), ptr(drep), st)
@@ -251,14 +268,14 @@ class _Backward:
                 call("ader_logits_bwd_drep", ptr(rep), emb, B, Bp, H, N, *ri, ptr(lse), ptr(slab), ptr(drep), st)
             with self._sec("logits_bwd_demb"):
                 call("ader_logits_bwd_demb", ptr(rep), emb, B, Bp, H, N, *ri, ptr(lse), ptr(demb), st)
-        self._early = None
+        sx.early = None
         if not defer and self.grad_early_hook is not None:
-            self._early = self.grad_early_hook(self, N)       # async all-reduce of demb: overlaps the blocks backward below
+            sx.early = self.grad_early_hook(self, N)          # async all-reduce of demb: overlaps the blocks backward below
         dx = self._blocks_backward(seq, drep, defer, demb)
-        if self._early is not None:
-            self._dp_rows = (seq, dx)                         # per-position input-gradient rows: exchanged and scattered in the hook
+        if sx.early is not None:
+            sx.dp_rows = (seq, dx)                            # per-position input-gradient rows: exchanged and scattered in the hook
         if defer:
-            self._deferred = dict(seq=seq, g=dx, B=(n_train if split_kd else B), Bp=Bp, N=N, rep_bf=rep_bf, rep_lo=rep_lo, off=off,
+            sx.deferred = dict(seq=seq, g=dx, B=(n_train if split_kd else B), Bp=Bp, N=N, rep_bf=rep_bf, rep_lo=rep_lo, off=off,
                                   lab=lab, wrow=wrow, extra=extra)
         return self.loss
 
@@ -269,6 +286,7 @@ class _Backward:
         loss = w (lse - rep.O2) and dRep = w (O1/l - O2); the table gradient w (softmax(s) - softmax(t))^T rep is formed inside the
         fused update (ader_tab_update_sh_kd), which reads the teacher tile a second time.  Nothing [rows, N]-sized is materialised."""
         st = self._stream()
+        sx = self._step
         H = self.H
         B = n_train + n_ex
         Bt, Bk = (n_train + 127) // 128 * 128, (n_ex + 127) // 128 * 128
@@ -297,8 +315,8 @@ class _Backward:
                      ptr(ex_trow), ptr(teacher), teacher.stride(0), ptr(tlse_all), float(w_train), float(w_ex), ptr(lab), ptr(wrow),
                      ptr(trow), ptr(tlse2), ptr(rep_bf), ptr(rep_lo), ptr(pm), ptr(pl), ptr(pO), ptr(pO2), ptr(lse), ptr(off),
                      ptr(rowloss), None if late_loss else ptr(self.loss), ptr(drep), ptr(img), self._lnf_desc(B), st)
-                self._img_ready = img is not None
-                self._pending_loss = (rowloss, Bp) if late_loss else None
+                sx.img_ready = img is not None
+                sx.pending_loss = (rowloss, Bp) if late_loss else None
             else:
                 call("ader_lbf_fwd_kd", ptr(rep), ptr(self.shadow), self.item_num, n_train, n_ex, Bt, Bp, H, N, Np, ptr(pos),
                      ptr(ex_trow), ptr(teacher), teacher.stride(0), ptr(tlse_all), float(w_train), float(w_ex), ptr(lab), ptr(wrow),
@@ -310,24 +328,25 @@ class _Backward:
             with self._sec("logits_bwd_demb"):
                 call("ader_tab_grad_kd", ptr(rep_bf), ptr(rep_lo), self._pp["emb"], self.item_num, Bp, Bt, H, N, Np, ptr(lab), ptr(wrow),
                      ptr(off), ptr(teacher), teacher.stride(0), ptr(trow), ptr(tlse2), ptr(demb), st)
-            self._early = None
+            sx.early = None
             if self.grad_early_hook is not None:
-                self._early = self.grad_early_hook(self, N)
+                sx.early = self.grad_early_hook(self, N)
             dx = self._blocks_backward(seq, drep, False, demb)
-            if self._early is not None:
-                self._dp_rows = (seq, dx)
+            if sx.early is not None:
+                sx.dp_rows = (seq, dx)
             return self.loss
         self._lists_async(seq, lab, N)            # one-hot targets in the padded row numbering (label 0 = none)
         dx = self._blocks_backward(seq, drep, True, None)
-        self._deferred = dict(seq=seq, g=dx, B=Bp, Bp=Bp, N=N, rep_bf=rep_bf, rep_lo=rep_lo, off=off, lab=lab, wrow=wrow, extra=None,
+        sx.deferred = dict(seq=seq, g=dx, B=Bp, Bp=Bp, N=N, rep_bf=rep_bf, rep_lo=rep_lo, off=off, lab=lab, wrow=wrow, extra=None,
                               kd=dict(row0=Bt, Np=Np, teacher=teacher, trow=trow, tlse2=tlse2))
         return self.loss
 
-    def _blocks_backward(self, seq, drep, defer, demb):
+    def _blocks_backward(self, seq, drep, defer, demb, late=False):
         """Backward of the final LayerNorm, the blocks and the prologue from drep [B,H] (gradient of the loss w.r.t. the
         representation).  Fills the gradients of every non-table parameter; the table's sparse term goes into demb (dense
-        path) or, with `defer`, stays as per-position rows in the returned dx [B*T,H] for the fused table update."""
-        A = self._act
+        path) or, with `defer`, stays as per-position rows in the returned dx [B*T,H] for the fused table update.  `late`: the small
+        launches are queued with dp_world > 1 too (the catalog-sharded step runs them under its row exchange)."""
+        A, sx = self._act, self._step
         B, T, H, L = A["B"], self.T, self.H, self.L
         rows = B * T
         st = self._stream()
@@ -345,15 +364,15 @@ class _Backward:
         else:
             dx = self.buf("dx_a", (rows, H), zero=True)
             dxn = self.buf("dx_b", (rows, H), zero=True)
-        self._late_on = bool(defer and (self.dp_world == 1 or self._late_force) and self.seq_fused and self.late_side_stream)
-        lnf_done, self._lnf_done = self._lnf_done, None
+        sx.late_on = bool(defer and (self.dp_world == 1 or late) and self.seq_fused and self.late_side_stream)
+        lnf_done, sx.lnf_done = sx.lnf_done, None
         if self.prune_last and lnf_done is not None and lnf_done[2] == B:
             # the merge launch of the logit forward has already written dx of the final LayerNorm and the per-row gamma / beta partials
             dxl, fslab = lnf_done[0], lnf_done[1]
             self._late_call("ader_reduce_slabs", ptr(fslab), 2 * H, B, H, 1, H, gp["lnf_g"], gp["lnf_b"])
         elif self.prune_last:
             dxl = self.buf("dx_L", (B, H))        # gradient of the final block's output row T-1 (compact)
-            if self._late_on:       # gamma / beta partials reduced later, beside the table update (their own slab buffer)
+            if sx.late_on:          # gamma / beta partials reduced later, beside the table update (their own slab buffer)
                 G = call("ader_ln_bwd_slabs", B)
                 fslab = self.buf("lnf_slab", (G * 2 * H,))
                 call("ader_ln_bwd", ptr(drep), H, ptr(xL), H, pp["lnf_g"], ptr(A["meanf"]), ptr(A["stdf"]), None, 0, ptr(dxl), H,
@@ -430,38 +449,34 @@ class _Backward:
             self._atb(S["x"], dK, p + "wk", p + "bk", wslab, rows)
             self._atb(S["x"], dV, p + "wv", p + "bv", wslab, rows)
             dx, dxn = dxn, dx
-        if not self._late_on:
+        if not sx.late_on:
             self._atb_flush()
         self._last_g = dx       # per-position gradient rows of the input embeddings (tests: column-sum checks)
         if pk is not None:
             # (the packed chain wrote the REAL positions of dx only: the positional gradient sums those; every other consumer
             #  addresses dx through the id lists, which leave the padding out)
             self._late_call("ader_pos_grad_packed", ptr(dx), ptr(pk["slen"]), gp["pos"], B, T, H)
-            if not defer and self._early is None:
+            if not defer and sx.early is None:
                 lab0 = self.buf("dp_lab0", (1,), torch.int32, zero=True)
                 ids_s, order, sp_start, _, _, _, _ = self._sparse_lists(seq, lab0, self.item_num)
                 call("ader_scatter_rows_ordered", ptr(ids_s), ptr(order), ptr(sp_start), sp_start.numel() - 1, ptr(dx), H, self.V,
                      float(np.sqrt(np.float32(H))), ptr(demb), st)
-        elif defer:
+        elif defer and fused_emb:
             # (block 0's ader_seq_bwd_qkv has already applied the prologue mask / dropout to the rows: seq = NULL)
-            if fused_emb:
-                self._late_call("ader_embed_bwd_rows", None, ptr(dx), gp["pos"], B, T, H, self.V, *A["d_emb"].args())
-            else:
-                call("ader_embed_bwd_rows", ptr(seq), ptr(dx), gp["pos"], B, T, H, self.V, *A["d_emb"].args(), st)
-        elif self._early is not None:
-            # the table gradient is being all-reduced: leave the masked rows in dx (scattered for all ranks after the reduction)
-            call("ader_embed_bwd_rows", None if fused_emb else ptr(seq), ptr(dx), gp["pos"], B, T, H, self.V, *A["d_emb"].args(), st)
+            self._late_call("ader_embed_bwd_rows", None, ptr(dx), gp["pos"], B, T, H, self.V, *A["d_emb"].args())
         else:
-            # unfused single-process path (exact-f32 logits, EWC, loss_and_grad without the optimiser): mask / dropout on the rows,
-            # then the rows are added into the table gradient bucket by bucket in position order -- no float atomics, so this path
-            # is bitwise reproducible too (the reference sets TF_DETERMINISTIC_OPS, main.py:121-122)
+            # mask / dropout on the rows.  With the table gradient being all-reduced they stay in dx (scattered for all ranks after the
+            # reduction); on the unfused single-process path (exact-f32 logits, EWC, loss_and_grad without the optimiser) they are then
+            # added into the table gradient bucket by bucket in position order -- no float atomics, so this path is bitwise
+            # reproducible too (the reference sets TF_DETERMINISTIC_OPS, main.py:121-122)
             call("ader_embed_bwd_rows", None if fused_emb else ptr(seq), ptr(dx), gp["pos"], B, T, H, self.V, *A["d_emb"].args(), st)
-            lab0 = self.buf("dp_lab0", (1,), torch.int32, zero=True)
-            ids_s, order, sp_start, _, _, _, _ = self._sparse_lists(seq, lab0, self.item_num)
-            call("ader_scatter_rows_ordered", ptr(ids_s), ptr(order), ptr(sp_start), sp_start.numel() - 1, ptr(dx), H, self.V,
-                 float(np.sqrt(np.float32(H))), ptr(demb), st)
+            if not defer and sx.early is None:
+                lab0 = self.buf("dp_lab0", (1,), torch.int32, zero=True)
+                ids_s, order, sp_start, _, _, _, _ = self._sparse_lists(seq, lab0, self.item_num)
+                call("ader_scatter_rows_ordered", ptr(ids_s), ptr(order), ptr(sp_start), sp_start.numel() - 1, ptr(dx), H, self.V,
+                     float(np.sqrt(np.float32(H))), ptr(demb), st)
         tb.__exit__(None, None, None)
-        self._late_on = False
+        sx.late_on = False
         return dx
 
     def _bwd_block_fused(self, l, S, seq, dxo, dxn, M, B, emb_bwd, d_emb):
@@ -522,7 +537,7 @@ class _Backward:
         M = B if pruned else rows
         mpk = None if pruned else pk           # the compact tensors of a pruned block are plain [B, H]
         # (cached only on the default training path: small launches queued for the side stream, weight gradients batched)
-        cacheable = bool(self.cache_descriptors and self._late_on and self.gemm_x3)
+        cacheable = bool(self.cache_descriptors and self._step.late_on and self.gemm_x3)
         ck = ("bwdp", l, B, ptr(dxo), ptr(dxn), bool(emb_bwd))
         ent = self._dc(ck) if cacheable else None
         if ent is not None and ent[0] is S and ent[1] is pk and ent[2] is d_emb:
@@ -531,18 +546,14 @@ class _Backward:
             f.d_ffn1, f.d_ffn2 = S["d1"].c, S["d2"].c
             q.d_emb = d_emb.c
             call("ader_seqp_bwd_ffn", ctypes.byref(f), pk["ref"], mt, st)
-            self._late.append(late2)
+            self._step.late.append(late2)
             for it in atbs2:
-                self._atb_q.append(it)
-                if len(self._atb_q) == 16:
-                    self._atb_flush()
+                self._atb_put(it)
             call(attn_name, *attn_args, st)
             call("ader_seqp_bwd_qkv", ctypes.byref(q), pk["ref"], mt, st)
-            self._late.append(late1)
+            self._step.late.append(late1)
             for it in atbs1:
-                self._atb_q.append(it)
-                if len(self._atb_q) == 16:
-                    self._atb_flush()
+                self._atb_put(it)
             return
         wp = lambda w: self.wbf.data_ptr() + self._widx[p + w] * self._wplane     # noqa: E731
         sfx = "L" if pruned else ""

@@ -83,6 +83,34 @@ class StepF(float):
         return o
 
 
+class StepState:
+    """What one train step hands from loss_and_grad to _blocks_backward to the update (_fused_table_adam*, _train_step_catalog,
+    dist.DataParallel).  Engine._step holds the current one; every public entry point that starts a step replaces it with a fresh
+    record (_State._begin_step), so a step never sees its predecessor's leftovers -- except the two fields marked SURVIVES."""
+    __slots__ = ("deferred", "pending_loss", "img_ready", "lists", "lists_seq", "late", "late_on", "atb_q", "lnf_done", "early",
+                 "dp_rows", "density", "keep_density", "held")
+
+    def __init__(self):
+        self.deferred = None        # fused update still owed: the operands loss_and_grad(_defer_table=True) leaves for _fused_table_adam*
+        # (rowloss, rows) of the loss sum that rides beside the table update.  SURVIVES: if the fused update never ran, the next entry
+        # point settles it (loss_and_grad)
+        self.pending_loss = None
+        self.img_ready = False      # the logit forward has already cut the operand images of the fused update
+        # id-bucketed sparse lists being built on the side lane (_lists_async -> _lists_wait); their inputs, alive until it has read them
+        self.lists, self.lists_seq = None, None
+        # (launcher, args) whose results only feed the small-parameter update, issued beside the table update (_late_call, _flush_late);
+        # queueing is on (set and cleared by _blocks_backward)
+        self.late, self.late_on = [], False
+        self.atb_q = []             # x3 mode: the weight-gradient products of a backward pass, issued as one launch
+        self.lnf_done = None        # (dxl, slab, B, descriptor): the logit forward's merge launch ran the final LayerNorm's backward
+        # replicated data parallel: the table all-reduces started under the blocks backward; (seq, dx), the rows exchanged after them
+        self.early, self.dp_rows = None, None
+        # fraction of real positions of a batch that came from the host (_seq_in; None = unknown); kept while a step being recorded
+        # re-enters with the device copy of that batch
+        self.density, self.keep_density = None, False
+        self.held = None            # SURVIVES: inputs of a replayed step, alive until the next step is enqueued behind it (_plan_run)
+
+
 class SectionTimer:
     """HIP-event timing of named launch groups on the stream the kernels are launched on (bench.py roofline leg).
     Events are recorded around each section; elapsed times are read back after a sync with collect()."""

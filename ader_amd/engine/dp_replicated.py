@@ -23,7 +23,7 @@ class _DpReplicated:
         Adam m/v of the table stay sharded.  The small parameters use a plain all-reduce."""
         import torch.distributed as dist
         self._refresh_stream()
-        D = self._deferred
+        D = self._step.deferred
         st = self._stream()
         W, r, grp = self.dp_world, self.dp_rank, self.dp_group
         H, B, Bp, N = self.H, D["B"], D["Bp"], D["N"]
@@ -45,7 +45,6 @@ class _DpReplicated:
             dist.all_reduce(self.grad[span:], group=grp)
             self._guard("sharded-update:loss", "all_reduce", self.loss.shape, self.loss.dtype)
             dist.all_reduce(self.loss, group=grp)
-        tiles = self.shard_items // 128
         ids, order, sp_start, tids, torder, tg_start, tmeta = self._sparse_lists(seq_g, lab_g, N)
         tiles = self.shard_items // 128
         with self._sec("logits_bwd_adam"):
@@ -65,7 +64,7 @@ class _DpReplicated:
             call("ader_adam_step", self.theta.data_ptr() + 4 * span, self.adam_m.data_ptr() + 4 * span,
                  self.adam_v.data_ptr() + 4 * span, self.grad.data_ptr() + 4 * span, self.P - span, lr_t, self.beta1, self.beta2,
                  self.eps, None, 0, H, st)
-        self._deferred = None
+        self._step.deferred = None
         self._mv_sharded = True
         self._advance_adam()
 

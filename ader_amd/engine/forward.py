@@ -55,7 +55,7 @@ class _Forward:
         x[:, -1, :] (ADER.py:85) and rows interact only through K/V, so the other T-1 rows of that block are dead work."""
         self._refresh_stream()
         if save:
-            self._lnf_done = None          # (a fused final-LayerNorm backward belongs to the forward it followed)
+            self._step.lnf_done = None     # (a fused final-LayerNorm backward belongs to the forward it followed)
         if self.seq_fused:
             if self._use_pack(seq):
                 return self._forward_packed(seq, training, rate, step, save)
@@ -205,12 +205,12 @@ class _Forward:
     def _seq_in(self, seq):
         """input_seq of a public entry point -> int32 device tensor.  A batch that arrives from the host (the reference-style feed
         dict) shows "auto" packing its density: the fraction of real positions."""
-        if isinstance(seq, torch.Tensor):
-            if not self._keep_density:         # (a step being recorded re-enters with the device copy of a batch whose density is known)
-                self._density_now = None
-        else:
+        s = self._step
+        if not isinstance(seq, torch.Tensor):
             a = np.asarray(seq)
-            self._density_now = float(np.count_nonzero(a)) / max(a.size, 1)
+            s.density = float(np.count_nonzero(a)) / max(a.size, 1)
+        elif not s.keep_density:
+            s.density = None
         return self._dev_i32(seq)
 
     def _use_pack(self, seq):
@@ -218,7 +218,7 @@ class _Forward:
             return False
         ps = self.pack_sessions
         if ps == "auto":
-            d = getattr(self, "_density_now", None)
+            d = self._step.density
             if d is None:
                 d = self.pack_density
             return d is not None and d <= self.PACK_DENSITY_MAX
@@ -246,7 +246,7 @@ class _Forward:
         # rows expected to exist (how the weight-gradient workgroups are shared out): this batch's own density when it came from the host,
         # else the feeder's announcement, else -- nothing known -- the densest batch "auto" would still pack (a low guess would share a
         # dense batch's products over too few workgroups: correct, but silently slow)
-        d = getattr(self, "_density_now", None)
+        d = self._step.density
         if d is None:
             d = self.pack_density if self.pack_density is not None else self.PACK_DENSITY_MAX
         est = int(min(n, max(64, 1.25 * d * B * T + 64)))
@@ -275,8 +275,7 @@ class _Forward:
         path, the tensors of the K / V side and of unpruned blocks in tile order ([B*64, ..], see include/ader_hip.h)."""
         B, T, H, L = seq.shape[0], self.T, self.H, self.L
         tag = "pt" if save else "pe"
-        ck = ("fwdp", tag, B, bool(training), float(rate), self.seed, self.row0, self.split_rows, self.row0_ex, self.pack_window,
-              self.pack_density, self.prune_last)
+        ck = ("fwdp", (tag, B, bool(training), float(rate), self.split_rows), self._mode_key())     # (split_rows: set per step from its shape)
         ent = self._dc(ck) if self.cache_descriptors else None
         if ent is not None:
             # same step shape as before: only the batch pointer and the dropout keys are new
@@ -356,12 +355,12 @@ class _Forward:
         """AderLnfBwd of the forward just saved (prune_last: xL / meanf / stdf are compact [B, ..]), or None when not fused."""
         A = self._act
         if not (self.prune_last and self.lx3):
-            self._lnf_done = None
+            self._step.lnf_done = None
             return None
         H = self.H
         dxl = self.buf("dx_L", (B, H))
         fslab = self.buf("lnf_slab_rows", (B * 2 * H,))
         c = _lib.AderLnfBwd()
         c.x, c.mean, c.std, c.gamma, c.dx, c.slab = ptr(A["xL"]), ptr(A["meanf"]), ptr(A["stdf"]), self._pp["lnf_g"], ptr(dxl), ptr(fslab)
-        self._lnf_done = (dxl, fslab, B, c)
+        self._step.lnf_done = (dxl, fslab, B, c)
         return ctypes.byref(c)

@@ -9,13 +9,12 @@ scalars (patches), the dropout keys (key = f(seed, step, site)) and the stream h
 `ader_step_enqueue(plan, inputs, step, main, side)`.
 
 A plan holds raw device pointers of workspace tensors: it is retired with the descriptor cache whenever the workspace allocates or
-evicts (`Engine._ws_gen`).  Everything that shapes the recorded arguments is part of the plan's key (`_Native._plan_key`); with
-`Engine.plan_verify` every replayed step is instead run through Python again, recorded, and compared slot by slot and descriptor
-byte by descriptor byte with what the plan would have issued (tests)."""
+evicts (`Engine._ws_gen`).  Its key is (tag, the step's shape, `Engine._mode_key()`): every switch and placement value that shapes a
+recorded argument.  With `Engine.plan_verify` every replayed step is instead run through Python again, recorded, and compared slot by
+slot and descriptor byte by descriptor byte with what the plan would have issued (tests)."""
 import ctypes
 import struct
 
-import numpy as np
 import torch
 
 from .. import _lib
@@ -194,27 +193,11 @@ class StepPlan:
             pass
 
 
-class _Slice:
-    """The tail of a device index array from address `p` on, with the three methods the recorder asks of an input tensor."""
-
-    def __init__(self, t, p):
-        self.t, self.p = t, p
-
-    def data_ptr(self):
-        return self.p
-
-    def numel(self):
-        return max(0, self.t.numel() - (self.p - self.t.data_ptr()) // self.t.element_size())
-
-    def element_size(self):
-        return self.t.element_size()
-
-
 class _Native:
     # ---------------------------------------------------------------------------------------- native step driver
     def _plan_state(self):
-        if getattr(self, "_plans", None) is None or self._plans_gen != self._ws_gen:
-            for p in (getattr(self, "_plans", None) or {}).values():
+        if self._plans_gen != self._ws_gen:
+            for p in self._plans.values():
                 if p is not None:
                     p.destroy()
             self._plans, self._plans_gen = {}, self._ws_gen
@@ -224,15 +207,13 @@ class _Native:
         """The step forms whose launch sequence is pure launcher calls + stream edges (no torch kernel, no collective, no host read)."""
         return (self.native_step and self.dp_world == 1 and self.lx3 and self.lfast and self.seq_fused and self.fuse_adam
                 and self.kd_fast and self.grad_hook is None and self.grad_early_hook is None
-                and self.timer is None and (self.ewc is None or self.ewc["lam"] == 0.0) and self._pending_loss is None
+                and self.timer is None and (self.ewc is None or self.ewc["lam"] == 0.0) and self._step.pending_loss is None
                 and not (kw.get("teacher") is not None and kw.get("ex_pos") is not None))
 
-    def _plan_key(self, tag, B_all, n_train, N, lr, rate, lambda_, teacher, has_expos, n_tg, n_eg, pack, extra=()):
+    def _plan_key(self, tag, seq, n_train, N, rate, lambda_, teacher, has_expos, n_tg, n_eg, extra=()):
         tk = None if teacher is None else (teacher.data_ptr(), tuple(teacher.shape), teacher.stride(0))
-        return (tag, B_all, n_train, N, float(rate), float(lambda_), tk, has_expos, n_tg, n_eg, pack, self.row0, self.row0_ex,
-                getattr(self, "_ex_row0_set", False), self.seed, self.prune_last, self.late_side_stream, self.cache_descriptors,
-                self.pack_window, self.pack_density, self._grad_hi <= N,
-                self.beta1, self.beta2, self.eps, extra)
+        return (tag, (seq.shape[0], n_train, N, float(rate), float(lambda_), tk, has_expos, n_tg, n_eg, bool(self._use_pack(seq)), extra),
+                self._mode_key())
 
     def _native_step(self, seq, pos, max_item, lr, kw):
         """train_step through a launch plan; returns None when this step form is not plannable (the caller takes the Python path)."""
@@ -248,12 +229,10 @@ class _Native:
             return None
         if n_ex > 0:
             if teacher is not None:
-                ex_trow = self._dev_i32(ex_trow if ex_trow is not None else np.arange(n_ex))
-                Np = teacher.shape[1]
-                if not (teacher.dtype == torch.float32 and teacher.stride(1) == 1 and Np <= N and ex_trow.shape[0] == n_ex
-                        and ((n_train + 127) // 128 + (n_ex + 127) // 128) * 128 <= self.MAX_ROWS_FAST):
+                ex_trow, _, flash = self._kd_form(teacher, ex_trow, n_train, n_ex, N)
+                if not flash or ex_trow.shape[0] != n_ex:
                     return None
-                self._teacher_lse(teacher, Np)           # (once per teacher tensor: outside the plan)
+                self._teacher_lse(teacher, teacher.shape[1])           # (once per teacher tensor: outside the plan)
                 ex_pos = None
             elif ex_pos is not None:
                 ex_pos = self._dev_i32(ex_pos)
@@ -263,56 +242,55 @@ class _Native:
                 return None
         else:
             teacher = ex_pos = ex_trow = None
-        pack = bool(self._use_pack(seq))
-        key = self._plan_key("step", B_all, n_train, N, lr, kw.get("rate", 0.0), kw.get("lambda_", 0.0), teacher, ex_pos is not None,
-                             kw.get("n_train_global"), kw.get("n_ex_global"), pack)
+        key = self._plan_key("step", seq, n_train, N, kw.get("rate", 0.0), kw.get("lambda_", 0.0), teacher, ex_pos is not None,
+                             kw.get("n_train_global"), kw.get("n_ex_global"))
         kw2 = dict(kw)
         kw2.update(teacher=teacher, ex_pos=ex_pos, ex_trow=ex_trow)
         kw2.pop("ids_host", None)
         kw2.pop("pack_counts", None)
-        ins = ((IN_SEQ, seq), (IN_POS, pos), (IN_EXPOS, ex_pos), (IN_EXTROW, ex_trow), (IN_TEACHER, teacher))
-        return self._plan_run(key, ins, (), lr, lambda: self._train_step(seq, pos, N, lr, **kw2))
+        ins = tuple((slot, t.data_ptr(), t) for slot, t in ((IN_SEQ, seq), (IN_POS, pos), (IN_EXPOS, ex_pos), (IN_EXTROW, ex_trow),
+                                                            (IN_TEACHER, teacher)) if t is not None)
+        return self._plan_run(key, ins, lr, lambda: self._train_step(seq, pos, N, lr, **kw2))
 
-    def _plan_run(self, key, tensors, scalars, lr, python_step):
-        """Replay the plan of `key`, or run `python_step` under the recorder and keep its plan.  tensors: ((slot, tensor | None), ...)
-        the step's input tensors (patched by address range); scalars: ((slot, raw 64-bit value), ...)."""
+    def _fill_inputs(self, plan, ins, lr_bits):
+        inp = plan.inputs
+        for slot, addr, _ in ins:
+            inp[slot] = addr
+        inp[IN_LR] = lr_bits
+
+    def _plan_run(self, key, ins, lr, python_step):
+        """Replay the plan of `key`, or run `python_step` under the recorder and keep its plan.  ins: ((slot, address, tensor), ...): the
+        plan patches `address` in for the slot -- the start of `tensor` or a place inside it (an epoch's index array from the batch's
+        offset on); recorded pointers between there and the end of `tensor` become patches; `tensor` is kept alive."""
         plans = self._plan_state()
         plan = plans.get(key, False)
         step = self.global_step
         if plan and not self.plan_verify:
-            inp = plan.inputs
-            for slot, t in tensors:
-                if t is not None:
-                    inp[slot] = t.data_ptr()
-            for slot, v in scalars:
-                inp[slot] = v
-            inp[IN_LR] = _fbits(self._lr_t(lr))
-            self._held = tensors                          # inputs stay alive until the next step has been enqueued behind this one
+            self._fill_inputs(plan, ins, _fbits(self._lr_t(lr)))
+            self._step.held = ins                         # inputs stay alive until the next step has been enqueued behind this one
             plan.enqueue(step, self._main.cuda_stream, self._side.cuda_stream if self._side is not None else 0)
-            self.b1p = np.float32(self.b1p * np.float32(self.beta1))
-            self.b2p = np.float32(self.b2p * np.float32(self.beta2))
-            self.global_step += 1
+            self._advance_step()
             self.plan_hits += 1
             return self.loss
         if plan is None and not self.plan_verify:
             return python_step()                          # a form that could not be planned: not tried again until the workspace changes
         rec = _lib.recorder = Recorder()
         gen0 = self._ws_gen
-        self._keep_density = True
+        self._step.keep_density = True
         try:
             out = python_step()
         finally:
             _lib.recorder = None
-            self._keep_density = False
+            self._step.keep_density = False
         self.plan_misses += 1
         if self._ws_gen != gen0 or self._plans_gen != gen0:
             return out                                    # the step allocated workspace: pointers of this recording may be stale
         lanes = {self._main.cuda_stream: 0}
         if self._side is not None:
             lanes[self._side.cuda_stream] = 1
-        ranges = [(slot, t.data_ptr(), t.numel() * t.element_size()) for slot, t in tensors if t is not None]
+        ranges = [(slot, addr, t.data_ptr() + t.numel() * t.element_size() - addr) for slot, addr, t in ins]
         if plan:                                          # verify mode: this step ran through Python; compare with the plan's version
-            self._plan_compare(plan, rec.items, lanes, ranges, step, tensors, scalars)
+            self._plan_compare(plan, rec.items, lanes, ranges, step, ins)
             return out
         try:
             plans[key] = StepPlan(rec.items, lanes, ranges, self.seed, step, 1 + 3 * self.L)
@@ -321,16 +299,10 @@ class _Native:
             self.plan_errors.append(str(e))
         return out
 
-    def _plan_compare(self, plan, items, lanes, ranges, step, tensors, scalars):
+    def _plan_compare(self, plan, items, lanes, ranges, step, ins):
         """plan_verify: the Python-driven step just recorded vs. the plan's patched ops for the same inputs."""
-        inp = plan.inputs
-        for slot, t in tensors:
-            if t is not None:
-                inp[slot] = t.data_ptr()
-        for slot, v in scalars:
-            inp[slot] = v
         lr_bits = [_fbits(a) for n, args in items if n is not None for a in args if isinstance(a, StepF)]
-        inp[IN_LR] = lr_bits[0] if lr_bits else 0
+        self._fill_inputs(plan, ins, lr_bits[0] if lr_bits else 0)
         ops, blobs = plan.peek(step)
         ref_ops, ref_blobs, _, _ = lower(items, lanes, ranges, self.seed, step, 1 + 3 * self.L)
         _check(len(ref_ops) == plan.n_ops, "plan_verify: %d ops recorded, the plan holds %d" % (len(ref_ops), plan.n_ops))
@@ -369,6 +341,8 @@ class _Native:
         _check(0 < n_t <= Bt and 0 <= n_e <= Be and rows_t.dtype == torch.int32 and rows_t.shape[1] == T + 1 and idx_t.dtype == torch.int64,
                "train_step_fed: packed rows [*, maxlen+1] int32, int64 index arrays, 0 < n_t <= Bt, 0 <= n_e <= Be")
         kd = teacher is not None and n_e > 0
+        self._begin_step()
+        placement = self.row0, self.row0_ex, self._ex_row0_set          # (this step's own, below: the caller's come back after it)
         self._in_step = True
         try:
             seq = self.buf("fd_seq", (Bt + Be, T), torch.int32)
@@ -386,7 +360,6 @@ class _Native:
                     kw.update(teacher=teacher, ex_trow=ex_trow)
                 else:
                     kw.update(ex_pos=ex_pos)
-            self._density_now = None
 
             def python_step():
                 call("ader_feed_step", ptr(rows_t), pt, n_t, Bt, ptr(rows_e), pe, n_e, Be, T, ptr(seq), ptr(pos), ptr(ex_pos), ptr(ex_trow),
@@ -396,35 +369,14 @@ class _Native:
             N = int(max_item)
             if kd:
                 self._teacher_lse(teacher, teacher.shape[1])
-            ok = (self._native_ok(kw) and 1 <= N <= self.item_num and N >= self._grad_hi and
-                  (not kd or (teacher.dtype == torch.float32 and teacher.stride(1) == 1 and teacher.shape[1] <= N and
-                              ((Bt + 127) // 128 + (Be + 127) // 128) * 128 <= self.MAX_ROWS_FAST)))
-            if not ok:
+            if not (self._native_ok(kw) and 1 <= N <= self.item_num and N >= self._grad_hi
+                    and (not kd or self._kd_form(teacher, ex_trow, Bt, Be, N)[2])):
                 return python_step()
-            pack = bool(self._use_pack(seq))
-            key = self._plan_key("fed", Bt + Be, Bt, N, lr, rate, lambda_ if n_e > 0 else 0.0, teacher if kd else None, ex_pos is not None,
-                                 n_t, n_e, pack, (rows_t.data_ptr(), rows_e.data_ptr() if rows_e is not None else 0, Be))
-            # the index slices are patched by VALUE range of the whole epoch arrays (pt / pe point into them)
-            tens = ((IN_IDX_T, idx_t), (IN_IDX_E, idx_e if n_e > 0 else None))
-            return self._plan_run_fed(key, tens, pt, pe, lr, python_step)
+            key = self._plan_key("fed", seq, Bt, N, rate, lambda_ if n_e > 0 else 0.0, teacher if kd else None, ex_pos is not None,
+                                 n_t, n_e, (rows_t.data_ptr(), rows_e.data_ptr() if rows_e is not None else 0, Be))
+            # the two index pointers are inputs given by address: the epoch array from the batch's offset on
+            ins = ((IN_IDX_T, pt, idx_t),) + (((IN_IDX_E, pe, idx_e),) if n_e > 0 else ())
+            return self._plan_run(key, ins, lr, python_step)
         finally:
             self._in_step = False
-
-    def _plan_run_fed(self, key, tens, pt, pe, lr, python_step):
-        """_plan_run for a device-fed step: the two index pointers are inputs given by address (base of the epoch array + offset)."""
-        plans = self._plan_state()
-        plan = plans.get(key, False)
-        if plan and not self.plan_verify:
-            inp = plan.inputs
-            inp[IN_IDX_T], inp[IN_IDX_E] = pt, pe
-            inp[IN_LR] = _fbits(self._lr_t(lr))
-            self._held = tens
-            plan.enqueue(self.global_step, self._main.cuda_stream, self._side.cuda_stream if self._side is not None else 0)
-            self.b1p = np.float32(self.b1p * np.float32(self.beta1))
-            self.b2p = np.float32(self.b2p * np.float32(self.beta2))
-            self.global_step += 1
-            self.plan_hits += 1
-            return self.loss
-        # record / verify through the generic path: the index arrays as address ranges, the slices' addresses as their inputs
-        tensors = tuple((slot, None if t is None else _Slice(t, p)) for (slot, t), p in zip(tens, (pt, pe)))
-        return self._plan_run(key, tensors, (), lr, python_step)
+            self.row0, self.row0_ex, self._ex_row0_set = placement

@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr
-from .common import _NULL, _check, param_layout, side_stream
+from .common import _NULL, StepState, _check, param_layout, side_stream
 
 
 class _State:
@@ -55,6 +55,8 @@ class _State:
         self.gemm_x3 = gemm == "x3" and hidden_units % 2 == 0 and hidden_units <= 150
         # whole forward stack in one launch (seq_fwd.hip); the per-op kernels remain for the shapes it does not cover
         self.seq_fused = (self.gemm_x3 and num_heads == 1 and maxlen <= 64 and num_blocks <= _lib.SEQ_MAXL)
+        # ---- switches.  One that is read INSIDE a step and shapes a launch argument goes into _mode_key (below): the launch plans and
+        # the cached descriptors of the packed kernels are keyed by it, so that flipping it between two steps never replays a stale one
         # packed session tiles (csrc/seqp_*.hip): the session kernels run on the REAL positions only, several short sessions per
         # 64-row tile.  True / False, or "auto": packed when the batch is sparse enough to pay for it -- decided from the host copy of
         # the batch when the caller passes one (numpy input_seq), else from Engine.pack_density, the fraction of real positions the
@@ -62,9 +64,8 @@ class _State:
         self.pack_sessions = "auto"
         self.pack_density = None
         self.pack_window = (17, 49, 224)   # stream window of the short class: at least / at most / tile count aimed at (seqp_plan.hip)
-        self._pack_now = False
         self.late_side_stream = True       # small-parameter gradients / Adam run beside the (HBM-bound) fused table update
-        self._late, self._late_on, self._late_force = [], False, False
+        self._step = StepState()           # the hand-off fields of the current step (common.StepState; replaced by _begin_step)
         self._st_ptr, self._main, self._in_step = None, None, False
         self._side, self._side_for = None, None
         # native step driver (plan.py): steps of a plannable form are recorded once per (shape, mode) and replayed by one C call
@@ -72,9 +73,8 @@ class _State:
         self.plan_verify = False           # tests: every replayable step runs through Python again and is compared with its plan
         self.plan_hits = self.plan_misses = self.plan_verified = 0
         self.plan_errors = []
-        self._plans, self._plans_gen, self._keep_density, self._held, self._density_now = None, -1, False, None, None
+        self._plans, self._plans_gen = {}, -1
         self._pin = {}
-        self._atb_q = []               # x3 mode: the weight-gradient products of a backward pass, issued as one launch
         self.attn_x3 = gemm == "x3" and (hidden_units // num_heads) % 2 == 0      # bf16x3 attention core (attn_x3.hip)
         self._wnames = ["b%d.%s" % (l, w) for l in range(num_blocks) for w in ("wq", "wk", "wv", "w1", "w2")]
         self._widx = {k: i for i, k in enumerate(self._wnames)}
@@ -90,6 +90,8 @@ class _State:
         self.global_step = 0
         self.row0 = 0            # global index of local row 0 (data-parallel shard offset of the dropout counters)
         self.split_rows, self.row0_ex = None, 0     # ... and of the first local exemplar row (set per step under data parallelism)
+        self._ex_row0_set = False                   # ... row0_ex is meant (dist.DataParallel.set_rows; train_step_fed for its own step)
+        self._tlse_key = None    # the teacher tensor whose row log-sum-exps the workspace buffer "tlse_all" holds (_teacher_lse)
         self._grad_hi = 0
         self._ws = {}
         self._ws_store = {}
@@ -99,11 +101,9 @@ class _State:
         # data-parallel dense path: called right after the logits backward has written the table gradient's dense term (99.8 % of
         # the gradient bytes) so that its all-reduce runs UNDER the blocks backward; returns the pending collectives
         self.grad_early_hook = None
-        self._early, self._dp_rows = None, None
         self.ewc = None          # EWC baseline (EWC.py): dict(F=, prev=, lam=) -> quadratic penalty added between backward and Adam
         self.timer = None        # optional SectionTimer
         self.prune_last = True   # final block: query/FFN path only for position T-1 (exact; see forward())
-        self._lnf_done = None
         # single-GPU bf16-logits steps: apply Adam to the item table inside the table-gradient GEMM (the table gradient
         # is never written to memory); needs the complete gradient locally, so it is off whenever a grad_hook is set
         self.fuse_adam = True
@@ -128,7 +128,6 @@ class _State:
         # "resident" = k_tab_upd (theta tile read once and kept in LDS, no shadow read: 8 % fewer bytes, 10 % slower; NOTEBOOK.md)
         self.bf16_update = "sh"
         self._table_stale = False
-        self._pending_loss, self._img_ready = None, False     # late loss sum / operand images of a deferred fused update
         self._mv_sharded = False   # dp: Adam m/v of the table are current only for the rank's own rows (see _gather_if_sharded)
         # raw device addresses of every parameter / gradient tensor (the flat buffers never move)
         self._pp = {k: self.theta.data_ptr() + 4 * off for k, (off, _) in self.layout.items()}
@@ -225,6 +224,22 @@ class _State:
         self._mv_sharded = False
         self._table_stale = False
         self.refresh_shadow()
+
+    # ---------------------------------------------------------------------------------------- per-step state and cache keys
+    def _begin_step(self):
+        """A fresh StepState for the step that starts here (train_step, train_step_fed, loss_and_grad on its own).  Carried over, on
+        purpose: a loss sum still owed by a deferred step whose fused update never ran, and the inputs of a replayed step."""
+        old, new = self._step, StepState()
+        new.pending_loss, new.held = old.pending_loss, old.held
+        self._step = new
+        return new
+
+    def _mode_key(self):
+        """Every engine switch and placement value that a step's launch arguments depend on: the mode part of a launch plan's key and of
+        the packed forward's descriptor-cache key.  A raw device pointer that enters a launch is workspace (Engine.buf: a reallocation
+        bumps _ws_gen and retires plans and descriptors), a flat parameter buffer (never moves), or an input the plan patches."""
+        return (self.seed, self.row0, self.row0_ex, self._ex_row0_set, self.prune_last, self.late_side_stream, self.cache_descriptors,
+                self.pack_window, self.pack_density, self.beta1, self.beta2, self.eps)
 
     # ---------------------------------------------------------------------------------------- workspaces
     def buf(self, name, shape, dtype=torch.float32, zero=False):

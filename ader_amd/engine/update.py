@@ -14,6 +14,9 @@ class _Update:
 
     def _advance_adam(self):
         self.refresh_weights()
+        self._advance_step()
+
+    def _advance_step(self):      # the host half of an optimiser step (also behind a replayed plan)
         self.b1p = np.float32(self.b1p * np.float32(self.beta1))
         self.b2p = np.float32(self.b2p * np.float32(self.beta2))
         self.global_step += 1
@@ -53,25 +56,23 @@ class _Update:
         return ids, order, sp_start, tids, torder, tg_start, meta
 
     def _lists_async(self, seq, lab, N):
-        main = self._main
+        main, sx = self._main, self._step
         # flat, contiguous int32 copies are made HERE, by torch on the main stream and before the side stream is told to wait for it:
         # a strided view (the catalog-sharded step passes ids_g[:, :n_pos]) would otherwise be materialised inside _sparse_lists --
         # a torch kernel on the main stream that the list kernels on the side stream do not wait for
         seq, lab = seq.reshape(-1).to(torch.int32).contiguous(), lab.reshape(-1).to(torch.int32).contiguous()
         self._edge(self._side_lane(), main)      # inputs ready; also orders reuse of last step's list memory after its reader
         with self._OnStream(self, self._side):
-            self._lists = self._sparse_lists(seq, lab, N)
-            pl_ = self._pending_loss
-            if pl_ is not None:
+            sx.lists = self._sparse_lists(seq, lab, N)
+            if sx.pending_loss is not None:
                 # the loss scalar feeds nothing in this step: its (single-workgroup) sum rides behind the lists on the side lane -- the
                 # row losses are complete (the edge above follows the logit forward) -- instead of heading the side lane's chain beside
                 # the table update, which at the shipped datasets' shapes ends a few microseconds after the update does
-                call("ader_lbf_sum", ptr(pl_[0]), pl_[1], ptr(self.loss), self._stream())
-                self._pending_loss = None
-        self._lists_seq = (seq, lab)         # keep the inputs alive until the side stream has consumed them
+                self._settle_loss()
+        sx.lists_seq = (seq, lab)
 
     def _lists_wait(self):
-        out, self._lists = self._lists, None
+        out, self._step.lists = self._step.lists, None
         self._edge(self._main, self._side)       # (the lists live in persistent workspace buffers: no record_stream needed)
         return out
 
@@ -79,18 +80,16 @@ class _Update:
         """Table rows 1..N: gradient GEMM + sparse terms + Adam in one pass (ader_lbf_bwd_adam); all other parameters:
         the flat Adam kernel on the tail of the buffer.  Rows 0 and > N have zero gradient and zero Adam state (the
         catalog only grows), so leaving them untouched equals the dense update."""
-        D = self._deferred
-        st = self._stream()
+        sx = self._step
+        D, st = sx.deferred, self._stream()
         H, T = self.H, self.T
         lr_t = self._lr_t(lr)
         ids, order, sp_start, tids, torder, tg_start, tmeta = self._lists_wait()
         span = self.layout["pos"][0]
 
         def small_update():     # everything that feeds / is the update of the non-table parameters
-            pl_ = self._pending_loss
-            if pl_ is not None:
-                call("ader_lbf_sum", ptr(pl_[0]), pl_[1], ptr(self.loss), self._stream())
-                self._pending_loss = None
+            if sx.pending_loss is not None:
+                self._settle_loss()
             self._flush_late()
             self._atb_flush()
             with self._sec("adam"):
@@ -100,7 +99,7 @@ class _Update:
             self._advance_adam()
 
         main = self._main
-        overlap = bool(self._late or self._atb_q) and self.late_side_stream
+        overlap = bool(sx.late or sx.atb_q) and self.late_side_stream
         if overlap:
             # weight-gradient products, LayerNorm / positional reductions, small Adam and the bf16 weight planes are compute /
             # latency bound and independent of the table: a side stream runs them under the HBM-bound table update.  The side
@@ -112,9 +111,9 @@ class _Update:
         with self._sec("logits_bwd_adam"):
             if self.lx3:        # operand rows as the LDS images k_tab16x3 streams by LDS-DMA
                 img = self.buf("lbf_rep_img", (call("ader_x3_rep_image_bytes", D["Bp"]),), torch.uint8, zero=True)
-                if not self._img_ready:
+                if not sx.img_ready:
                     call("ader_x3_rep_image", ptr(D["rep_bf"]), ptr(D["rep_lo"]), D["Bp"], ptr(img), st)
-                self._img_ready = False
+                sx.img_ready = False
             if self.lx3 and D.get("kd"):
                 K = D["kd"]
                 call("ader_tab_update_x3_kd", ptr(D["rep_bf"]), ptr(D["rep_lo"]), ptr(img), self.item_num, D["Bp"], K["row0"], H, D["N"],
@@ -149,12 +148,13 @@ class _Update:
             self._edge(main, self._side)
         else:
             small_update()
-        self._deferred = None
+        sx.deferred = None
 
     def train_step(self, seq, pos, max_item, lr, **kw):
         """One `sess.run(train_op)` (main.py:233-256): forward, loss, backward, [gradient exchange], Adam.
         Returns the loss as a 1-element device tensor (no host sync)."""
         self._refresh_stream()
+        self._begin_step()
         self._in_step = True
         try:
             out = self._native_step(seq, pos, max_item, lr, kw)        # one C call per step when a launch plan exists (plan.py)
@@ -174,7 +174,7 @@ class _Update:
         if self.ewc is not None and self.ewc["lam"] != 0.0:
             fuse, sharded = False, False         # the penalty's gradient lives in the dense gradient buffer
         loss = self.loss_and_grad(seq, pos, max_item, _defer_table=fuse, **kw)
-        if self._deferred is not None:
+        if self._step.deferred is not None:
             if sharded:
                 self._fused_table_adam_sharded(lr)
             else:

@@ -124,3 +124,74 @@ def test_device_fed_steps_equal_the_host_assembled_batches():
         assert other[3] == thetas[0][3]
         for a, b in zip(thetas[0][:3], other[:3]):
             assert torch.equal(a, b)
+
+
+def _assert_same_state(ref, nat):
+    assert float(ref.loss) == float(nat.loss)
+    for a, b, name in ((ref.theta, nat.theta, "theta"), (ref.adam_m, nat.adam_m, "m"), (ref.adam_v, nat.adam_v, "v")):
+        assert torch.equal(a, b), name
+    assert (ref.global_step, float(ref.b1p), float(ref.b2p)) == (nat.global_step, float(nat.b1p), float(nat.b2p))
+
+
+def test_replayed_distilled_steps_follow_the_teacher_they_are_given():
+    """Distilled steps of ONE shape that alternate between two teacher tensors of equal shape (A, B, A, B, ...) and go on after
+    A.copy_(B): the teacher's row log-sum-exps are workspace (Engine._teacher_lse), so the address a plan recorded holds the values
+    of the teacher the step was given -- not those of the teacher the plan was recorded with."""
+    B, E = 96, 24
+    engines = []
+    for native in (False, True):
+        e = _engine(ITEM, T, H, L, 1, seed=3, logits_dtype="x3")
+        e.pack_sessions, e.native_step = True, native
+        ta = (torch.randn(40, NP, generator=torch.Generator().manual_seed(5)) * 2).cuda()
+        tb = (torch.randn(40, NP, generator=torch.Generator().manual_seed(6)) * 2 + 1.5).cuda()    # (log-sum-exps far from A's)
+        rs = np.random.RandomState(23)
+        for s in range(16):
+            if s == 10:
+                ta.copy_(tb)
+            seq = torch.from_numpy(_law(rs, B + E, T, N, "geom")).cuda()
+            pos = torch.from_numpy(rs.randint(1, N + 1, size=B).astype(np.int32)).cuda()
+            tr = torch.from_numpy(rs.randint(0, 40, size=E).astype(np.int32)).cuda()
+            e.train_step(seq, pos, N, 1e-3, rate=0.3, teacher=(ta, tb)[s % 2], ex_trow=tr, lambda_=0.7)
+        torch.cuda.synchronize()
+        e.check_status()
+        engines.append(e)
+    ref, nat = engines
+    # two plans (one per teacher address); each loses at most its first two steps (workspace allocation, recording)
+    assert ref.plan_hits == 0 and not nat.plan_errors and nat.plan_hits >= 12, (nat.plan_hits, nat.plan_misses, nat.plan_errors)
+    _assert_same_state(ref, nat)
+
+
+def test_a_device_fed_step_leaves_the_row_placement_as_it_found_it():
+    """train_step_fed places its own rows (row0 / row0_ex of the unpadded batch) and puts the caller's placement back: a plain
+    train_step with exemplar rows that follows it on the same engine is the step of an engine that was handed the same state and
+    never ran a fed step -- its exemplar rows do not inherit the fed step's dropout counters."""
+    from ader_amd.data import pack_rows
+    rs = np.random.RandomState(8)
+    Bt, Be, n_rows, n_ex_rows = 64, 16, 300, 40
+    sessions = [rs.randint(1, N + 1, size=int(k)).tolist() for k in np.clip(rs.geometric(0.25, size=n_rows) + 1, 2, 70)]
+    ex_sessions = [rs.randint(1, NP + 1, size=int(k)).tolist() for k in np.clip(rs.geometric(0.25, size=n_ex_rows) + 1, 2, 70)]
+    rows_t = torch.from_numpy(pack_rows(sessions, T)[0]).cuda()
+    rows_e = torch.from_numpy(pack_rows(ex_sessions, T)[0]).cuda()
+    teacher = (torch.randn(n_ex_rows, NP, generator=torch.Generator().manual_seed(9)) * 2).cuda()
+    perm_t, perm_e = torch.from_numpy(rs.permutation(n_rows)).cuda(), torch.from_numpy(rs.permutation(n_ex_rows)).cuda()
+    seq = torch.from_numpy(_law(rs, Bt + Be, T, N, "geom")).cuda()
+    pos = torch.from_numpy(rs.randint(1, N + 1, size=Bt).astype(np.int32)).cuda()
+    tr = torch.from_numpy(rs.randint(0, n_ex_rows, size=Be).astype(np.int32)).cuda()
+
+    def plain_steps(e):             # (three of one shape: the native engine replays the last)
+        for _ in range(3):
+            e.train_step(seq, pos, N, 1e-3, rate=0.3, teacher=teacher, ex_trow=tr, lambda_=0.6)
+        torch.cuda.synchronize()
+        e.check_status()
+
+    nat = _engine(ITEM, T, H, L, 1, seed=3, logits_dtype="x3")
+    ref = _engine(ITEM, T, H, L, 1, seed=3, logits_dtype="x3")
+    for e, native in ((nat, True), (ref, False)):
+        e.pack_sessions, e.pack_density, e.native_step = "auto", 0.1, native
+    nat.train_step_fed((rows_t, perm_t, 0, Bt - 2, Bt, rows_e, perm_e, 0, Be - 1, Be), N, 1e-3, 0.3, teacher=teacher, lambda_=0.6)
+    assert (nat.row0, nat.row0_ex, nat._ex_row0_set) == (0, 0, False)
+    ref.load_state_dict(nat.state_dict())
+    plain_steps(nat)
+    plain_steps(ref)
+    assert nat.plan_hits >= 1 and not nat.plan_errors, (nat.plan_hits, nat.plan_misses, nat.plan_errors)
+    _assert_same_state(ref, nat)

@@ -282,7 +282,7 @@ def test_auto_packing_follows_the_batch_density():
     rs = np.random.RandomState(0)
     sparse, dense = _law(rs, 64, 50, 300, "geom"), rs.randint(1, 301, size=(64, 50)).astype(np.int32)
     e.encode(sparse)
-    assert e._density_now < 0.2
+    assert e._step.density < 0.2
     e.forward(e._seq_in(sparse), save=True)
     assert e._act.get("pack") is not None
     e.forward(e._seq_in(dense), save=True)
