@@ -58,13 +58,13 @@ struct FuseArgs {
     const float* extra1;        // EXTRA: dense gradient rows to add (row of item 1; [.,H] fp32), e.g. distilled rows' term
 };
 
-// arguments of the 64-row table-update kernels (table_update.hip: k_tab_upd, table_update_x3.hip: k_tab16x3)
+// arguments of the fp32-table update kernels (table_update.hip: k_tab_upd, table_update_x3.hip: k_tab32x3); tiles are 64 rows
 struct TabArgs {
     const float* emb1;      // fp32 table, row of item 1: GEMM operand source (and the parameters, FuseArgs.emb1 == this)
     int vrows;              // table rows that exist from emb1 on (item_num)
     const bf16* rep_hi;     // [Bp][LDR] bf16(rep), zero padded
     const bf16* rep_lo;     // [Bp][LDR] bf16(rep - hi)   (X3)
-    const void* rep_img;    // k_tab16x3: LDS images of the rep chunks (ader_x3_rep_image); NULL elsewhere
+    const void* rep_img;    // k_tab32x3: LDS images of the rep chunks (ader_x3_rep_image); NULL elsewhere
     const float* off;       // [Bp] log2(w_b) - lse2_b; -inf for rows without a loss term
     int Bp, H, N, tile_off;
     int tile_end;           // k_tab32x3: first 64-row tile beyond the launch (its workgroups own PAIRS of tiles)

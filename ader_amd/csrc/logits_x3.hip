@@ -7,8 +7,10 @@
 // nothing [rows, N]-sized is ever written.  The table block is split into hi/lo on its way into LDS as the bank-conflict-free image
 // of x3_image.h (16-byte k-chunks [kc][item][8 channels]), and both operand reads -- ds_read_b128 rows for S^T, ds_read_b64_tr_b16
 // k-major for the readout -- are pipelined by hand ahead of their MFMAs.
-//   k_lx3g  32 batch rows per wave on v_mfma_f32_32x32x16_bf16 (128 per workgroup, two workgroups per CU); any supported H
-//   k_lx3p  k_lx3g with the softmax / staging vector work issued inside the MFMA phases (H = 150: the default forward)
+//   k_lx3g  32 batch rows per wave on v_mfma_f32_32x32x16_bf16 (128 per workgroup, two workgroups per CU); any supported H, the
+//           table block staged by k-chunks.  Launched for H != 150
+//   k_lx3p  the same with the softmax / staging vector work issued inside the MFMA phases, the table block staged in memory
+//           order (H = 150 only: the default forward)
 //   k_lx3r  the teacher readout of distilled steps (ADER.py:132-137) on the same images
 // (k_lx3f, 16 rows per wave on 16x16x32 tiles, and k_lx3h, k_lx3g's blocking on 16x16x32 tiles, were measured 25 % and 4 % slower in
 // round 3 -- NOTEBOOK.md -- and removed in round 4.)
@@ -18,20 +20,43 @@
 #include "../../include/ader_hip.h"
 
 #define F3_FB 32                   // items per streamed block
-#define F3_RND 3                   // staging rounds: 12 units of (8 items x 8 k-chunks), 4 waves
+#define F3_RND 3                   // staging rounds of k_lx3g: 12 units of (8 items x 8 k-chunks), 4 waves
+#define G3_ROWS 128                // batch rows per workgroup
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-struct __attribute__((packed, aligned(8))) F3Vec { f32x4_t v; };      // 16-byte vector at an 8-byte aligned address (rows are 8 H bytes)
+
+// ---- what the three kernels share: the operand reads of a block image (x3_image.h, 32x32x16 maps) and the rotation of its three
+// LDS buffers.  (The reads are macros, expanded in the kernel, and not functions: as functions they compile to other streams.)
+// Per-lane byte offsets into a block image, with lane, r32 = lane & 31 and hh = lane >> 5 in scope: t_off = transposed read of (item
+// 4 hh + q4, channels 16 g1 + 4 p4.. of a 32-channel block = k-chunks 2 g1 + (p4 >> 1) of its four); a_off = row read of (item r32,
+// k-half hh)
+#define G3_T_OFF()                                                                                        \
+    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;                                 \
+    const int t_off = X3B_KC * (2 * g1 + (p4 >> 1)) + 16 * (4 * hh + q4) + 8 * (p4 & 1);
+#define G3_A_OFF() const int a_off = X3B_KC * hh + 16 * r32;
+// S^T = 32 items x 32 batch rows: A = table rows (lane: item r32, k = 8 hh..8 hh + 7 of the k-step), B = rep fragments.
+// set_ = {hi, lo} of k-step ks_ of the image at img_
+#define G3_LOADA(set_, img_, ks_)                                                                         \
+    { const char* ap_ = (img_) + a_off + 2 * X3B_KC * (ks_);                                              \
+      set_[0] = *(const bf16x8*)ap_; set_[1] = *(const bf16x8*)(ap_ + X3B_PLANE_B); }
+// transposed reads of the 32-channel block nb_ of plane pl_ (0 hi, 1 lo) of the image at Bh: {items 4hh.., 8 + 4hh.., 16 + 4hh..,
+// 24 + 4hh..}
+#define G3_LOADT(set_, nb_, pl_)                                                                          \
+    { const bf16* tp_ = (const bf16*)(Bh + t_off + 4 * X3B_KC * (nb_) + (pl_) * X3B_PLANE_B);              \
+      set_[0] = tr_read(tp_); set_[1] = tr_read(tp_ + 64); set_[2] = tr_read(tp_ + 128); set_[3] = tr_read(tp_ + 192); }
+// three LDS buffers: block i is read from buffer i % 3 while block i + 1 (stored during iteration i - 1) waits in the next one and
+// block i + 2 -- requested at the head of iteration i, converted and stored between its two MFMA phases -- goes into the third:
+// the staging registers are live only under the S^T phase, where the operand sets are small
+__device__ __forceinline__ int g3_buf_next(int b) { return b == 2 ? 0 : b + 1; }       // (i + 1) % 3 from i % 3
+__device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; }        // (i + 2) % 3
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // k_lx3g: 32 batch rows per wave on v_mfma_f32_32x32x16_bf16 (128 per workgroup, two workgroups per CU): every LDS operand fragment
 // feeds twice the flops of a 16x16x32 form with 16-row waves, which keeps the LDS pipe as busy as the matrix pipe.
 // Register plan (<= 256): rep fragments 80, O 80, S / P 16, one block in flight 24, operand sets 16 / 32.
-#define G3_ROWS 128
-template <int HT>
 __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [2 buffers][block image]
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [3 buffers][block image]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
@@ -40,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
     const int range = xcd + 8 * (slot / nchunk);           // the row chunks of an item range sit on one XCD: the table block is
     const int bc = slot % nchunk;                          // fetched from HBM once and served to the others by that XCD's L2
     if (range >= a.ranges) return;
-    const int H = HT ? HT : a.H;
+    const int H = a.H;
     const int N = (bc * G3_ROWS >= a.kd_row0) ? a.Np : a.N;            // columns of this chunk's softmax (distilled rows: first Np)
     const int nblk_all = (a.N + F3_FB - 1) / F3_FB;
     const int per = (nblk_all + a.ranges - 1) / a.ranges;
@@ -72,38 +97,6 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
     const int voffp = voff + 4 * (rem - 4);                // second vector of the partial k-chunk: ends with the row
     const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
     const int dst0 = X3B_KC * kc0 + 16 * it_;               // byte offset inside a plane (round r: + 8 k-chunks)
-    // ---- H = 150: the block as 16-byte pieces read in memory order.  Lane l -> item 8 wave + (l >> 3), piece (l & 7) + 8 r of the
-    // row's 37.5 (round r = 0..4): a wave-instruction reads 8 x 128 contiguous bytes -- ~12 cache lines, every byte used -- where the
-    // k-chunk mapping above reads 8 x 8 half-used 32-byte pieces (~20 lines, each touched by two instructions); 5 loads instead of
-    // 6.  A piece = 4 channels = half a k-chunk slot: one ds_write_b64 per plane (two-way bank conflicts, hidden under the
-    // VGPR-to-LDS transfer of the store).
-    constexpr bool MAPB = (HT == 150);
-    const int itb = 8 * wave + (lane >> 3), qb = lane & 7;
-    const int voffb = itb * (4 * 150) + 16 * qb;           // round r: + 128 r
-    const int dstb = X3B_KC * (qb >> 1) + 16 * itb + 8 * (qb & 1);      // round r: + 4 k-chunks
-    f32x4_t sc[5];
-#define G3B_LOAD(blk_)                                                                                    \
-    {                                                                                                     \
-        const int so_ = (blk_) * (F3_FB * 4) * 150;                                                       \
-        _Pragma("unroll") for (int r = 0; r < 5; ++r)                                                     \
-            sc[r] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(trs, voffb + 128 * r, so_, 0)); \
-    }
-#define G3B_STORE(buf_)                                                                                   \
-    {                                                                                                     \
-        unsigned char* dst_ = smem_raw + (buf_) * X3B_IMG_B;                                              \
-        _Pragma("unroll") for (int r = 0; r < 5; ++r) {                                                   \
-            const int p_ = qb + 8 * r;                          /* piece 37 = channels 148, 149 and two floats of the next row */ \
-            float x_[4];                                        /* pieces 38, 39 = channels 152..159: zeros (no branch) */ \
-            x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[r][0]; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[r][1];                  \
-            x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[r][2]; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[r][3];                  \
-            bf16x4 h_, l_;                                                                                \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) { h_[j] = (bf16)x_[j]; l_[j] = (bf16)(x_[j] - (float)h_[j]); } \
-            *(bf16x4*)(dst_ + dstb + 4 * X3B_KC * r) = h_;                                                \
-            *(bf16x4*)(dst_ + X3B_PLANE_B + dstb + 4 * X3B_KC * r) = l_;                                  \
-        }                                                                                                 \
-    }
-#define G3_LOADBLK(blk_) { if constexpr (MAPB) G3B_LOAD(blk_) else F3_LOAD(blk_) }
-#define G3_STOREBLK(buf_) { if constexpr (MAPB) G3B_STORE(buf_) else F3_STORE(buf_) }
 #define F3_KC(r_) (8 * (r_) + kc0)
 #define F3_PART(r_) (rem && F3_KC(r_) == nfull)
 #define F3_VALID(r_) (F3_KC(r_) < nfull || F3_PART(r_))
@@ -140,40 +133,25 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
             }                                                                                             \
         }                                                                                                 \
     }
-    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
-    // per-lane byte offsets into a block image: row read of (item r32, k-half hh); transposed read of (item 4 hh + q4, channels
-    // 16 g1 + 4 p4.. of a 32-channel block = k-chunks 2 g1 + (p4 >> 1) of its four)
-    const int a_off = X3B_KC * hh + 16 * r32;
-    const int t_off = X3B_KC * (2 * g1 + (p4 >> 1)) + 16 * (4 * hh + q4) + 8 * (p4 & 1);
-    // three LDS buffers: block i is read from buffer i % 3 while block i + 1 (stored during iteration i - 1) waits in the next one and
-    // block i + 2 -- requested at the head of iteration i, converted and stored between its two MFMA phases -- goes into the third:
-    // the 24 staging registers are live only under the S^T phase, where the operand sets are small
-    if (nb_blocks > 0) G3_LOADBLK(blk_begin);
+    G3_T_OFF()
+    G3_A_OFF()
+    if (nb_blocks > 0) F3_LOAD(blk_begin);
     __syncthreads();                                       // zero fill done
-    if (nb_blocks > 0) G3_STOREBLK(0);
-    if (nb_blocks > 1) { G3_LOADBLK(blk_begin + 1); G3_STOREBLK(1); }
+    if (nb_blocks > 0) F3_STORE(0);
+    if (nb_blocks > 1) { F3_LOAD(blk_begin + 1); F3_STORE(1); }
     int bcur = 0;                                          // i % 3
     for (int i = 0; i < nb_blocks; ++i) {
         __syncthreads();                                   // blocks i and i + 1 are in LDS; every wave is done with block i - 1
         const bool more = i + 2 < nb_blocks;
-        if (more) G3_LOADBLK(blk_begin + i + 2);
+        if (more) F3_LOAD(blk_begin + i + 2);
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
-        const int bnew = bcur == 0 ? 2 : bcur - 1;         // (i + 2) % 3
         const int i0 = (blk_begin + i) * F3_FB;
-        // S^T = 32 items x 32 batch rows: A = table rows (lane: item r32, k = 8 hh..8 hh + 7 of the k-step), B = rep fragments
-#define G3_LOADA(set_, ks_)                                                                               \
-        { const char* ap_ = Bh + a_off + 2 * X3B_KC * (ks_);                                              \
-          set_[0] = *(const bf16x8*)ap_; set_[1] = *(const bf16x8*)(ap_ + X3B_PLANE_B); }
-        // transposed reads of the 32-channel block nb: {hi: items 4hh.., 8 + 4hh.., 16 + 4hh.., 24 + 4hh..; lo: the same}
-#define G3_LOADT(set_, nb_, pl_)                                                                          \
-        { const bf16* tp_ = (const bf16*)(Bh + t_off + 4 * X3B_KC * (nb_) + (pl_) * X3B_PLANE_B);            \
-          set_[0] = tr_read(tp_); set_[1] = tr_read(tp_ + 64); set_[2] = tr_read(tp_ + 128); set_[3] = tr_read(tp_ + 192); }
         f32x16 S;
 #pragma unroll
         for (int j = 0; j < 16; ++j) S[j] = 0.0f;
         bf16x8 fa[2][2];
-        G3_LOADA(fa[0], 0);
-        G3_LOADA(fa[1], 1);
+        G3_LOADA(fa[0], Bh, 0);
+        G3_LOADA(fa[1], Bh, 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < 10; ++ks) {
@@ -181,10 +159,10 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
             S = mfma_bf16(A_[1], rh[ks], S);
             S = mfma_bf16(A_[0], rl[ks], S);
             S = mfma_bf16(A_[0], rh[ks], S);
-            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], ks + 2);
+            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bh, ks + 2);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (more) G3_STOREBLK(bnew);
+        if (more) F3_STORE(g3_buf_new(bcur));
         __builtin_amdgcn_sched_barrier(0);
         // the first transposed reads of the readout do not depend on S: in flight under the softmax section
         bf16x4 ft[3][4];        // half sets: {items 4hh.., 8 + 4hh.., 16 + 4hh.., 24 + 4hh..} of ONE plane; hi, lo, hi, lo ...
@@ -243,10 +221,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
             if (hs + 3 < 10) G3_LOADT(ft[hs % 3], (hs + 3) >> 1, (hs + 3) & 1);
             __builtin_amdgcn_sched_barrier(0);
         }
-        bcur = bcur == 2 ? 0 : bcur + 1;
+        bcur = g3_buf_next(bcur);
     }
-#undef G3_LOADA
-#undef G3_LOADT
+#undef F3_STORE
+#undef F3_LOAD
+#undef F3_VALID
+#undef F3_PART
+#undef F3_KC
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     if (hh == 0) {
         a.pm[(size_t)range * a.Bp + b0 + r32] = m_run;
@@ -265,9 +246,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
 // the kernel is bound by the waves' serial chains, not by the matrix pipe (68 % busy).  Here the logits of the NEXT block are
 // accumulated (a second S, 16 registers) while the exp / sum / hi-lo split of the current block's logits are placed between its
 // MFMAs; the rescale test (a branch) stays in front.  Same arithmetic in the same order as k_lx3g: bit-equal results.
+// (H = 150 only.  It stays a template although HT has one value: the benchmark picks this kernel's counters by the name prefix
+//  "k_lx3p<".)
 template <int HT>
 __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [2 buffers][block image]
+    static_assert(HT == 150, "k_lx3p: piece staging (H = 150) only");
+    constexpr int H = HT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [3 buffers][block image]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
@@ -276,7 +261,6 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
     const int range = xcd + 8 * (slot / nchunk);           // the row chunks of an item range sit on one XCD: the table block is
     const int bc = slot % nchunk;                          // fetched from HBM once and served to the others by that XCD's L2
     if (range >= a.ranges) return;
-    const int H = HT ? HT : a.H;
     const int N = (bc * G3_ROWS >= a.kd_row0) ? a.Np : a.N;            // columns of this chunk's softmax (distilled rows: first Np)
     const int nblk_all = (a.N + F3_FB - 1) / F3_FB;
     const int per = (nblk_all + a.ranges - 1) / a.ranges;
@@ -298,33 +282,25 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
     float m_run = -INFINITY, l_run = 0.0f;
-    // ---- staging: a block = 32 table rows of H floats.  Round r (0..2) of wave w covers items 8 w.. and k-chunks 8 r..:
-    // lane l -> item + (l & 7), k-chunk + (l >> 3): the 8 lanes of an LDS write group store 8 consecutive 16-byte
-    // slots (conflict-free), and a wave's two 16-byte loads per slot touch 2 cache lines per table row.
-    const int nfull = H >> 3, rem = H & 7;                 // full k-chunks; channels of the partial one (0, 4 or 6: see launcher)
-    // round r of this lane: item it_ (= 8 wave + (lane & 7): a wave stages the same 8 items in every round), k-chunk 8 r + kc0
-    const int it_ = 8 * wave + (lane & 7), kc0 = lane >> 3;
-    const int voff = 4 * (it_ * H + 8 * kc0);              // byte offset inside the block (round r: + 256 r)
-    const int voffp = voff + 4 * (rem - 4);                // second vector of the partial k-chunk: ends with the row
+    // ---- staging: a block = 32 table rows of 150 floats, as 16-byte pieces read in memory order.  Lane l -> item 8 wave + (l >> 3),
+    // piece (l & 7) + 8 r of the row's 37.5 (round r = 0..4): a wave-instruction reads 8 x 128 contiguous bytes -- ~12 cache lines,
+    // every byte used -- where k_lx3g's k-chunk mapping reads 8 x 8 half-used 32-byte pieces (~20 lines, each touched by two
+    // instructions); 5 loads instead of 6.  A piece = 4 channels = half a k-chunk slot: one ds_write_b64 per plane (two-way bank
+    // conflicts, hidden under the VGPR-to-LDS transfer of the store).  The loads go through a buffer descriptor of the table as in
+    // k_lx3g; rows beyond the table's last one come back as zeros from the hardware range check.
+    const int qb = lane & 7, ib = lane >> 3;
     const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
-    const int dst0 = X3B_KC * kc0 + 16 * it_;               // byte offset inside a plane (round r: + 8 k-chunks)
-    // ---- H = 150: the block as 16-byte pieces read in memory order.  Lane l -> item 8 wave + (l >> 3), piece (l & 7) + 8 r of the
-    // row's 37.5 (round r = 0..4): a wave-instruction reads 8 x 128 contiguous bytes -- ~12 cache lines, every byte used -- where the
-    // k-chunk mapping above reads 8 x 8 half-used 32-byte pieces (~20 lines, each touched by two instructions); 5 loads instead of
-    // 6.  A piece = 4 channels = half a k-chunk slot: one ds_write_b64 per plane (two-way bank conflicts, hidden under the
-    // VGPR-to-LDS transfer of the store).
-    constexpr bool MAPB = (HT == 150);
-    const int itb = 8 * wave + (lane >> 3), qb = lane & 7;
-    const int voffb = itb * (4 * 150) + 16 * qb;           // round r: + 128 r
+    const int itb = 8 * wave + ib;
+    const int voffb = itb * (4 * H) + 16 * qb;               // round r: + 128 r
     const int dstb = X3B_KC * (qb >> 1) + 16 * itb + 8 * (qb & 1);      // round r: + 4 k-chunks
     f32x4_t sc[5];
-#define G3B_LOAD(blk_)                                                                                    \
+#define P3_LOADBLK(blk_)                                                                                  \
     {                                                                                                     \
-        const int so_ = (blk_) * (F3_FB * 4) * 150;                                                       \
+        const int so_ = (blk_) * (F3_FB * 4) * H;              /* byte offset of the block (< 2^31: checked by the launcher) */ \
         _Pragma("unroll") for (int r = 0; r < 5; ++r)                                                     \
             sc[r] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(trs, voffb + 128 * r, so_, 0)); \
     }
-#define G3B_STORE(buf_)                                                                                   \
+#define P3_STOREBLK(buf_)                                                                                 \
     {                                                                                                     \
         unsigned char* dst_ = smem_raw + (buf_) * X3B_IMG_B;                                              \
         _Pragma("unroll") for (int r = 0; r < 5; ++r) {                                                   \
@@ -338,64 +314,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
             *(bf16x4*)(dst_ + X3B_PLANE_B + dstb + 4 * X3B_KC * r) = l_;                                  \
         }                                                                                                 \
     }
-#define G3_LOADBLK(blk_) { if constexpr (MAPB) G3B_LOAD(blk_) else F3_LOAD(blk_) }
-#define G3_STOREBLK(buf_) { if constexpr (MAPB) G3B_STORE(buf_) else F3_STORE(buf_) }
-#define F3_KC(r_) (8 * (r_) + kc0)
-#define F3_PART(r_) (rem && F3_KC(r_) == nfull)
-#define F3_VALID(r_) (F3_KC(r_) < nfull || F3_PART(r_))
-    f32x4_t sa[F3_RND], sb[F3_RND];
-    // Block loads through a buffer descriptor of the table (base in scalar registers, ONE 32-bit per-lane offset, the block's
-    // offset as the scalar offset, the round's as the instruction's immediate): no 64-bit per-lane pointers, and rows beyond the
-    // table's last one (only in its last block; their items are >= N: outside the softmax) come back as zeros from the hardware
-    // range check.  Lanes without a k-chunk read whatever follows their row (never stored).  NOTHING is selected on the loaded data
-    // here -- a select would make hipcc wait for each load right behind its issue.
-#define F3_LOAD(blk_)                                                                                     \
-    {                                                                                                     \
-        const int so_ = (blk_) * (F3_FB * 4) * H;              /* byte offset of the block (< 2^31: checked by the launcher) */ \
-        _Pragma("unroll") for (int r = 0; r < F3_RND; ++r) {                                              \
-            const u32x4_t va_ = __builtin_amdgcn_raw_buffer_load_b128(trs, voff + 256 * r, so_, 0);         \
-            const u32x4_t vb_ = __builtin_amdgcn_raw_buffer_load_b128(trs, (F3_PART(r) ? voffp : voff + 16) + 256 * r, so_, 0); \
-            sa[r] = __builtin_bit_cast(f32x4_t, va_); sb[r] = __builtin_bit_cast(f32x4_t, vb_);           \
-        }                                                                                                 \
-    }
-    // hi = bf16(x), lo = bf16(x - hi), 8 channels -> one 16-byte slot per plane
-#define F3_STORE(buf_)                                                                                    \
-    {                                                                                                     \
-        unsigned char* dst_ = smem_raw + (buf_) * X3B_IMG_B;                                               \
-        _Pragma("unroll") for (int r = 0; r < F3_RND; ++r) {                                              \
-            float x_[8];                                                                                  \
-            x_[0] = sa[r][0]; x_[1] = sa[r][1]; x_[2] = sa[r][2]; x_[3] = sa[r][3];                       \
-            if (F3_PART(r)) {       /* rem = 6: channels 4,5 are elements 2,3 of the shifted vector; rem = 4: none */ \
-                x_[4] = (rem == 6) ? sb[r][2] : 0.f; x_[5] = (rem == 6) ? sb[r][3] : 0.f; x_[6] = 0.f; x_[7] = 0.f; \
-            } else { x_[4] = sb[r][0]; x_[5] = sb[r][1]; x_[6] = sb[r][2]; x_[7] = sb[r][3]; }            \
-            bf16x8 h_, l_;                                                                                \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) { h_[j] = (bf16)x_[j]; l_[j] = (bf16)(x_[j] - (float)h_[j]); } \
-            if (F3_VALID(r)) {                                                                            \
-                *(bf16x8*)(dst_ + dst0 + 8 * X3B_KC * r) = h_;                                            \
-                *(bf16x8*)(dst_ + X3B_PLANE_B + dst0 + 8 * X3B_KC * r) = l_;                              \
-            }                                                                                             \
-        }                                                                                                 \
-    }
-    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
-    // per-lane byte offsets into a block image: row read of (item r32, k-half hh); transposed read of (item 4 hh + q4, channels
-    // 16 g1 + 4 p4.. of a 32-channel block = k-chunks 2 g1 + (p4 >> 1) of its four)
-    const int a_off = X3B_KC * hh + 16 * r32;
-    const int t_off = X3B_KC * (2 * g1 + (p4 >> 1)) + 16 * (4 * hh + q4) + 8 * (p4 & 1);
-    // three LDS buffers: block i is read from buffer i % 3 while block i + 1 (stored during iteration i - 1) waits in the next one and
-    // block i + 2 -- requested at the head of iteration i, converted and stored between its two MFMA phases -- goes into the third:
-    // the 24 staging registers are live only under the S^T phase, where the operand sets are small
-    if (nb_blocks > 0) G3_LOADBLK(blk_begin);
+    G3_T_OFF()
+    G3_A_OFF()
+    if (nb_blocks > 0) P3_LOADBLK(blk_begin);
     __syncthreads();                                       // zero fill done
-    if (nb_blocks > 0) G3_STOREBLK(0);
-    if (nb_blocks > 1) { G3_LOADBLK(blk_begin + 1); G3_STOREBLK(1); }
+    if (nb_blocks > 0) P3_STOREBLK(0);
+    if (nb_blocks > 1) { P3_LOADBLK(blk_begin + 1); P3_STOREBLK(1); }
     int bcur = 0;                                          // i % 3
-    // S^T = 32 items x 32 batch rows: A = table rows (lane: item r32, k = 8 hh..8 hh + 7 of the k-step), B = rep fragments
-#define G3_LOADA(set_, ks_)                                                                               \
-    { const char* ap_ = Bs + a_off + 2 * X3B_KC * (ks_);                                                  \
-      set_[0] = *(const bf16x8*)ap_; set_[1] = *(const bf16x8*)(ap_ + X3B_PLANE_B); }
-#define G3_LOADT(set_, nb_, pl_)                                                                          \
-    { const bf16* tp_ = (const bf16*)(Bh + t_off + 4 * X3B_KC * (nb_) + (pl_) * X3B_PLANE_B);              \
-      set_[0] = tr_read(tp_); set_[1] = tr_read(tp_ + 64); set_[2] = tr_read(tp_ + 128); set_[3] = tr_read(tp_ + 192); }
     // softmax of ONE pair of logits of the current block (elements 2 q_, 2 q_ + 1 of S): p = exp2(s log2e - m), running sum in
     // element order (the order of k_lx3g: bit-equal results), hi / lo split into packed pairs
 #define P3_PAIR(q_)                                                                                       \
@@ -413,8 +338,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) S[j] = 0.0f;
         bf16x8 fa[2][2];
-        G3_LOADA(fa[0], 0);
-        G3_LOADA(fa[1], 1);
+        G3_LOADA(fa[0], Bs, 0);
+        G3_LOADA(fa[1], Bs, 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < 10; ++ks) {
@@ -422,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
             S = mfma_bf16(A_[1], rh[ks], S);
             S = mfma_bf16(A_[0], rl[ks], S);
             S = mfma_bf16(A_[0], rh[ks], S);
-            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], ks + 2);
+            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bs, ks + 2);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -449,10 +374,9 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
         const float nm = -m_run;                                                                          \
         float ls = 0.0f;                                                                                  \
         uint32_t ph2[8], pl2[8];                           /* P hi / lo as packed bf16 pairs */
-    // ... and behind it: the block in flight goes to LDS, then the readout O += P^T . E of the current block
+    // ... and behind it: the readout O += P^T . E of the current block
 #define P3_TAIL()                                                                                         \
         l_run += ls;                                                                                      \
-        if constexpr (more) G3_STOREBLK(bnew);                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                \
         bf16x4 ft[3][4];                                                                                  \
         G3_LOADT(ft[0], 0, 0);                                                                            \
@@ -485,10 +409,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
     int i = 0;
     for (; i + 2 < nb_blocks; ++i) {                       // (every iteration stages a block: NO branch between the S phase and the readout --
         __syncthreads();                                   //  across one the compiler sinks the whole softmax to its first use)
-        constexpr bool more = true;
-        G3_LOADBLK(blk_begin + i + 2);
-        const int bnext = bcur == 2 ? 0 : bcur + 1;        // (i + 1) % 3
-        const int bnew = bcur == 0 ? 2 : bcur - 1;         // (i + 2) % 3
+        P3_LOADBLK(blk_begin + i + 2);
+        const int bnext = g3_buf_next(bcur), bnew = g3_buf_new(bcur);
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
         const char* Bs = (const char*)(smem_raw + bnext * X3B_IMG_B);
         P3_HEAD()
@@ -501,8 +423,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) Sn[j] = 0.0f;
         bf16x8 fa[2][2];
-        G3_LOADA(fa[0], 0);
-        G3_LOADA(fa[1], 1);
+        G3_LOADA(fa[0], Bs, 0);
+        G3_LOADA(fa[1], Bs, 1);
         __builtin_amdgcn_sched_barrier(0);
         // (order pinned piece by piece: the machine scheduler's own interleaving -- sched_group_barrier -- is reverted at 254
         //  registers, and vector instructions left to instruction selection all land behind the MFMAs)
@@ -533,13 +455,12 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
                 bf16x2 l_; l_[0] = (bf16)S[2 * q]; l_[1] = (bf16)S[2 * q + 1];
                 pl2[q] = __builtin_bit_cast(uint32_t, l_);
             }
-            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], ks + 2);
+            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bs, ks + 2);
             __builtin_amdgcn_sched_barrier(0);
         }
         l_run += ls;
         // ---- the readout O += P^T . E of block i, with the conversion of block i + 2 (fp32 -> hi / lo image: ~17 vector instructions
         // and two 8-byte LDS stores per 16-byte piece) in the shadows of its MFMAs: round r of the staging goes with half steps 2 r, 2 r + 1
-        static_assert(HT == 150, "k_lx3p: piece staging (H = 150) only");
         bf16x4 ft[3][4];
         G3_LOADT(ft[0], 0, 0);
         G3_LOADT(ft[1], 0, 1);
@@ -608,9 +529,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
     }
     for (; i < nb_blocks; ++i) {                           // ---- the last two blocks: plain order (nothing left to stage)
         __syncthreads();
-        constexpr bool more = false;
-        const int bnew = 0;
-        const int bnext = bcur == 2 ? 0 : bcur + 1;
+        const int bnext = g3_buf_next(bcur);
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
         const char* Bs = (const char*)(smem_raw + bnext * X3B_IMG_B);
         P3_HEAD()
@@ -621,8 +540,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
         for (int j = 0; j < 16; ++j) Sn[j] = 0.0f;
         if (i + 1 < nb_blocks) {
             bf16x8 fa[2][2];
-            G3_LOADA(fa[0], 0);
-            G3_LOADA(fa[1], 1);
+            G3_LOADA(fa[0], Bs, 0);
+            G3_LOADA(fa[1], Bs, 1);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int ks = 0; ks < 10; ++ks) {
@@ -630,7 +549,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
                 Sn = mfma_bf16(A_[1], rh[ks], Sn);
                 Sn = mfma_bf16(A_[0], rl[ks], Sn);
                 Sn = mfma_bf16(A_[0], rh[ks], Sn);
-                if (ks + 2 < 10) G3_LOADA(fa[ks & 1], ks + 2);
+                if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bs, ks + 2);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -641,8 +560,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
 #undef P3_HEAD
 #undef P3_TAIL
 #undef P3_PAIR
-#undef G3_LOADA
-#undef G3_LOADT
+#undef P3_STOREBLK
+#undef P3_LOADBLK
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     if (hh == 0) {
         a.pm[(size_t)range * a.Bp + b0 + r32] = m_run;
@@ -740,11 +659,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
             _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                 \
                 tt[set_][4 * q + k] = trp[min(i0_ + 8 * q + k, Np - 1 - 4 * hh)];                         \
     }
-    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
-    const int t_off = X3B_KC * (2 * g1 + (p4 >> 1)) + 16 * (4 * hh + q4) + 8 * (p4 & 1);
-#define R3_LOADT(set_, nb_, pl_)                                                                          \
-        { const bf16* tp_ = (const bf16*)(Bh + t_off + 4 * X3B_KC * (nb_) + (pl_) * X3B_PLANE_B);            \
-          set_[0] = tr_read(tp_); set_[1] = tr_read(tp_ + 64); set_[2] = tr_read(tp_ + 128); set_[3] = tr_read(tp_ + 192); }
+    G3_T_OFF()
     const int nb_full = max(0, min(blk_end, nfull_all) - blk_begin);       // full blocks of this range (the rest: the partial one)
     // prologue: blocks 0, 1 -> LDS buffers 0, 1; blocks 2, 3 -> staging sets 0, 1; teacher blocks 0, 1 -> sets 0, 1
     R3_LOAD(0, blk_begin);
@@ -762,14 +677,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
 #define R3_ITER(e_)                                                                                       \
     {                                                                                                     \
         lds_only_barrier();                                /* blocks i, i + 1 in LDS; every wave is done with block i - 1 */ \
-        const int bnew = bcur == 0 ? 2 : bcur - 1;         /* (i + 2) % 3 */                              \
-        R3_STORE(e_, bnew);                                                                               \
+        R3_STORE(e_, g3_buf_new(bcur));                                                                            \
         R3_LOAD(e_, blk_begin + i + 4);                                                                   \
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);                                      \
         bf16x4 ft[3][4];                                                                                  \
-        R3_LOADT(ft[0], 0, 0);                                                                            \
-        R3_LOADT(ft[1], 0, 1);                                                                            \
-        R3_LOADT(ft[2], 1, 0);                                                                            \
+        G3_LOADT(ft[0], 0, 0);                                                                            \
+        G3_LOADT(ft[1], 0, 1);                                                                            \
+        G3_LOADT(ft[2], 1, 0);                                                                            \
         f32x16 S;                                                                                         \
         const int lim_ = (tr >= 0) ? Np - (blk_begin + i) * F3_FB - 4 * hh : 0;     /* items of this lane's positions inside [0, Np) */ \
         _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                                  \
@@ -794,10 +708,10 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
                 O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);                                              \
                 O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);                                              \
             }                                                                                             \
-            if (hs + 3 < 10) R3_LOADT(ft[hs % 3], (hs + 3) >> 1, (hs + 3) & 1);                           \
+            if (hs + 3 < 10) G3_LOADT(ft[hs % 3], (hs + 3) >> 1, (hs + 3) & 1);                           \
             __builtin_amdgcn_sched_barrier(0);                                                            \
         }                                                                                                 \
-        bcur = bcur == 2 ? 0 : bcur + 1;                                                                  \
+        bcur = g3_buf_next(bcur);                                                                         \
         ++i;                                                                                              \
     }
     int i = 0;
@@ -811,7 +725,6 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
     }
 #undef R3_TSLOW
 #undef R3_ITER
-#undef R3_LOADT
 #undef R3_TLOAD
 #undef R3_STORE
 #undef R3_LOAD
@@ -845,15 +758,12 @@ int lx3g_launch(const Lx3Args& x, void* stream) {
     static bool f_dev[ADER_MAX_DEV] = {};
     bool& f = f_dev[ader_cur_dev()];
     if (!f) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_lx3g<150>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * X3B_IMG_B);
-        if (e != hipSuccess) return (int)e;
-        e = hipFuncSetAttribute((const void*)k_lx3g<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * X3B_IMG_B);
+        hipError_t e = hipFuncSetAttribute((const void*)k_lx3g, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * X3B_IMG_B);
         if (e != hipSuccess) return (int)e;
         f = true;
     }
     if ((long)x.vrows * x.H * 4 >= (1l << 31)) return -2;          // the block offsets of the buffer loads are 32-bit
-    if (x.H == 150) hipLaunchKernelGGL(k_lx3g<150>, dim3(x.ranges * (x.Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
-    else hipLaunchKernelGGL(k_lx3g<0>, dim3(x.ranges * (x.Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
+    hipLaunchKernelGGL(k_lx3g, dim3(x.ranges * (x.Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
     return 0;
 }
 

@@ -27,12 +27,12 @@
 // 15 % SLOWER: gfx950 counts loads and stores in ONE in-order vmcnt, so the first load a wave waits for in tile t+1 also waits
 // for every store of tile t, whereas a workgroup that simply ends never waits for its stores.
 #include "lbf_common.h"
+#include "sparse_terms.h"
 #include "../../include/ader_hip.h"
 
 #define TI 64                      // table rows per workgroup
 #define PCS_ROW (LDR * 2 / 16)     // 16-byte pieces per bf16 operand row (21)
 #define NVEC 10                    // 16-byte vectors per thread covering a tile: 10 * 1024 floats >= 64 * 160 (+ 2 peeled)
-#define SPV 3                      // input-embedding gradient rows prefetched under the GEMM phase
 #define SPB 4                      // sparse-list entries per batch of the optimiser phase
 #define TM_LIST 18                 // ints per list in a tile record: [k0, k1, 8 x (id, row)]
 
@@ -296,67 +296,10 @@ __global__ __launch_bounds__(256, 2) void k_tab_upd(TabArgs a, FuseArgs f) {
         if (tid < H && id_lo < id_hi) {
             const int* ms = meta_l;
             const int* mg = meta_l + TM_LIST;
-            const int k0s = ms[0], k1s = ms[1];
-#pragma unroll
-            for (int i = 0; i < SPV; ++i) {                  // rows already in registers (same (id, row) order)
-                if (k0s + i < k1s) {
-                    const int id = ms[2 + 2 * i];
-                    if (id < id_hi) F_l[(id - id_lo) * H + tid] += spv[i];
-                }
-            }
-            // batches of SPB entries: ids and rows, then every gradient row, then the adds in entry order (one dependent memory
-            // round trip per entry made a hot item's workgroup the straggler of the launch; see table_update_sh.hip)
-            for (int k = k0s + SPV, i = SPV; k < k1s; k += SPB, i += SPB) {
-                int idv[SPB], rw[SPB];
-                float val[SPB];
-#pragma unroll
-                for (int u = 0; u < SPB; ++u) {
-                    const int ic = (i + u) < 8 ? (i + u) : 7;
-                    const int id_c = ms[2 + 2 * ic], row_c = ms[3 + 2 * ic];     // the first 8 entries: from the LDS record
-                    const bool in = k + u < k1s;
-                    int id_g = 0, row_g = 0;
-                    if (i + SPB > 8) {                           // (batch-uniform) later entries: from the global lists,
-                        const int ke = in ? k + u : k0s;         //  UNCONDITIONAL loads of an always-valid entry
-                        id_g = f.sp_ids[ke]; row_g = f.sp_rows[ke];
-                    }
-                    idv[u] = !in ? 0x7fffffff : ((i + u < 8) ? id_c : id_g);
-                    rw[u] = !in ? 0 : ((i + u < 8) ? row_c : row_g);
-                }
-#pragma unroll
-                for (int u = 0; u < SPB; ++u)      // (ids beyond max_item have no table row)
-                    val[u] = f.sp_src[(size_t)rw[u] * H + tid] * ((idv[u] < id_hi) ? f.sp_scale : 0.0f);
-#pragma unroll
-                for (int u = 0; u < SPB; ++u)
-                    if (idv[u] < id_hi) F_l[(idv[u] - id_lo) * H + tid] += val[u];
-            }
-            for (int k = mg[0], k1 = mg[1], i = 0; k < k1; k += SPB, i += SPB) {
-                int idv[SPB], bw[SPB];
-                float val[SPB];
-#pragma unroll
-                for (int u = 0; u < SPB; ++u) {
-                    const int ic = (i + u) < 8 ? (i + u) : 7;
-                    const int id_c = mg[2 + 2 * ic], b_c = mg[3 + 2 * ic];
-                    const bool in = k + u < k1;
-                    int id_g = 0, b_g = 0;
-                    if (i + SPB > 8) {
-                        const int ke = in ? k + u : mg[0];
-                        id_g = f.tg_ids[ke]; b_g = f.tg_rows[ke];
-                    }
-                    idv[u] = !in ? 0x7fffffff : ((i + u < 8) ? id_c : id_g);
-                    bw[u] = !in ? 0 : ((i + u < 8) ? b_c : b_g);
-                }
-#pragma unroll
-                for (int u = 0; u < SPB; ++u) {
-                    // (unconditional loads -- row 0 for entries that do not count: a load under a per-entry branch is waited for
-                    //  at the branch's end, one memory round trip per ENTRY instead of per batch)
-                    float rv = (float)a.rep_hi[(size_t)bw[u] * LDR + tid];
-                    if (X3) rv += (float)a.rep_lo[(size_t)bw[u] * LDR + tid];
-                    val[u] = rv * f.wrow[bw[u]] * ((idv[u] < id_hi) ? 1.0f : 0.0f);
-                }
-#pragma unroll
-                for (int u = 0; u < SPB; ++u)
-                    if (idv[u] < id_hi) F_l[(idv[u] - id_lo) * H + tid] -= val[u];
-            }
+#define UPD_TG_VAL(b_) (X3 ? (float)a.rep_hi[(size_t)(b_) * LDR + tid] + (float)a.rep_lo[(size_t)(b_) * LDR + tid] \
+                           : (float)a.rep_hi[(size_t)(b_) * LDR + tid]) * f.wrow[b_]
+            SPARSE_TERMS_LIGHT(SPB, spv, UPD_TG_VAL)
+#undef UPD_TG_VAL
         }
     }
     lds_only_barrier();

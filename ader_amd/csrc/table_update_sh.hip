@@ -6,6 +6,7 @@
 // the 128-row 32x32x16 predecessor of this kernel fitted two workgroups per CU: 0.95 ms against 0.90 ms per 10^6 rows).
 // table_update.hip serves the x3 mode and the gradient-only entry point.
 #include "lbf_common.h"
+#include "sparse_terms.h"
 #include "../../include/ader_hip.h"
 
 struct ShArgs {
@@ -34,7 +35,6 @@ struct FuseArgs128 {
     const float* extra1;        // EXTRA: dense gradient rows to add (row of item 1; [.,H] fp32), e.g. distilled rows' term
 };
 
-#define SPV 3                      // input-embedding gradient rows prefetched under the GEMM phase
 #define HEAVY_N 32                 // a bucket with more entries than this in either list takes the heavy path
 #define HVB 16                     // gradient rows in flight per thread on the heavy path
 #define SPB 8                      // sparse-list entries per batch of the optimiser phase (loads of a batch are independent)
@@ -282,65 +282,9 @@ __global__ __launch_bounds__(256, 3) void k_tab16(ShArgs a, FuseArgs128 f) {
         } else if (tid < H && id_lo < id_hi) {
             const int* ms = meta_l;
             const int* mg = meta_l + 18;
-            const int k0s = ms[0], k1s = ms[1];
-#pragma unroll
-            for (int i = 0; i < SPV; ++i) {                  // rows already in registers (same (id, row) order)
-                if (k0s + i < k1s) {
-                    const int id = ms[2 + 2 * i];
-                    if (id < id_hi) F_l[(id - id_lo) * H + tid] += spv[i];
-                }
-            }
-            // entries SPV..7 of the bucket are in the LDS record, the rest in the global lists.  Batches of SPB entries: ids and
-            // rows first, then every gradient row, then the adds in entry order (the order fixes the rounding) -- a hot item's
-            // bucket holds hundreds of entries, and one dependent memory round trip per ENTRY made its workgroup the straggler of
-            // the launch (Zipf ids: 1.02 ms against 0.84 ms for uniform ids).  The loads are UNCONDITIONAL (row 0 for entries that do
-            // not count): under a per-entry branch hipcc waits for each load at the end of its branch -- one round trip per entry
-            for (int k = k0s + SPV, i = SPV; k < k1s; k += SPB, i += SPB) {
-                int idv[SPB], rw[SPB];
-                float val[SPB];
-#pragma unroll
-                for (int u = 0; u < SPB; ++u) {
-                    const int ic = (i + u) < 8 ? (i + u) : 7;
-                    const int id_c = ms[2 + 2 * ic], row_c = ms[3 + 2 * ic];     // the first 8 entries: from the LDS record
-                    const bool in = k + u < k1s;
-                    int id_g = 0, row_g = 0;
-                    if (i + SPB > 8) {                           // (batch-uniform) later entries: from the global lists,
-                        const int ke = in ? k + u : k0s;         //  UNCONDITIONAL loads of an always-valid entry
-                        id_g = f.sp_ids[ke]; row_g = f.sp_rows[ke];
-                    }
-                    idv[u] = !in ? 0x7fffffff : ((i + u < 8) ? id_c : id_g);
-                    rw[u] = !in ? 0 : ((i + u < 8) ? row_c : row_g);
-                }
-#pragma unroll
-                for (int u = 0; u < SPB; ++u)      // (ids beyond max_item have no table row)
-                    val[u] = f.sp_src[(size_t)rw[u] * H + tid] * ((idv[u] < id_hi) ? f.sp_scale : 0.0f);
-#pragma unroll
-                for (int u = 0; u < SPB; ++u)
-                    if (idv[u] < id_hi) F_l[(idv[u] - id_lo) * H + tid] += val[u];
-            }
-            for (int k = mg[0], k1 = mg[1], i = 0; k < k1; k += SPB, i += SPB) {
-                int idv[SPB], bw[SPB];
-                float val[SPB];
-#pragma unroll
-                for (int u = 0; u < SPB; ++u) {
-                    const int ic = (i + u) < 8 ? (i + u) : 7;
-                    const int id_c = mg[2 + 2 * ic], b_c = mg[3 + 2 * ic];
-                    const bool in = k + u < k1;
-                    int id_g = 0, b_g = 0;
-                    if (i + SPB > 8) {
-                        const int ke = in ? k + u : mg[0];
-                        id_g = f.tg_ids[ke]; b_g = f.tg_rows[ke];
-                    }
-                    idv[u] = !in ? 0x7fffffff : ((i + u < 8) ? id_c : id_g);
-                    bw[u] = !in ? 0 : ((i + u < 8) ? b_c : b_g);
-                }
-#pragma unroll
-                for (int u = 0; u < SPB; ++u)
-                    val[u] = f.wrow[bw[u]] * (float)a.rep_bf[(size_t)bw[u] * LDR + tid] * ((idv[u] < id_hi) ? 1.0f : 0.0f);
-#pragma unroll
-                for (int u = 0; u < SPB; ++u)
-                    if (idv[u] < id_hi) F_l[(idv[u] - id_lo) * H + tid] -= val[u];
-            }
+#define SH_TG_VAL(b_) f.wrow[b_] * (float)a.rep_bf[(size_t)(b_) * LDR + tid]
+            SPARSE_TERMS_LIGHT(SPB, spv, SH_TG_VAL)
+#undef SH_TG_VAL
         }
     }
     if (heavy) { ROUND_LOAD(); }

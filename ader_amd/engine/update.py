@@ -109,7 +109,7 @@ class _Update:
             # (profiles/r5_packed/timeline_cfgY_update_late.txt)
             self._edge(self._side_lane(), main)
         with self._sec("logits_bwd_adam"):
-            if self.lx3:        # operand rows as the LDS images k_tab16x3 streams by LDS-DMA
+            if self.lx3:        # operand rows as the LDS images k_tab32x3 streams by LDS-DMA
                 img = self.buf("lbf_rep_img", (call("ader_x3_rep_image_bytes", D["Bp"]),), torch.uint8, zero=True)
                 if not sx.img_ready:
                     call("ader_x3_rep_image", ptr(D["rep_bf"]), ptr(D["rep_lo"]), D["Bp"], ptr(img), st)
