@@ -422,13 +422,7 @@ int ader_attn_fwd(const float* Q, const float* K, const float* V, const float* q
                   float* out, float* P, int B, int T, int H, int heads, const AderDrop* drop, void* stream) {
     if (B <= 0) return 0;
     if (T > TR || heads < 1 || H % heads != 0 || H / heads > 160) return -2;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnFwdLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_attn_fwd>(kAttnFwdLds)) return e;
     AttnArgs a;
     a.Q = Q; a.K = K; a.V = V; a.res = q_in; a.kmask = kmask; a.qmask = qmask; a.out = out; a.P = P;
     a.dQ = a.dK = a.dV = nullptr;
@@ -443,13 +437,7 @@ int ader_attn_bwd(const float* dO, const float* Q, const float* K, const float* 
                   const float* qmask, float* dQ, float* dK, float* dV, int B, int T, int H, int heads, const AderDrop* drop, void* stream) {
     if (B <= 0) return 0;
     if (T > TR || heads < 1 || H % heads != 0 || H / heads > 160) return -2;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnBwdLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_attn_bwd>(kAttnBwdLds)) return e;
     AttnArgs a;
     a.Q = Q; a.K = K; a.V = V; a.res = dO; a.kmask = kmask; a.qmask = qmask; a.out = nullptr; a.P = (float*)P;
     a.dQ = dQ; a.dK = dK; a.dV = dV;
@@ -475,13 +463,7 @@ int ader_attn_last_fwd(const float* Q_last, const float* K, const float* V, cons
     AttnLastArgs a;
     int rc = attn_last_args(a, B, T, H, heads, drop);
     if (rc) return rc;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_last_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnLastLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_attn_last_fwd>(kAttnLastLds)) return e;
     a.Ql = Q_last; a.K = K; a.V = V; a.res = q_in_last; a.kmask = kmask; a.qmask = qmask_last; a.out = out_last; a.P = P_last;
     a.dQl = a.dK = a.dV = nullptr;
     hipLaunchKernelGGL(k_attn_last_fwd, dim3(B * heads), dim3(256), kAttnLastLds, (hipStream_t)stream, a);

@@ -403,13 +403,7 @@ int ader_attn_x3_fwd(const float* Q, const float* K, const float* V, const float
     AttnX3Args a;
     int rc = x3_args(a, B, T, H, heads, drop);
     if (rc) return rc;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_x3_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_attn_x3_fwd>(kFwdLds)) return e;
     a.Q = Q; a.K = K; a.V = V; a.res = q_in; a.kmask = kmask; a.qmask = qmask; a.out = out; a.PT = PT;
     a.dQ = a.dK = a.dV = nullptr;
     hipLaunchKernelGGL(k_attn_x3_fwd, dim3(B * heads), dim3(128), kFwdLds, (hipStream_t)stream, a);
@@ -423,13 +417,7 @@ int ader_attn_x3_bwd(const float* dO, const float* Q, const float* K, const floa
     AttnX3Args a;
     int rc = x3_args(a, B, T, H, heads, drop);
     if (rc) return rc;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_x3_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBwdLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_attn_x3_bwd>(kBwdLds)) return e;
     a.Q = Q; a.K = K; a.V = V; a.res = dO; a.kmask = kmask; a.qmask = qmask; a.out = nullptr; a.PT = (float*)PT;
     a.dQ = dQ; a.dK = dK; a.dV = dV;
     hipLaunchKernelGGL(k_attn_x3_bwd, dim3(B * heads), dim3(256), kBwdLds, (hipStream_t)stream, a);

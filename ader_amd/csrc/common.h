@@ -10,13 +10,26 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// Launch-side caches (hipFuncSetAttribute done, CU count, largest dynamic-LDS size granted) are kept PER DEVICE: a function attribute
-// belongs to the device that was current when it was set, and a process may drive engines on several devices.
+// Launch-side caches (largest dynamic-LDS size granted, CU count) are kept PER DEVICE: a function attribute belongs to the device
+// that was current when it was set, and a process may drive engines on several devices.
 #define ADER_MAX_DEV 32
 static inline int ader_cur_dev() {
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= ADER_MAX_DEV) d = 0;
     return d;
+}
+// The dynamic-LDS opt-in of every launcher: kernel Kern may be launched with up to `bytes` of dynamic LDS on the current device.
+// The cache is the kernel's own (one per instantiation, whichever entry points launch it) and keeps the largest size granted, so a
+// fixed size costs one attribute call per device and a size that grows with the batch one per new maximum.  0, or the HIP error.
+template <auto Kern> static int ader_dyn_lds(size_t bytes) {
+    static int granted[ADER_MAX_DEV] = {};
+    int& g = granted[ader_cur_dev()];
+    if ((int)bytes > g) {
+        hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return (int)e;
+        g = (int)bytes;
+    }
+    return 0;
 }
 
 // status bits written by kernels into the engine's status word

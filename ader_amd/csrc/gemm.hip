@@ -143,13 +143,7 @@ static const size_t kGemmAtbLds = (size_t)(2 * TM * LDT) * sizeof(float);
 
 template <int EPI, bool TB>
 static int launch_rows(const GemmArgs& g, hipStream_t st) {
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_rows<EPI, TB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmRowsLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_gemm_rows<EPI, TB>>(kGemmRowsLds)) return e;
     const int n_tiles = (g.M + TM - 1) / TM;
     const int per = (n_tiles + 255) / 256;                 // tiles per workgroup, balanced over the 256 CUs
     const int grid = (n_tiles + per - 1) / per;
@@ -192,13 +186,7 @@ int ader_gemm_atb_slabs(int M) {
 int ader_gemm_atb(const float* A, const float* G, float* slab, float* dW, float* db, int M, int H, void* stream) {
     if (M <= 0) return 0;
     if (H >= HP || H < 1) return -2;     // needs one spare row for the ones-column bias trick
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_atb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmAtbLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_gemm_atb>(kGemmAtbLds)) return e;
     const int S = ader_gemm_atb_slabs(M);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_gemm_atb, dim3(S), dim3(256), kGemmAtbLds, st, A, G, slab, M, H);

@@ -435,16 +435,12 @@ int ader_herding_select(const float* rep, const long* seg, const int* quota, con
     hipStream_t st = (hipStream_t)stream;
     static int cus_dev[ADER_MAX_DEV] = {};
     int& cus = cus_dev[ader_cur_dev()];
-    static bool attr_dev[ADER_MAX_DEV] = {};
-    bool& attr = attr_dev[ader_cur_dev()];
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_herding_reg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHerdLds);
-        if (e != hipSuccess) return (int)e;
+    if (int e = ader_dyn_lds<k_herding_reg>(kHerdLds)) return e;
+    if (!cus) {
         int dev = 0;
         hipDeviceProp_t p;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return -3;
         cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-        attr = true;
     }
     hipError_t e = hipMemsetAsync(chosen, 0, (size_t)n_total, st);
     if (e != hipSuccess) return (int)e;

@@ -57,6 +57,32 @@ struct FuseArgs {
     float lr_t, omb1, omb2, eps;
     const float* extra1;        // EXTRA: dense gradient rows to add (row of item 1; [.,H] fp32), e.g. distilled rows' term
 };
+// host side: the fields FuseArgs shares with table_update_sh.hip's FuseArgs128, from the arguments of the C ABI (lists, tables
+// [item_num+1, H] and their shadow or NULL, Adam constants, extra_grad or NULL); the caller adds how its kernel finds a tile's
+// list entries (tile_meta / bucket offsets).  Everything else is zero.
+template <class F>
+static inline F fuse_args(const int* sp_ids, const int* sp_rows, int n_sp, const float* sp_src, float sp_scale, const int* tg_ids,
+                          const int* tg_rows, int n_tg, const float* wrow, float* emb, float* adam_m, float* adam_v, void* shadow, int H,
+                          float lr_t, float beta1, float beta2, float eps, const float* extra_grad) {
+    F f = {};
+    f.sp_ids = sp_ids; f.sp_rows = sp_rows; f.n_sp = n_sp; f.sp_src = sp_src; f.sp_scale = sp_scale;
+    f.tg_ids = tg_ids; f.tg_rows = tg_rows; f.n_tg = n_tg; f.wrow = wrow;
+    f.emb1 = emb + H; f.m1 = adam_m + H; f.v1 = adam_v + H; f.sh1w = shadow ? (bf16*)shadow + LDR : nullptr;
+    f.lr_t = lr_t; f.omb1 = 1.0f - beta1; f.omb2 = 1.0f - beta2; f.eps = eps;
+    f.extra1 = extra_grad ? extra_grad + H : nullptr;
+    return f;
+}
+// The tile range of a fused update: the C ABI counts 128-item tiles [tile_begin, tile_begin + tile_count) (tile_count < 0: all; a
+// rank's rows of a row-sharded table), the kernels 64-row tiles.  *t0 / *tiles: the first 64-row tile and how many, clipped to the
+// ceil(N / 64) that exist; false: none.
+static inline bool tab_tile_range(int N, int tile_begin, int tile_count, int* t0, int* tiles) {
+    const int all = (N + 63) / 64;
+    const int tb = (tile_begin < 0 ? 0 : tile_begin) * 2;
+    int te = tile_count < 0 ? all : tb + tile_count * 2;
+    if (te > all) te = all;
+    *t0 = tb; *tiles = te - tb;
+    return te > tb;
+}
 
 // arguments of the fp32-table update kernels (table_update.hip: k_tab_upd, table_update_x3.hip: k_tab32x3); tiles are 64 rows
 struct TabArgs {
@@ -74,6 +100,18 @@ struct TabArgs {
     int kd_row0, Np;
     const float* teacher; long ldt; const int* trow; const float* tlse2;
 };
+// host side: the table slice, the operand planes (rep_lo NULL: bf16 grade), the batch and the catalog, no distilled rows; the launcher
+// sets tile_off / rep_img / demb1 where it has them, and tab_args_kd adds the distilled rows
+static inline TabArgs tab_args(const float* emb1, int vrows, const void* rep_hi, const void* rep_lo, const float* off, int Bp, int H,
+                               int N) {
+    TabArgs a = {};
+    a.emb1 = emb1; a.vrows = vrows; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo; a.off = off;
+    a.Bp = Bp; a.H = H; a.N = N; a.kd_row0 = Bp;
+    return a;
+}
+static inline void tab_args_kd(TabArgs& a, int kd_row0, int Np, const float* teacher, long ldt, const int* trow, const float* tlse2) {
+    a.kd_row0 = kd_row0; a.Np = Np; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
+}
 
 // arguments of the x3 flash forward kernels (logits_bf16.hip: k_lx3_fwd, logits_x3.hip: k_lx3g / k_lx3p / k_lx3r)
 struct Lx3Args {
@@ -87,3 +125,15 @@ struct Lx3Args {
     const float* teacher; long ldt; const int* trow; const float* tlse2; float* pO2;
     int ranges2;                // item ranges of the readout launch (it is a launch of its own in x3 mode: its own partition)
 };
+// host side: the table slice, the operand planes, the batch, the catalog and the softmax partials, no distilled rows; lx3_args_kd adds them
+static inline Lx3Args lx3_args(const float* emb1, int vrows, const void* rep_hi, const void* rep_lo, int Bp, int H, int N, int ranges,
+                               float* pm, float* pl, float* pO) {
+    Lx3Args x = {};
+    x.emb1 = emb1; x.vrows = vrows; x.rep_hi = (const bf16*)rep_hi; x.rep_lo = (const bf16*)rep_lo;
+    x.Bp = Bp; x.H = H; x.N = N; x.ranges = ranges; x.pm = pm; x.pl = pl; x.pO = pO; x.kd_row0 = Bp;
+    return x;
+}
+static inline void lx3_args_kd(Lx3Args& x, int kd_row0, int Np, const float* teacher, long ldt, const int* trow, const float* tlse2,
+                               float* pO2, int ranges2) {
+    x.kd_row0 = kd_row0; x.Np = Np; x.teacher = teacher; x.ldt = ldt; x.trow = trow; x.tlse2 = tlse2; x.pO2 = pO2; x.ranges2 = ranges2;
+}

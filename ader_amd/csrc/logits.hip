@@ -401,16 +401,6 @@ static const size_t kTileLds = (size_t)(2 * 64 * LDE + 4 * TB * 3 + MAXB * 3) * 
 static const size_t kBwdLds = (size_t)(2 * 64 * LDE + 64 * LDD) * sizeof(float);
 static const size_t kTgtLds = (size_t)(2 * 64 * LDE) * sizeof(float);
 
-template <typename K>
-static int set_lds(K kern, size_t bytes, bool& flag) {
-    if (!flag) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return (int)e;
-        flag = true;
-    }
-    return 0;
-}
-
 static int fill_args(LogitArgs& a, const float* rep, const float* emb, int B, int Bp, int H, int N, const int* lab, const int* ncol,
                      const float* wrow, const int* trow, const float* tlse, const float* teacher, long ldt) {
     if (Bp % TB != 0 || Bp > MAXB || B > Bp || H > HP || H < 1) return -2;
@@ -468,9 +458,7 @@ int ader_logits_loss_fwd(const float* rep, const float* emb, int B, int Bp, int 
     LogitArgs a;
     int rc = fill_args(a, rep, emb, B, Bp, H, N, lab, ncol, wrow, trow, tlse, teacher, ldt);
     if (rc) return rc;
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    rc = set_lds(k_logits_tile<MODE_LSE>, kTileLds, f);
+    rc = ader_dyn_lds<k_logits_tile<MODE_LSE>>(kTileLds);
     if (rc) return rc;
     a.part = part; a.sub = ader_logits_sub(N);
     const int parts = ader_logits_parts(N);
@@ -490,9 +478,7 @@ int ader_logits_bwd_drep(const float* rep, const float* emb, int B, int Bp, int 
     LogitArgs a;
     int rc = fill_args(a, rep, emb, B, Bp, H, N, lab, ncol, wrow, trow, tlse, teacher, ldt);
     if (rc) return rc;
-    static bool f1_dev[ADER_MAX_DEV] = {};
-    bool& f1 = f1_dev[ader_cur_dev()];
-    rc = set_lds(k_logits_bwd_drep, kBwdLds, f1);
+    rc = ader_dyn_lds<k_logits_bwd_drep>(kBwdLds);
     if (rc) return rc;
     a.lse = lse; a.slab = slab; a.ranges = ader_logits_ranges(N, Bp);
     const int nchunk = Bp / TB;
@@ -509,9 +495,7 @@ int ader_logits_bwd_demb(const float* rep, const float* emb, int B, int Bp, int 
     LogitArgs a;
     int rc = fill_args(a, rep, emb, B, Bp, H, N, lab, ncol, wrow, trow, tlse, teacher, ldt);
     if (rc) return rc;
-    static bool f2_dev[ADER_MAX_DEV] = {};
-    bool& f2 = f2_dev[ader_cur_dev()];
-    rc = set_lds(k_logits_bwd_de, kBwdLds, f2);
+    rc = ader_dyn_lds<k_logits_bwd_de>(kBwdLds);
     if (rc) return rc;
     a.lse = lse; a.demb1 = demb + H;
     hipLaunchKernelGGL(k_logits_bwd_de, dim3((N + TI - 1) / TI), dim3(512), kBwdLds, (hipStream_t)stream, a);
@@ -526,9 +510,7 @@ int ader_logits_store(const float* rep, const float* emb, int B, int Bp, int H, 
     LogitArgs a;
     int rc = fill_args(a, rep, emb, B, Bp, H, N, nullptr, ncol_all, nullptr, nullptr, nullptr, nullptr, 0);
     if (rc) return rc;
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    rc = set_lds(k_logits_tile<MODE_STORE>, kTileLds, f);
+    rc = ader_dyn_lds<k_logits_tile<MODE_STORE>>(kTileLds);
     if (rc) return rc;
     a.out = out; a.ldo = ldo;
     hipLaunchKernelGGL(k_logits_tile<MODE_STORE>, dim3((N + TI - 1) / TI), dim3(512), kTileLds, (hipStream_t)stream, a);
@@ -544,12 +526,9 @@ int ader_rank_targets(const float* rep, const float* emb, int B, int Bp, int H, 
     LogitArgs a;
     int rc = fill_args(a, rep, emb, B, Bp, H, N, target, ncol, nullptr, nullptr, nullptr, nullptr, 0);
     if (rc) return rc;
-    static bool f1_dev[ADER_MAX_DEV] = {}, f2_dev[ADER_MAX_DEV] = {};
-    bool& f1 = f1_dev[ader_cur_dev()];
-    bool& f2 = f2_dev[ader_cur_dev()];
-    rc = set_lds(k_logits_tile<MODE_RANK>, kTileLds, f1);
+    rc = ader_dyn_lds<k_logits_tile<MODE_RANK>>(kTileLds);
     if (rc) return rc;
-    rc = set_lds(k_target_logit, kTgtLds, f2);
+    rc = ader_dyn_lds<k_target_logit>(kTgtLds);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(rank, 0, sizeof(int) * (size_t)Bp, st);

@@ -1,6 +1,8 @@
-// Full-catalog logits + softmax cross-entropy, bf16-MFMA path (fp32 master table, fp32 accumulation and softmax).
-// Reference: ADER.py:88-93 (logits = rep . item_emb^T, one-hot softmax CE) and its gradient.  One-hot rows only
-// (vanilla loss / disable_distillation); distilled rows use the float32 path of logits.hip.
+// Full-catalog logits + softmax cross-entropy on the bf16 matrix cores (fp32 master table, fp32 accumulation and softmax).
+// Reference: ADER.py:88-93 (logits = rep . item_emb^T, one-hot softmax CE), ADER.py:132-137 (distilled rows) and their gradients.
+// This file holds the bf16 flash forward (k_lbf_fwd) and the merges of its partials, the generic float32-grade (x3) forward k_lx3_fwd
+// (three bf16 MFMAs per product on the fp32 table; the block-image x3 forwards are in logits_x3.hip and share the merges), and the
+// C ABI of both grades, one-hot and distilled rows, including the catalog-sharded forms (_shard / _merge_parts).
 //
 // Two streaming passes over the table instead of the TF graph's materialised [B,N] logits/softmax/one-hot:
 //
@@ -110,9 +112,25 @@ struct LbfArgs {
     int ranges2;                // item ranges of the readout (= ranges when it shares the forward's launch)
 };
 
-static inline void lbf_no_kd(LbfArgs& a) {
-    a.kd_row0 = a.Bp; a.Np = 0; a.n_train = a.B; a.n_ex = 0; a.teacher = nullptr; a.ldt = 0; a.trow = nullptr; a.tlse2 = nullptr;
-    a.pO2 = nullptr; a.ranges2 = 0;
+// host side (as logits.hip's fill_args): the table slice (sh1 NULL: an x3 forward's merge), the batch, the catalog and the softmax
+// partials, no distilled rows; lbf_args_kd adds them.  Everything else is zero.
+static inline LbfArgs lbf_args(const bf16* sh1, int vrows, const void* rep_bf, int B, int Bp, int H, int N, int ranges, float* pm, float* pl,
+                               float* pO) {
+    LbfArgs a = {};
+    a.sh1 = sh1; a.vrows = vrows; a.rep_bf = (const bf16*)rep_bf; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ranges = ranges;
+    a.pm = pm; a.pl = pl; a.pO = pO; a.kd_row0 = Bp; a.n_train = B;
+    return a;
+}
+static inline void lbf_args_kd(LbfArgs& a, int kd_row0, int Np, int n_train, int n_ex, const float* teacher, long ldt, const int* trow,
+                               const float* tlse2, float* pO2, int ranges2) {
+    a.kd_row0 = kd_row0; a.Np = Np; a.n_train = n_train; a.n_ex = n_ex; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
+    a.pO2 = pO2; a.ranges2 = ranges2;
+}
+// the merge kernels' view of an x3 forward: its partials and its distilled rows (none: n_train = the batch rows, n_ex = 0)
+static inline LbfArgs lbf_args_of(const Lx3Args& x, int n_train, int n_ex) {
+    LbfArgs a = lbf_args(nullptr, x.vrows, x.rep_hi, n_train + n_ex, x.Bp, x.H, x.N, x.ranges, x.pm, x.pl, x.pO);
+    lbf_args_kd(a, x.kd_row0, x.Np, n_train, n_ex, x.teacher, x.ldt, x.trow, x.tlse2, x.pO2, x.ranges2);
+    return a;
 }
 
 #define FB 32                      // items per streamed block
@@ -590,9 +608,9 @@ __global__ __launch_bounds__(256) void k_lx3_prep(const float* __restrict__ rep,
 
 
 #define XPPT 5                     // 16-byte fp32 vectors per thread per 32-item block (5 * 1024 floats >= 32 * 160)
-// XRD = register ring depth, OCC = workgroups per CU the register budget is sized for (256 / 512 registers per lane)
-template <int XRD, int OCC, bool READOUT = false>
-__global__ __launch_bounds__(256, OCC) void k_lx3_fwd(Lx3Args a) {
+#define XRING 2                    // register ring depth: table blocks in flight per workgroup
+template <bool READOUT>             // (two workgroups per CU: the register budget is 256 of the 512 registers per lane)
+__global__ __launch_bounds__(256, 2) void k_lx3_fwd(Lx3Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16* E_l = (bf16*)smem_raw;                       // [2 buffers][2 planes: hi, lo][FB][LDR]
     typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -646,8 +664,8 @@ __global__ __launch_bounds__(256, OCC) void k_lx3_fwd(Lx3Args a) {
         const int c1 = col + 2;
         lo1[j] = (e + 2 < nfl) ? ((c1 >= H) ? (row + 1) * LDR + (c1 - H) : row * LDR + c1) : -1;
     }
-    f32x4_t ring[XRD][XPPT];
-    f32x2_t ringh[XRD];
+    f32x4_t ring[XRING][XPPT];
+    f32x2_t ringh[XRING];
 #define LX3_LOAD(slot_, blk_)                                                                            \
     {                                                                                                    \
         const float* src_ = a.emb1 + (size_t)(blk_) * FB * H;                                            \
@@ -688,18 +706,18 @@ __global__ __launch_bounds__(256, OCC) void k_lx3_fwd(Lx3Args a) {
         const int Np = N;
         float tc[16], tn[16];
 #pragma unroll
-        for (int s_ = 0; s_ < XRD; ++s_) if (s_ < nb_blocks) LX3_LOAD(s_, blk_begin + s_);
+        for (int s_ = 0; s_ < XRING; ++s_) if (s_ < nb_blocks) LX3_LOAD(s_, blk_begin + s_);
         if (nb_blocks > 0) LBF_TLOAD(tc, blk_begin);
         __syncthreads();
         int cur = 0, i = 0;
         while (i < nb_blocks) {
 #pragma unroll
-            for (int s_ = 0; s_ < XRD; ++s_) {
+            for (int s_ = 0; s_ < XRING; ++s_) {
                 if (i >= nb_blocks) break;
                 const int blk = blk_begin + i;
                 const int i0 = blk * FB;
                 LX3_STORE(s_, cur);
-                if (i + XRD < nb_blocks) LX3_LOAD(s_, blk + XRD);
+                if (i + XRING < nb_blocks) LX3_LOAD(s_, blk + XRING);
                 if (i + 1 < nb_blocks) { LBF_TLOAD(tn, blk + 1); }
                 __syncthreads();
                 const bf16* Eh = E_l + cur * 2 * FB * LDR;
@@ -749,16 +767,16 @@ __global__ __launch_bounds__(256, OCC) void k_lx3_fwd(Lx3Args a) {
     }
     else {
 #pragma unroll
-    for (int s_ = 0; s_ < XRD; ++s_) if (s_ < nb_blocks) LX3_LOAD(s_, blk_begin + s_);
+    for (int s_ = 0; s_ < XRING; ++s_) if (s_ < nb_blocks) LX3_LOAD(s_, blk_begin + s_);
     __syncthreads();                                    // zero fill done before the first block store
     int cur = 0, i = 0;
     while (i < nb_blocks) {
 #pragma unroll
-        for (int s_ = 0; s_ < XRD; ++s_) {
+        for (int s_ = 0; s_ < XRING; ++s_) {
             if (i >= nb_blocks) break;                  // workgroup-uniform
             const int blk = blk_begin + i;
             LX3_STORE(s_, cur);
-            if (i + XRD < nb_blocks) LX3_LOAD(s_, blk + XRD);
+            if (i + XRING < nb_blocks) LX3_LOAD(s_, blk + XRING);
             __syncthreads();
             const bf16* Eh = E_l + cur * 2 * FB * LDR;
             const bf16* El = Eh + FB * LDR;
@@ -849,11 +867,30 @@ int lx3p_launch(const Lx3Args& x, void* stream);
 // lx3r_supports: H = 150, 16-byte aligned teacher rows, at least one whole block
 bool lx3r_supports(const Lx3Args& x);
 int lx3r_launch(const Lx3Args& x, void* stream);
-// 2: the block-image kernels (Bp % 128 == 0 and a supported H), 0: k_lx3_fwd
-static int lx3_kind(int H, int Bp) { return lx3f_supports(H) && Bp % 128 == 0 ? 2 : 0; }
 
 // ============================================================================================= C ABI
-static const size_t kFwdLds = (size_t)2 * FB * LDR * sizeof(bf16);
+static const size_t kFwdLds = (size_t)2 * FB * LDR * sizeof(bf16);          // k_lbf_fwd: two buffers of one block
+static const size_t kLx3FwdLds = 2 * kFwdLds;                               // k_lx3_fwd: ... of two planes (hi, lo)
+
+// x3 forward of x.ranges item ranges x Bp / 128 chunks: the block-image kernels where they take H, else k_lx3_fwd
+static int lx3_forward(const Lx3Args& x, void* stream) {
+    if (lx3f_supports(x.H)) return lx3p_launch(x, stream);
+    if (int e = ader_dyn_lds<k_lx3_fwd<false>>(kLx3FwdLds)) return e;
+    hipLaunchKernelGGL(k_lx3_fwd<false>, dim3(x.ranges * (x.Bp / 128)), dim3(256), kLx3FwdLds, (hipStream_t)stream, x);
+    return 0;
+}
+// teacher readout of x.ranges2 item ranges x (Bp - kd_row0) / 128 chunks: k_lx3r where it takes the shape, else k_lx3_fwd's readout form
+static int lx3_readout(const Lx3Args& x, void* stream) {
+    if (lx3r_supports(x)) return lx3r_launch(x, stream);
+    if (int e = ader_dyn_lds<k_lx3_fwd<true>>(kLx3FwdLds)) return e;
+    hipLaunchKernelGGL(k_lx3_fwd<true>, dim3(x.ranges2 * ((x.Bp - x.kd_row0) / 128)), dim3(256), kLx3FwdLds, (hipStream_t)stream, x);
+    return 0;
+}
+// items of the shard [item_begin + 1, item_begin + item_count] that lie within the first N
+static int shard_items(int N, int item_begin, int item_count) {
+    const int n = N - item_begin < item_count ? N - item_begin : item_count;
+    return n < 0 ? 0 : n;
+}
 
 extern "C" {
 
@@ -890,19 +927,10 @@ int ader_lbf_fwd(const float* rep, const void* shadow, int item_num, int B, int 
                  void* stream) {
     if (B <= 0) return 0;
     if (Bp % 128 != 0 || B > Bp || H > HP || (H & 1) || H < 2) return -2;
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    if (!f) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_lbf_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLds);
-        if (e != hipSuccess) return (int)e;
-        f = true;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    LbfArgs a;
+    if (int e = ader_dyn_lds<k_lbf_fwd>(kFwdLds)) return e;
     if (N > item_num) return -2;
-    a.sh1 = (const bf16*)shadow + LDR; a.vrows = item_num; a.tile_off = 0;
-    a.rep_bf = (const bf16*)rep_bf; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ranges = ader_lbf_ranges(N, Bp);
-    a.pm = pm; a.pl = pl; a.pO = pO; a.off = nullptr; a.demb1 = nullptr; lbf_no_kd(a);
+    hipStream_t st = (hipStream_t)stream;
+    const LbfArgs a = lbf_args((const bf16*)shadow + LDR, item_num, rep_bf, B, Bp, H, N, ader_lbf_ranges(N, Bp), pm, pl, pO);
     hipLaunchKernelGGL(k_lbf_prep, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_bf, B, Bp, H);
     hipLaunchKernelGGL(k_lbf_fwd, dim3(a.ranges * (Bp / 128)), dim3(256), kFwdLds, st, a);
     hipLaunchKernelGGL(k_lbf_combine<false>, dim3(Bp), dim3(640), 0, st, a, lab, wrow, lse, off, rowloss, drep, (const float*)nullptr,
@@ -925,22 +953,11 @@ int ader_lbf_fwd_kd(const float* rep, const void* shadow, int item_num, int n_tr
     if (n_train + n_ex <= 0) return 0;
     if (Bp % 128 != 0 || kd_row0 % 128 != 0 || n_train > kd_row0 || kd_row0 + n_ex > Bp || H > HP || (H & 1) || H < 2 || N > item_num ||
         Np > N || Np < 1) return -2;
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    if (!f) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_lbf_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLds);
-        if (e != hipSuccess) return (int)e;
-        f = true;
-    }
+    if (int e = ader_dyn_lds<k_lbf_fwd>(kFwdLds)) return e;
     hipStream_t st = (hipStream_t)stream;
-    LbfArgs a;
-    a.sh1 = (const bf16*)shadow + LDR; a.vrows = item_num; a.tile_off = 0;
-    a.rep_bf = (const bf16*)rep_bf; a.B = n_train + n_ex; a.Bp = Bp; a.H = H; a.N = N;
+    LbfArgs a = lbf_args((const bf16*)shadow + LDR, item_num, rep_bf, n_train + n_ex, Bp, H, N, ader_lbf_ranges_kd(N, Bp, kd_row0), pm, pl, pO);
+    lbf_args_kd(a, kd_row0, Np, n_train, n_ex, teacher, ldt, trow, tlse2, pO2, ader_lbf_readout_ranges(N, Bp, kd_row0));
     const int nsm = Bp / 128, nkd = (Bp - kd_row0) / 128;
-    a.ranges = ader_lbf_ranges_kd(N, Bp, kd_row0);
-    a.pm = pm; a.pl = pl; a.pO = pO; a.off = nullptr; a.demb1 = nullptr;
-    a.kd_row0 = kd_row0; a.Np = Np; a.n_train = n_train; a.n_ex = n_ex; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
-    a.pO2 = pO2; a.ranges2 = ader_lbf_readout_ranges(N, Bp, kd_row0);
     hipLaunchKernelGGL(k_lbf_prep_kd, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_bf, (bf16*)nullptr, n_train, n_ex,
                        kd_row0, Bp, H, pos, ex_trow, tlse_all, w_train, w_ex, lab, wrow, trow, tlse2, (char*)nullptr);
     hipLaunchKernelGGL(k_lbf_fwd, dim3(a.ranges * nsm + a.ranges2 * nkd), dim3(256), kFwdLds, st, a);
@@ -980,22 +997,11 @@ int ader_lbf_fwd_shard(const void* rep_bf, const void* shadow, int item_num, int
                        float* pm, float* pl, float* pO, float* part, void* stream) {
     if (Bp <= 0) return 0;
     if (Bp % 128 != 0 || H > HP || (H & 1) || H < 2 || N > item_num || item_begin < 0) return -2;
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    if (!f) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_lbf_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLds);
-        if (e != hipSuccess) return (int)e;
-        f = true;
-    }
+    if (int e = ader_dyn_lds<k_lbf_fwd>(kFwdLds)) return e;
     hipStream_t st = (hipStream_t)stream;
-    int n_loc = N - item_begin;
-    if (n_loc > item_count) n_loc = item_count;
-    if (n_loc < 0) n_loc = 0;
-    LbfArgs a;
-    a.sh1 = (const bf16*)shadow + (size_t)LDR * (1 + item_begin); a.vrows = item_num - item_begin; a.tile_off = 0;
-    a.rep_bf = (const bf16*)rep_bf; a.B = Bp; a.Bp = Bp; a.H = H; a.N = n_loc;
-    a.ranges = n_loc > 0 ? ader_lbf_ranges(n_loc, Bp) : 0;
-    a.pm = pm; a.pl = pl; a.pO = pO; a.off = nullptr; a.demb1 = nullptr; lbf_no_kd(a);
+    const int n_loc = shard_items(N, item_begin, item_count);
+    const LbfArgs a = lbf_args((const bf16*)shadow + (size_t)LDR * (1 + item_begin), item_num - item_begin, rep_bf, Bp, Bp, H, n_loc,
+                               n_loc > 0 ? ader_lbf_ranges(n_loc, Bp) : 0, pm, pl, pO);
     if (a.ranges > 0) hipLaunchKernelGGL(k_lbf_fwd, dim3(a.ranges * (Bp / 128)), dim3(256), kFwdLds, st, a);
     hipLaunchKernelGGL(k_lbf_combine_partial, dim3(Bp), dim3(640), 0, st, a, part);
     HIP_LAUNCH_CHECK();
@@ -1028,21 +1034,6 @@ int ader_lx3_prep(const float* rep, void* rep_hi, void* rep_lo, int B, int Bp, i
 
 // Forward of the one-hot softmax CE over items 1..N at float32 grade (three bf16 MFMAs per product), streaming the fp32
 // table itself.  Same scratch and outputs as ader_lbf_fwd; rep_hi / rep_lo: Bp*168 bf16 each.
-static int lx3_attr() {
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    if (!f) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_lx3_fwd<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)((size_t)2 * 2 * FB * LDR * sizeof(bf16)));
-        if (e != hipSuccess) return (int)e;
-        e = hipFuncSetAttribute((const void*)k_lx3_fwd<2, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((size_t)2 * 2 * FB * LDR * sizeof(bf16)));
-        if (e != hipSuccess) return (int)e;
-        f = true;
-    }
-    return 0;
-}
-
 int ader_lx3_fwd_img(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* lab, const float* wrow,
                      void* rep_hi, void* rep_lo, float* pm, float* pl, float* pO, float* lse, float* off, float* rowloss, float* loss,
                      float* drep, void* rep_img, void* stream);
@@ -1068,21 +1059,11 @@ int ader_lx3_fwd_img_lnf(const float* rep, const float* emb, int item_num, int B
     if (B <= 0) return 0;
     if (rep_img && ((uintptr_t)rep_img & 15)) return -2;
     if (Bp % 128 != 0 || B > Bp || H > HP || (H & 1) || H < 2 || N > item_num || ((uintptr_t)emb & 7)) return -2;
-    const size_t lds = (size_t)2 * 2 * FB * LDR * sizeof(bf16);
-    int rc = lx3_attr();
-    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    Lx3Args x;
-    x.emb1 = emb + H; x.vrows = item_num; x.rep_hi = (const bf16*)rep_hi; x.rep_lo = (const bf16*)rep_lo;
-    const int nk = lx3_kind(H, Bp);
-    x.Bp = Bp; x.H = H; x.N = N; x.ranges = ader_lbf_ranges(N, Bp); x.pm = pm; x.pl = pl; x.pO = pO;
-    x.kd_row0 = Bp; x.Np = 0; x.teacher = nullptr; x.ldt = 0; x.trow = nullptr; x.tlse2 = nullptr; x.pO2 = nullptr; x.ranges2 = 0;
-    LbfArgs a;
-    a.sh1 = nullptr; a.vrows = item_num; a.tile_off = 0; a.rep_bf = (const bf16*)rep_hi; a.B = B; a.Bp = Bp; a.H = H; a.N = N;
-    a.ranges = x.ranges; a.pm = pm; a.pl = pl; a.pO = pO; a.off = nullptr; a.demb1 = nullptr; lbf_no_kd(a);
+    const Lx3Args x = lx3_args(emb + H, item_num, rep_hi, rep_lo, Bp, H, N, ader_lbf_ranges(N, Bp), pm, pl, pO);
+    const LbfArgs a = lbf_args_of(x, B, 0);
     hipLaunchKernelGGL(k_lx3_prep, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_hi, (bf16*)rep_lo, B, Bp, H, (char*)rep_img);
-    if (nk) { rc = lx3p_launch(x, stream); if (rc) return rc; }
-    else hipLaunchKernelGGL((k_lx3_fwd<2, 2>), dim3(x.ranges * (Bp / 128)), dim3(256), lds, st, x);
+    if (int rc = lx3_forward(x, stream)) return rc;
     hipLaunchKernelGGL(k_lbf_combine<true>, dim3(Bp), dim3(640), 0, st, a, lab, wrow, lse, off, rowloss, drep, emb + H, rep,
                        lnf ? *lnf : AderLnfBwd{});
     if (loss) hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, B, loss);     // NULL: ader_lbf_sum later (off the critical path)
@@ -1126,27 +1107,14 @@ int ader_lx3_fwd_kd_lnf(const float* rep, const float* emb, int item_num, int n_
     if (n_train + n_ex <= 0) return 0;
     if (Bp % 128 != 0 || kd_row0 % 128 != 0 || n_train > kd_row0 || kd_row0 + n_ex > Bp || H > HP || (H & 1) || H < 2 || N > item_num ||
         Np > N || Np < 1 || ((uintptr_t)emb & 7) || ((uintptr_t)rep_img & 15)) return -2;
-    const size_t lds = (size_t)2 * 2 * FB * LDR * sizeof(bf16);
-    int rc = lx3_attr();
-    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    Lx3Args x;
-    x.emb1 = emb + H; x.vrows = item_num; x.rep_hi = (const bf16*)rep_hi; x.rep_lo = (const bf16*)rep_lo;
-    const int nk = lx3_kind(H, Bp);
-    x.Bp = Bp; x.H = H; x.N = N; x.ranges = ader_lbf_ranges(N, Bp); x.pm = pm; x.pl = pl; x.pO = pO;
-    x.kd_row0 = kd_row0; x.Np = Np; x.teacher = teacher; x.ldt = ldt; x.trow = trow; x.tlse2 = tlse2; x.pO2 = pO2;
-    x.ranges2 = ader_lx3_readout_ranges(Np, Bp - kd_row0);
-    LbfArgs a;
-    a.sh1 = nullptr; a.vrows = item_num; a.tile_off = 0; a.rep_bf = (const bf16*)rep_hi; a.B = n_train + n_ex; a.Bp = Bp; a.H = H; a.N = N;
-    a.ranges = x.ranges; a.pm = pm; a.pl = pl; a.pO = pO; a.off = nullptr; a.demb1 = nullptr;
-    a.kd_row0 = kd_row0; a.Np = Np; a.n_train = n_train; a.n_ex = n_ex; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
-    a.pO2 = pO2; a.ranges2 = x.ranges2;
+    Lx3Args x = lx3_args(emb + H, item_num, rep_hi, rep_lo, Bp, H, N, ader_lbf_ranges(N, Bp), pm, pl, pO);
+    lx3_args_kd(x, kd_row0, Np, teacher, ldt, trow, tlse2, pO2, ader_lx3_readout_ranges(Np, Bp - kd_row0));
+    const LbfArgs a = lbf_args_of(x, n_train, n_ex);
     hipLaunchKernelGGL(k_lbf_prep_kd, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_hi, (bf16*)rep_lo, n_train, n_ex,
                        kd_row0, Bp, H, pos, ex_trow, tlse_all, w_train, w_ex, lab, wrow, trow, tlse2, (char*)rep_img);
-    if (nk) { rc = lx3p_launch(x, stream); if (rc) return rc; }
-    else hipLaunchKernelGGL((k_lx3_fwd<2, 2>), dim3(x.ranges * (Bp / 128)), dim3(256), lds, st, x);
-    if (lx3r_supports(x)) { rc = lx3r_launch(x, stream); if (rc) return rc; }
-    else hipLaunchKernelGGL((k_lx3_fwd<2, 2, true>), dim3(x.ranges2 * ((Bp - kd_row0) / 128)), dim3(256), lds, st, x);
+    if (int rc = lx3_forward(x, stream)) return rc;
+    if (int rc = lx3_readout(x, stream)) return rc;
     hipLaunchKernelGGL(k_lbf_combine<true>, dim3(Bp), dim3(640), 0, st, a, (const int*)lab, (const float*)wrow, lse, off, rowloss, drep,
                        emb + H, rep, lnf ? *lnf : AderLnfBwd{});
     if (loss) hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, Bp, loss);     // NULL: ader_lbf_sum(rowloss, Bp) later
@@ -1163,26 +1131,12 @@ int ader_lx3_fwd_shard(const void* rep_hi, const void* rep_lo, const float* emb,
     if (Bp <= 0) return 0;
     if (Bp % 128 != 0 || H > HP || (H & 1) || H < 2 || N > item_num || item_begin < 0 || ((uintptr_t)emb & 7)) return -2;
     hipStream_t st = (hipStream_t)stream;
-    int n_loc = N - item_begin;
-    if (n_loc > item_count) n_loc = item_count;
-    if (n_loc < 0) n_loc = 0;
-    Lx3Args x;
-    x.emb1 = emb + (size_t)H * (1 + item_begin); x.vrows = item_num - item_begin;
-    x.rep_hi = (const bf16*)rep_hi; x.rep_lo = (const bf16*)rep_lo;
-    x.Bp = Bp; x.H = H; x.N = n_loc; x.ranges = n_loc > 0 ? ader_lbf_ranges(n_loc, Bp) : 0; x.pm = pm; x.pl = pl; x.pO = pO;
-    x.kd_row0 = Bp; x.Np = 0; x.teacher = nullptr; x.ldt = 0; x.trow = nullptr; x.tlse2 = nullptr; x.pO2 = nullptr; x.ranges2 = 0;
-    LbfArgs a;
-    a.sh1 = nullptr; a.vrows = x.vrows; a.tile_off = 0; a.rep_bf = (const bf16*)rep_hi; a.B = Bp; a.Bp = Bp; a.H = H; a.N = n_loc;
-    a.ranges = x.ranges; a.pm = pm; a.pl = pl; a.pO = pO; a.off = nullptr; a.demb1 = nullptr; lbf_no_kd(a);
-    if (x.ranges > 0) {
-        int rc = 0;
-        if (lx3_kind(H, Bp) == 2) rc = lx3p_launch(x, stream);
-        else {
-            rc = lx3_attr();
-            if (!rc) hipLaunchKernelGGL((k_lx3_fwd<2, 2>), dim3(x.ranges * (Bp / 128)), dim3(256), (size_t)2 * 2 * FB * LDR * sizeof(bf16), st, x);
-        }
-        if (rc) return rc;
-    }
+    const int n_loc = shard_items(N, item_begin, item_count);
+    const Lx3Args x = lx3_args(emb + (size_t)H * (1 + item_begin), item_num - item_begin, rep_hi, rep_lo, Bp, H, n_loc,
+                               n_loc > 0 ? ader_lbf_ranges(n_loc, Bp) : 0, pm, pl, pO);
+    const LbfArgs a = lbf_args_of(x, Bp, 0);
+    if (x.ranges > 0)
+        if (int rc = lx3_forward(x, stream)) return rc;
     hipLaunchKernelGGL(k_lbf_combine_partial, dim3(Bp), dim3(640), 0, st, a, part);
     HIP_LAUNCH_CHECK();
     return 0;
@@ -1211,22 +1165,13 @@ int ader_lx3_readout_shard(const float* emb, int item_num, int Bk, int H, int Np
     if (Bk % 128 != 0 || H > HP || (H & 1) || H < 2 || Np > item_num || item_begin < 0 || (item_begin & 3) || ((uintptr_t)emb & 7) ||
         !teacher || !trow || !tlse2) return -2;
     hipStream_t st = (hipStream_t)stream;
-    int n_loc = Np - item_begin;
-    if (n_loc > item_count) n_loc = item_count;
-    if (n_loc < 0) n_loc = 0;
-    int ranges2 = 0;
-    if (n_loc > 0) {
-        int rc = lx3_attr();
-        if (rc) return rc;
-        Lx3Args x;
-        x.emb1 = emb + (size_t)H * (1 + item_begin); x.vrows = item_num - item_begin;
-        x.rep_hi = nullptr; x.rep_lo = nullptr;
-        x.Bp = Bk; x.H = H; x.N = n_loc; x.ranges = 0; x.pm = nullptr; x.pl = nullptr; x.pO = nullptr;
-        x.kd_row0 = 0; x.Np = n_loc; x.teacher = teacher + item_begin; x.ldt = ldt; x.trow = trow; x.tlse2 = tlse2; x.pO2 = pO2;
-        ranges2 = ader_lx3_readout_ranges(n_loc, Bk);
-        x.ranges2 = ranges2;
-        if (lx3r_supports(x)) { rc = lx3r_launch(x, stream); if (rc) return rc; }
-        else hipLaunchKernelGGL((k_lx3_fwd<2, 2, true>), dim3(x.ranges2 * (Bk / 128)), dim3(256), (size_t)2 * 2 * FB * LDR * sizeof(bf16), st, x);
+    const int n_loc = shard_items(Np, item_begin, item_count);
+    const int ranges2 = n_loc > 0 ? ader_lx3_readout_ranges(n_loc, Bk) : 0;
+    if (n_loc > 0) {        // every batch row is a distilled row: no operand planes, no softmax partials
+        Lx3Args x = lx3_args(emb + (size_t)H * (1 + item_begin), item_num - item_begin, nullptr, nullptr, Bk, H, n_loc, 0, nullptr, nullptr,
+                             nullptr);
+        lx3_args_kd(x, 0, n_loc, teacher + item_begin, ldt, trow, tlse2, pO2, ranges2);
+        if (int rc = lx3_readout(x, stream)) return rc;
     }
     hipLaunchKernelGGL(k_lx3_sum_ranges, dim3(Bk), dim3(256), 0, st, (const float*)pO2, ranges2, Bk, H, part2);
     HIP_LAUNCH_CHECK();

@@ -581,7 +581,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
 // logits of its accumulator positions (four 16-byte loads), p = exp2(t log2e - tlse2) is exact (the teacher's log-sum-exp is known),
 // split hi / lo.  HBM-bound (teacher tile + table block per 32 items): both streams run TWO blocks ahead of their use in registers
 // (table: two staging sets, converted into the third LDS buffer at the head of an iteration; teacher: two sets), and the block
-// barrier orders LDS traffic only -- __syncthreads would drain those loads.  Replaces k_lx3_fwd<2, 2, true> (logits_bf16.hip: one
+// barrier orders LDS traffic only -- __syncthreads would drain those loads.  Replaces k_lx3_fwd<true> (logits_bf16.hip: one
 // block of lookahead, per-lane branches around the teacher loads; 0.30 ms against 0.2 at cfg-S + 128 exemplar rows) for H = 150,
 // 16-byte aligned teacher rows.  Output partials pO2 [range][Bk][160] as before.
 __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
@@ -740,13 +740,7 @@ bool lx3r_supports(const Lx3Args& x) {
     return x.H == 150 && x.Np >= F3_FB && (x.ldt & 3) == 0 && (((uintptr_t)x.teacher) & 15) == 0 && (long)(x.vrows + 5 * F3_FB) * x.H * 4 < (1l << 31);      // (block offsets are 32-bit; the stream runs 4 blocks ahead)
 }
 int lx3r_launch(const Lx3Args& x, void* stream) {
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    if (!f) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_lx3r, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * X3B_IMG_B);
-        if (e != hipSuccess) return (int)e;
-        f = true;
-    }
+    if (int e = ader_dyn_lds<k_lx3r>(3 * X3B_IMG_B)) return e;
     hipLaunchKernelGGL(k_lx3r, dim3(x.ranges2 * ((x.Bp - x.kd_row0) / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
     return 0;
 }
@@ -755,26 +749,14 @@ bool lx3f_supports(int H) { return (H & 1) == 0 && H >= 8 && H <= HP && ((H & 7)
 
 // x.ranges must be ader_lbf_ranges(x.N, x.Bp); Bp % 128 == 0
 int lx3g_launch(const Lx3Args& x, void* stream) {
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    if (!f) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_lx3g, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * X3B_IMG_B);
-        if (e != hipSuccess) return (int)e;
-        f = true;
-    }
+    if (int e = ader_dyn_lds<k_lx3g>(3 * X3B_IMG_B)) return e;
     if ((long)x.vrows * x.H * 4 >= (1l << 31)) return -2;          // the block offsets of the buffer loads are 32-bit
     hipLaunchKernelGGL(k_lx3g, dim3(x.ranges * (x.Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
     return 0;
 }
 
 int lx3p_launch(const Lx3Args& x, void* stream) {
-    static bool f_dev[ADER_MAX_DEV] = {};
-    bool& f = f_dev[ader_cur_dev()];
-    if (!f) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_lx3p<150>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * X3B_IMG_B);
-        if (e != hipSuccess) return (int)e;
-        f = true;
-    }
+    if (int e = ader_dyn_lds<k_lx3p<150>>(3 * X3B_IMG_B)) return e;
     if ((long)x.vrows * x.H * 4 >= (1l << 31)) return -2;
     if (x.H != 150) return lx3g_launch(x, stream);                 // (the pipelined form exists for the reference's hidden size only)
     hipLaunchKernelGGL(k_lx3p<150>, dim3(x.ranges * (x.Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);

@@ -353,13 +353,7 @@ int ader_seq_bwd_ffn(const AderSeqBwdFfn* desc, void* stream) {
     const AderSeqBwdFfn& a = *desc;
     const int rc = check_dims(a.B, a.T, a.H);
     if (rc) return rc < 0 ? rc : 0;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_seq_bwd_ffn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeqBwdLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_seq_bwd_ffn>(kSeqBwdLds)) return e;
     hipLaunchKernelGGL(k_seq_bwd_ffn, dim3(a.B), dim3(640), kSeqBwdLds, (hipStream_t)stream, a);
     HIP_LAUNCH_CHECK();
     return 0;
@@ -369,13 +363,7 @@ int ader_seq_bwd_qkv(const AderSeqBwdQkv* desc, void* stream) {
     const AderSeqBwdQkv& a = *desc;
     const int rc = check_dims(a.B, a.T, a.H);
     if (rc) return rc < 0 ? rc : 0;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_seq_bwd_qkv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeqBwdLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_seq_bwd_qkv>(kSeqBwdLds)) return e;
     hipLaunchKernelGGL(k_seq_bwd_qkv, dim3(a.B), dim3(640), kSeqBwdLds, (hipStream_t)stream, a);
     HIP_LAUNCH_CHECK();
     return 0;

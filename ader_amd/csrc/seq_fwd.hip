@@ -514,13 +514,7 @@ int ader_seq_fwd(const AderSeqFwd* desc, void* stream) {
     const AderSeqFwd& a = *desc;
     if (a.B <= 0) return 0;
     if (a.T < 1 || a.T > TR || a.H < 2 || a.H > 150 || (a.H & 1) || a.L < 1 || a.L > ADER_SEQ_MAXL) return -2;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_seq_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeqFwdLds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = ader_dyn_lds<k_seq_fwd>(kSeqFwdLds)) return e;
     hipLaunchKernelGGL(k_seq_fwd, dim3(a.B), dim3(640), kSeqFwdLds, (hipStream_t)stream, a);
     HIP_LAUNCH_CHECK();
     return 0;

@@ -906,14 +906,6 @@ static int check_dims(int B, int T, int H) {
     if (T < 1 || T > TR || H < 2 || H > 150 || (H & 1) || B > 4096) return -2;
     return 0;
 }
-template <class K> static int set_lds(K kernel, size_t bytes, bool& done) {
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return (int)e;
-        done = true;
-    }
-    return 0;
-}
 
 extern "C" {
 
@@ -923,9 +915,7 @@ int ader_seqp_bwd_ffn(const AderSeqBwdFfn* desc, const AderSeqPack* pack, int ma
     if (rc) return rc < 0 ? rc : 0;
     if (!pack) return -2;
     if (max_tiles <= 0 || max_tiles > a.B) max_tiles = a.B;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (int e = set_lds(k_seqp_bwd_ffn, kSeqpBwdLds, attr_set)) return e;
+    if (int e = ader_dyn_lds<k_seqp_bwd_ffn>(kSeqpBwdLds)) return e;
     hipLaunchKernelGGL(k_seqp_bwd_ffn, dim3(max_tiles), dim3(640), kSeqpBwdLds, (hipStream_t)stream, a, *pack);
     HIP_LAUNCH_CHECK();
     return 0;
@@ -937,9 +927,7 @@ int ader_seqp_bwd_qkv(const AderSeqBwdQkv* desc, const AderSeqPack* pack, int ma
     if (rc) return rc < 0 ? rc : 0;
     if (!pack) return -2;
     if (max_tiles <= 0 || max_tiles > a.B) max_tiles = a.B;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (int e = set_lds(k_seqp_bwd_qkv, kSeqpBwdLds, attr_set)) return e;
+    if (int e = ader_dyn_lds<k_seqp_bwd_qkv>(kSeqpBwdLds)) return e;
     hipLaunchKernelGGL(k_seqp_bwd_qkv, dim3(max_tiles), dim3(640), kSeqpBwdLds, (hipStream_t)stream, a, *pack);
     HIP_LAUNCH_CHECK();
     return 0;
@@ -952,9 +940,7 @@ int ader_attnp_bwd(const float* dO, const float* Q, const float* K, const float*
     if (rc) return rc < 0 ? rc : 0;
     if (!pack) return -2;
     if (max_tiles <= 0 || max_tiles > B) max_tiles = B;
-    static bool attr_set_dev[ADER_MAX_DEV] = {};
-    bool& attr_set = attr_set_dev[ader_cur_dev()];
-    if (int e = set_lds(k_attnp_bwd, kAttnpBwdLds, attr_set)) return e;
+    if (int e = ader_dyn_lds<k_attnp_bwd>(kAttnpBwdLds)) return e;
     AttnPkArgs a;
     a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.kmask = kmask; a.qmask = qmask; a.PT = PT; a.dQ = dQ; a.dK = dK; a.dV = dV;
     a.H = H; a.T = T; a.sqrt_dh = sqrtf((float)H);

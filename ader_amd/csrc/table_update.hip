@@ -446,13 +446,7 @@ static size_t tab_lds(int Bp, int H, bool x3, bool adam) {
 
 template <bool X3, bool ADAM, bool EXTRA, bool KD = false>
 static int tab_launch(const TabArgs& a, const FuseArgs& fa, int tiles, size_t lds, hipStream_t st) {
-    static int lds_set_dev[ADER_MAX_DEV] = {};
-    int& lds_set = lds_set_dev[ader_cur_dev()];
-    if ((int)lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_tab_upd<X3, ADAM, EXTRA, KD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        lds_set = (int)lds;
-    }
+    if (int e = ader_dyn_lds<k_tab_upd<X3, ADAM, EXTRA, KD>>(lds)) return e;
     hipLaunchKernelGGL((k_tab_upd<X3, ADAM, EXTRA, KD>), dim3(tiles), dim3(256), lds, st, a, fa);
     return 0;
 }
@@ -480,10 +474,8 @@ int ader_tab_grad(const void* rep_hi, const void* rep_lo, const float* emb, int 
     if (B <= 0) return 0;
     if (Bp % 128 != 0 || B > Bp || H > HP || (H & 1) || H < 2 || N > item_num || ((uintptr_t)emb & 7)) return -2;
     hipStream_t st = (hipStream_t)stream;
-    TabArgs a;
-    a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo; a.off = off;
-    a.Bp = Bp; a.H = H; a.N = N; a.tile_off = 0; a.rep_img = nullptr; a.demb1 = demb + H;
-    a.kd_row0 = Bp; a.Np = 0; a.teacher = nullptr; a.ldt = 0; a.trow = nullptr; a.tlse2 = nullptr;
+    TabArgs a = tab_args(emb + H, item_num, rep_hi, rep_lo, off, Bp, H, N);
+    a.demb1 = demb + H;
     FuseArgs fa = {};
     const int tiles = (N + TI - 1) / TI;
     int rc = rep_lo ? tab_launch<true, false, false>(a, fa, tiles, tab_lds(Bp, H, true, false), st)
@@ -504,10 +496,9 @@ int ader_tab_grad_kd(const void* rep_hi, const void* rep_lo, const float* emb, i
     if (Bp % 128 != 0 || kd_row0 % 128 != 0 || kd_row0 >= Bp || H > HP || (H & 1) || H < 2 || N > item_num || ((uintptr_t)emb & 7) ||
         !teacher || !trow || !tlse2 || Np < 1 || Np > N) return -2;
     hipStream_t st = (hipStream_t)stream;
-    TabArgs a;
-    a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo; a.off = off;
-    a.Bp = Bp; a.H = H; a.N = N; a.tile_off = 0; a.rep_img = nullptr; a.demb1 = demb + H;
-    a.kd_row0 = kd_row0; a.Np = Np; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
+    TabArgs a = tab_args(emb + H, item_num, rep_hi, rep_lo, off, Bp, H, N);
+    tab_args_kd(a, kd_row0, Np, teacher, ldt, trow, tlse2);
+    a.demb1 = demb + H;
     FuseArgs fa = {};
     fa.wrow = wrow;
     const int tiles = (N + TI - 1) / TI;
@@ -538,28 +529,15 @@ int ader_tab_update(const void* rep_hi, void* shadow, int item_num, int B, int B
     const uintptr_t ph = (uintptr_t)emb & 15;
     if ((ph & 7) || ((uintptr_t)adam_m & 15) != ph || ((uintptr_t)adam_v & 15) != ph) return -2;
     if (extra_grad && ((uintptr_t)extra_grad & 15) != ph) return -2;
-    TabArgs a;
-    a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = nullptr; a.off = off;
-    a.Bp = Bp; a.H = H; a.N = N; a.tile_off = 0; a.rep_img = nullptr; a.demb1 = nullptr;
-    a.kd_row0 = Bp; a.Np = 0; a.teacher = nullptr; a.ldt = 0; a.trow = nullptr; a.tlse2 = nullptr;
-    FuseArgs fa;
-    fa.sp_ids = sp_ids; fa.sp_rows = sp_rows; fa.n_sp = n_sp; fa.sp_src = sp_src; fa.sp_scale = sp_scale;
-    fa.tg_ids = tg_ids; fa.tg_rows = tg_rows; fa.n_tg = n_tg; fa.wrow = wrow;
+    TabArgs a = tab_args(emb + H, item_num, rep_hi, nullptr, off, Bp, H, N);
+    FuseArgs fa = fuse_args<FuseArgs>(sp_ids, sp_rows, n_sp, sp_src, sp_scale, tg_ids, tg_rows, n_tg, wrow, emb, adam_m, adam_v, shadow, H,
+                                      lr_t, beta1, beta2, eps, extra_grad);
     fa.tile_meta = tile_meta;
-    fa.emb1 = emb + H; fa.m1 = adam_m + H; fa.v1 = adam_v + H;
-    fa.sh1w = shadow ? (bf16*)shadow + LDR : nullptr;
-    fa.lr_t = lr_t; fa.omb1 = 1.0f - beta1; fa.omb2 = 1.0f - beta2; fa.eps = eps;
-    fa.extra1 = extra_grad ? extra_grad + H : nullptr;
-    // tiles [tile_begin, tile_begin + tile_count) of the ceil(N/128) 128-item tiles (tile_count < 0: all) = two 64-row tiles each
-    const int all = (N + TI - 1) / TI;
-    int tb = (tile_begin < 0 ? 0 : tile_begin) * 2;
-    int te = tile_count < 0 ? all : tb + tile_count * 2;
-    if (te > all) te = all;
-    if (te <= tb) return 0;
-    a.tile_off = tb;
+    int tiles;
+    if (!tab_tile_range(N, tile_begin, tile_count, &a.tile_off, &tiles)) return 0;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = tab_lds(Bp, H, false, true);
-    int rc = extra_grad ? tab_launch<false, true, true>(a, fa, te - tb, lds, st) : tab_launch<false, true, false>(a, fa, te - tb, lds, st);
+    int rc = extra_grad ? tab_launch<false, true, true>(a, fa, tiles, lds, st) : tab_launch<false, true, false>(a, fa, tiles, lds, st);
     if (rc) return rc;
     HIP_LAUNCH_CHECK();
     return 0;

@@ -333,6 +333,26 @@ __global__ __launch_bounds__(256, 3) void k_tab16(ShArgs a, FuseArgs128 f) {
 #undef ADAM1
 }
 
+// host side: the shadow rows as the GEMM operand, the batch and the catalog, no distilled rows (sh_args_kd adds them); the launcher
+// sets tile_off, everything else is zero
+static ShArgs sh_args(const void* shadow, int item_num, const void* rep_bf, int B, int Bp, int H, int N, const float* off) {
+    ShArgs a = {};
+    a.sh1 = (const bf16*)shadow + LDR; a.vrows = item_num; a.rep_bf = (const bf16*)rep_bf; a.B = B; a.Bp = Bp; a.H = H; a.N = N;
+    a.off = off; a.kd_row0 = Bp;
+    return a;
+}
+static void sh_args_kd(ShArgs& a, int kd_row0, int Np, const float* teacher, long ldt, const int* trow, const float* tlse2) {
+    a.kd_row0 = kd_row0; a.Np = Np; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
+}
+
+template <bool EXTRA, bool KD>
+static int tab16_launch(const ShArgs& a, const FuseArgs128& fa, int tiles, size_t lds, void* stream) {
+    if (int e = ader_dyn_lds<k_tab16<EXTRA, KD>>(lds)) return e;
+    hipLaunchKernelGGL((k_tab16<EXTRA, KD>), dim3(tiles), dim3(256), lds, (hipStream_t)stream, a, fa);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+
 static size_t bwd_lds(int Bp, int Bk) { return (size_t)2 * 64 * LDR * sizeof(bf16) + (size_t)Bp * sizeof(float) + 2 * 18 * sizeof(int) + (size_t)Bk * 8; }
 
 extern "C" {
@@ -349,47 +369,17 @@ static int tab_update_sh(const void* rep_bf, void* shadow, int item_num, int B, 
     if (Bp % 128 != 0 || B > Bp || H > HP || (H & 1) || H < 2 || N > item_num || !shadow) return -2;
     const bool kd = kd_row0 < Bp;
     if (kd && (kd_row0 % 128 != 0 || extra_grad || !teacher || !trow || !tlse2 || Np < 1 || Np > N)) return -2;
-    static int lds_set_dev[ADER_MAX_DEV] = {};
-    int& lds_set = lds_set_dev[ader_cur_dev()];
     const size_t lds = bwd_lds(Bp, kd ? Bp - kd_row0 : 0);
-    if ((int)lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_tab16<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        e = hipFuncSetAttribute((const void*)k_tab16<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        e = hipFuncSetAttribute((const void*)k_tab16<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        lds_set = (int)lds;
-    }
-    ShArgs a;
-    a.sh1 = (const bf16*)shadow + LDR; a.vrows = item_num; a.tile_off = 0;
-    a.rep_bf = (const bf16*)rep_bf; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ranges = 0;
-    a.pm = a.pl = a.pO = nullptr; a.off = off; a.demb1 = nullptr;
-    a.kd_row0 = kd ? kd_row0 : Bp; a.Np = Np; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
-    FuseArgs128 fa;
-    fa.sp_ids = sp_ids; fa.sp_rows = sp_rows; fa.n_sp = n_sp; fa.sp_src = sp_src; fa.sp_scale = sp_scale;
-    fa.tg_ids = tg_ids; fa.tg_rows = tg_rows; fa.n_tg = n_tg; fa.wrow = wrow;
+    ShArgs a = sh_args(shadow, item_num, rep_bf, B, Bp, H, N, off);
+    if (kd) sh_args_kd(a, kd_row0, Np, teacher, ldt, trow, tlse2);
+    FuseArgs128 fa = fuse_args<FuseArgs128>(sp_ids, sp_rows, n_sp, sp_src, sp_scale, tg_ids, tg_rows, n_tg, wrow, emb, adam_m, adam_v, shadow,
+                                            H, lr_t, beta1, beta2, eps, extra_grad);
     fa.sp_start = sp_start; fa.tg_start = tg_start;
-    fa.emb1 = emb + H; fa.m1 = adam_m + H; fa.v1 = adam_v + H; fa.sh1w = (bf16*)shadow + LDR;
-    fa.lr_t = lr_t; fa.omb1 = 1.0f - beta1; fa.omb2 = 1.0f - beta2; fa.eps = eps;
-    fa.extra1 = extra_grad ? extra_grad + H : nullptr;
-    const int all = (N + 127) / 128;
-    int tb = tile_begin < 0 ? 0 : tile_begin;
-    int te = tile_count < 0 ? all : tb + tile_count;
-    if (te > all) te = all;
-    if (te <= tb) return 0;
-    a.tile_off = tb;
-    hipStream_t st = (hipStream_t)stream;
-    // 64-row tiles: the tile range (given in 128-row units) in units of 64 rows
-    const int all64 = (N + 63) / 64;
-    int t0 = 2 * tb, t1 = 2 * te;
-    if (t1 > all64) t1 = all64;
-    a.tile_off = t0;
-    if (kd) hipLaunchKernelGGL((k_tab16<false, true>), dim3(t1 - t0), dim3(256), lds, st, a, fa);
-    else if (extra_grad) hipLaunchKernelGGL((k_tab16<true, false>), dim3(t1 - t0), dim3(256), lds, st, a, fa);
-    else hipLaunchKernelGGL((k_tab16<false, false>), dim3(t1 - t0), dim3(256), lds, st, a, fa);
-    HIP_LAUNCH_CHECK();
-    return 0;
+    int tiles;
+    if (!tab_tile_range(N, tile_begin, tile_count, &a.tile_off, &tiles)) return 0;
+    if (kd) return tab16_launch<false, true>(a, fa, tiles, lds, stream);
+    if (extra_grad) return tab16_launch<true, false>(a, fa, tiles, lds, stream);
+    return tab16_launch<false, false>(a, fa, tiles, lds, stream);
 }
 
 int ader_tab_update_sh(const void* rep_bf, void* shadow, int item_num, int B, int Bp, int H, int N, const float* off,

@@ -436,13 +436,7 @@ static size_t tab32x3_lds(int Bp, int Bk) {
 
 template <bool EXTRA, bool KD>
 static int tab32x3_launch_t(const TabArgs& a, const FuseArgs& fa, int tiles, size_t lds, hipStream_t st) {
-    static int lds_set_dev[ADER_MAX_DEV] = {};
-    int& lds_set = lds_set_dev[ader_cur_dev()];
-    if ((int)lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_tab32x3<EXTRA, KD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        lds_set = (int)lds;
-    }
+    if (int e = ader_dyn_lds<k_tab32x3<EXTRA, KD>>(lds)) return e;
     hipLaunchKernelGGL((k_tab32x3<EXTRA, KD>), dim3((tiles + 1) / 2), dim3(256), lds, st, a, fa);
     return 0;
 }
@@ -472,25 +466,15 @@ static int tab_update_x3(const void* rep_hi, const void* rep_lo, const void* rep
     const uintptr_t ph = (uintptr_t)emb & 15;
     if ((ph & 7) || ((uintptr_t)adam_m & 15) != ph || ((uintptr_t)adam_v & 15) != ph) return -2;
     if (extra_grad && ((uintptr_t)extra_grad & 15) != ph) return -2;
-    TabArgs a;
-    a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo; a.rep_img = rep_img;
-    a.off = off; a.Bp = Bp; a.H = H; a.N = N; a.tile_off = 0; a.demb1 = nullptr;
-    a.kd_row0 = kd ? kd_row0 : Bp; a.Np = kd ? Np : 0; a.teacher = teacher; a.ldt = ldt; a.trow = trow; a.tlse2 = tlse2;
-    FuseArgs fa;
-    fa.sp_ids = sp_ids; fa.sp_rows = sp_rows; fa.n_sp = n_sp; fa.sp_src = sp_src; fa.sp_scale = sp_scale;
-    fa.tg_ids = tg_ids; fa.tg_rows = tg_rows; fa.n_tg = n_tg; fa.wrow = wrow;
+    TabArgs a = tab_args(emb + H, item_num, rep_hi, rep_lo, off, Bp, H, N);
+    if (kd) tab_args_kd(a, kd_row0, Np, teacher, ldt, trow, tlse2);
+    a.rep_img = rep_img;
+    FuseArgs fa = fuse_args<FuseArgs>(sp_ids, sp_rows, n_sp, sp_src, sp_scale, tg_ids, tg_rows, n_tg, wrow, emb, adam_m, adam_v, nullptr, H,
+                                      lr_t, beta1, beta2, eps, extra_grad);
     fa.tile_meta = tile_meta;
-    fa.emb1 = emb + H; fa.m1 = adam_m + H; fa.v1 = adam_v + H; fa.sh1w = nullptr;
-    fa.lr_t = lr_t; fa.omb1 = 1.0f - beta1; fa.omb2 = 1.0f - beta2; fa.eps = eps;
-    fa.extra1 = extra_grad ? extra_grad + H : nullptr;
-    // tiles [tile_begin, tile_begin + tile_count) of the ceil(N/128) 128-item tiles (tile_count < 0: all) = two 64-row tiles each
-    const int all = (N + TI - 1) / TI;
-    int tb = (tile_begin < 0 ? 0 : tile_begin) * 2;
-    int te = tile_count < 0 ? all : tb + tile_count * 2;
-    if (te > all) te = all;
-    if (te <= tb) return 0;
-    a.tile_off = tb;
-    int rc = tab32x3_launch(a, fa, te - tb, extra_grad != nullptr, kd, stream);
+    int tiles;
+    if (!tab_tile_range(N, tile_begin, tile_count, &a.tile_off, &tiles)) return 0;
+    int rc = tab32x3_launch(a, fa, tiles, extra_grad != nullptr, kd, stream);
     if (rc) return rc;
     HIP_LAUNCH_CHECK();
     return 0;
