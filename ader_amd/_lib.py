@@ -96,6 +96,8 @@ _SIGS = {
     "ader_embed_bwd_rows": [P, P, P, I, I, I, I] + _DROP + [P],
     "ader_logits_store": [P, P, I, I, I, I, P, P, L, P],
     "ader_rank_targets": [P, P, I, I, I, I, P, P, P, P, P],
+    "ader_rank_emax": [P, I, I, I, P, P],
+    "ader_rank_targets_x3": [P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, I, P, P, P],
     "ader_adam_step": [P, P, P, P, Z, F, F, F, F, P, Z, I, P],
     "ader_fill": [P, Z, F, P],
     "ader_reduce_slabs": [P, L, I, I, I, I, P, P, P],

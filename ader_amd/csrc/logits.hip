@@ -396,6 +396,49 @@ __global__ __launch_bounds__(256) void k_target_logit(LogitArgs a, float* __rest
         if (q * 4 + r == col) { const int b = bc * TB + wave * 16 + col; tl[b] = acc[0][r]; }
 }
 
+// The recheck of the x3 rank filter (k_lx3k, logits_x3.hip): k_target_logit generalised from "row b with its own target" to a list of
+// (row, item, x3 logit) pairs.  A wave takes 16 pairs, their 16 table rows and 16 rep rows in the [64][LDE] layout, runs the same
+// mma_tile<1> k-order and reads the diagonal: the very bits k_logits_tile<MODE_RANK> computes for that pair, so its comparison gives
+// the same answer.  diag[0] = entries the filter asked for (min(diag[0], cap) are in the list); diag[1] <- max |s_x3 - s| / delta as
+// float bits (non-negative: an integer max orders them) -- the observed error of the filter as a share of its band.
+__global__ __launch_bounds__(256) void k_pair_logit_rank(LogitArgs a, const float* __restrict__ delta, const int* __restrict__ cand,
+                                                         int cap, int* __restrict__ diag) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* E_l = smem;
+    float* R_l = E_l + TI * LDE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H = a.H, ksteps = (H + 3) >> 2;
+    const int count = min(diag[0], cap);
+    const int p0 = blockIdx.x * 64;
+    if (p0 >= count) return;                                  // (the grid is sized for cap)
+    for (int i = tid; i < 64 * LDE; i += 256) {
+        const int r = i / LDE, c = i - r * LDE;
+        int b = -1, it = -1;
+        if (p0 + r < count) { b = cand[3 * (size_t)(p0 + r)]; it = cand[3 * (size_t)(p0 + r) + 1]; }
+        const bool ok = b >= 0 && b < a.B && it >= 0 && it < a.N && c < H;
+        E_l[i] = ok ? a.emb1[(size_t)it * H + c] : 0.0f;
+        R_l[i] = ok ? a.rep[(size_t)b * H + c] : 0.0f;
+    }
+    __syncthreads();
+    f32x4 acc[1];
+    acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    mma_tile<1>(E_l + wave * 16 * LDE, LDE, 1, R_l + wave * 16 * LDE, 1, LDE, ksteps, acc, lane);
+    const int col = lane & 15, q = lane >> 4;
+    const int p = p0 + wave * 16 + col;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (q * 4 + r == col && p < count) {
+            const int b = cand[3 * (size_t)p], it = cand[3 * (size_t)p + 1];
+            if (b < 0 || b >= a.B || it < 0 || it >= a.N) continue;
+            const float s = acc[0][r], s3 = __int_as_float(cand[3 * (size_t)p + 2]);
+            const float tl = a.tlogit[b], d = delta[b];
+            const int tgt = a.ri.lab[b] - 1;
+            if ((s > tl) || (s == tl && it < tgt)) atomicAdd(a.rank + b, 1);
+            const float err = d > 0.0f ? fabsf(s3 - s) / d : 0.0f;
+            if (err > 0.0f) atomicMax(diag + 1, __float_as_int(err));
+        }
+}
+
 // ============================================================================================= C ABI
 static const size_t kTileLds = (size_t)(2 * 64 * LDE + 4 * TB * 3 + MAXB * 3) * sizeof(float);
 static const size_t kBwdLds = (size_t)(2 * 64 * LDE + 64 * LDD) * sizeof(float);
@@ -408,6 +451,32 @@ static int fill_args(LogitArgs& a, const float* rep, const float* emb, int B, in
     a.ri.lab = lab; a.ri.ncol = ncol; a.ri.wrow = wrow; a.ri.trow = trow; a.ri.tlse = tlse; a.ri.teacher = teacher; a.ri.ldt = ldt;
     a.part = nullptr; a.sub = 1; a.tlogit = nullptr; a.rank = nullptr; a.out = nullptr; a.ldo = 0; a.lse = nullptr;
     a.demb1 = nullptr; a.slab = nullptr; a.ranges = 0;
+    return 0;
+}
+
+// the two exact-f32 pieces of ader_rank_targets_x3 (logits_x3.hip): target logits, and the recheck of the filter's list
+int rank_target_logit_launch(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
+                             float* tlogit, void* stream) {
+    LogitArgs a;
+    int rc = fill_args(a, rep, emb, B, Bp, H, N, target, ncol, nullptr, nullptr, nullptr, nullptr, 0);
+    if (rc) return rc;
+    rc = ader_dyn_lds<k_target_logit>(kTgtLds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_target_logit, dim3(Bp / TB), dim3(256), kTgtLds, (hipStream_t)stream, a, tlogit);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+int rank_pairs_launch(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
+                      const float* tlogit, const float* delta, const int* cand, int cap, int* diag, int* rank, void* stream) {
+    if (cap <= 0) return 0;
+    LogitArgs a;
+    int rc = fill_args(a, rep, emb, B, Bp, H, N, target, ncol, nullptr, nullptr, nullptr, nullptr, 0);
+    if (rc) return rc;
+    rc = ader_dyn_lds<k_pair_logit_rank>(kTgtLds);
+    if (rc) return rc;
+    a.tlogit = tlogit; a.rank = rank;
+    hipLaunchKernelGGL(k_pair_logit_rank, dim3((cap + 63) / 64), dim3(256), kTgtLds, (hipStream_t)stream, a, delta, cand, cap, diag);
+    HIP_LAUNCH_CHECK();
     return 0;
 }
 

@@ -3,9 +3,28 @@ import numpy as np
 import torch
 
 from .._lib import call, ptr
+from .common import _check
+
+# Half-width of the undecided band of the x3 rank filter, as a share of |rep_b| * max_n |E_n|: the SAME value as KAPPA of k_lx3k
+# (csrc/logits_x3.hip, where the bound is derived).  |s_x3 - s_f32| stays below half of it; tests/test_rank_x3_host.py emulates that.
+RANK_X3_KAPPA = 2.0 ** -13
+RANK_X3_CAND_PER_ROW = 64      # default candidate-list entries per padded row of a chunk (Engine.rank_targets cand_cap)
+RANK_DTYPES = ("f32", "x3")
+
+
+def _check_rank_dtype(v):
+    _check(v in RANK_DTYPES, "rank_dtype must be 'f32' or 'x3' (got %r)" % (v,))
+    return v
+
+
+def rank_x3_supports(H):
+    """Hidden sizes of k_lx3k (lx3f_supports of csrc/logits_x3.hip)."""
+    return H % 2 == 0 and 8 <= H <= 160 and H % 8 in (0, 4, 6)
 
 
 class _Infer:
+    last_rank_stats = None     # Engine.rank_targets(dtype="x3"): candidates, pairs, overflowed_chunks, max_err_over_delta of the last call
+
     # ---------------------------------------------------------------------------------------- inference paths
     def encode(self, seq):
         """Eval-mode representation (is_training=False): rep [n,H] for any n (chunks of MAX_ROWS)."""
@@ -50,8 +69,14 @@ class _Infer:
         self._refresh_stream()
         return self.logits(seq, max_item)
 
-    def rank_targets(self, seq, pos, max_item):
-        """0-based rank of pos[b] among items 1..N for every row (Evaluator path, util.py:323-325) -> int32 numpy [n]."""
+    def rank_targets(self, seq, pos, max_item, dtype=None, cand_cap=None):
+        """0-based rank of pos[b] among items 1..N for every row (Evaluator path, util.py:323-325) -> int32 numpy [n].
+        dtype: "f32" (the exact-f32 MFMA kernel) or "x3" (bf16 matrix cores as a filter + exact recheck of the undecided pairs: the same
+        ranks, ties included); None: the engine's rank_dtype.  cand_cap: candidate-list entries per chunk of the "x3" path (None: 64 per
+        padded row)."""
+        dtype = _check_rank_dtype(self.rank_dtype if dtype is None else dtype)
+        if dtype == "x3" and rank_x3_supports(self.H):       # (other hidden sizes: the exact kernel, as the flash forward does)
+            return self._rank_targets_x3(seq, pos, max_item, cand_cap)
         self._refresh_stream()
         self.sync_table()
         seq = self._seq_in(seq)
@@ -72,6 +97,57 @@ class _Infer:
                  ptr(tl), ptr(rk), self._stream())
             out[s:e] = rk[:B]
         return out.cpu().numpy()
+
+    def _rank_targets_x3(self, seq, pos, max_item, cand_cap):
+        """rank_targets on the bf16 matrix cores (ader_rank_targets_x3): per 128-row-padded chunk the x3 filter decides every (row, item)
+        whose x3 logit is outside the band tl +- delta, the exact-f32 recheck decides the listed rest; a chunk whose list overflowed is
+        ranked again by the exact kernel.  One device -> host copy: ranks + per-chunk (count, max err / delta)."""
+        self._refresh_stream()
+        self.sync_table()
+        seq = self._seq_in(seq)
+        pos = self._dev_i32(pos)
+        n, N = seq.shape[0], int(max_item)
+        st = self._stream()
+        chunks = [(s, min(n, s + self.MAX_ROWS)) for s in range(0, n, self.MAX_ROWS)]
+        res = torch.zeros(n + 2 * len(chunks), dtype=torch.int32, device=self.device)
+        emax = self.buf("rkx_emax", (1,))
+        if chunks:
+            call("ader_rank_emax", self._pp["emb"], self.item_num, self.H, N, ptr(emax), st)      # once per call, not per chunk
+        caps = []
+        for c, (s, e) in enumerate(chunks):
+            B = e - s
+            Bp = (B + 127) // 128 * 128
+            cap = int(cand_cap) if cand_cap is not None else RANK_X3_CAND_PER_ROW * Bp
+            caps.append(cap)
+            rep = self.forward(seq[s:e], training=False)
+            rep_hi, rep_lo = self.buf("rkx_hi", (Bp * 168,), torch.bfloat16), self.buf("rkx_lo", (Bp * 168,), torch.bfloat16)
+            tl, delta = self.buf("rkx_tl", (Bp,)), self.buf("rkx_delta", (Bp,))
+            rk = self.buf("rkx_rank", (Bp,), torch.int32)
+            tgt = self.buf("rkx_tgt", (Bp,), torch.int32)
+            cand = self.buf("rkx_cand", (3 * max(cap, 1),), torch.int32)      # (one list: the chunks' launches are ordered on the stream)
+            tgt.zero_()
+            tgt[:B] = pos[s:e]
+            call("ader_rank_targets_x3", ptr(rep), self._pp["emb"], self.item_num, B, Bp, self.H, N, ptr(tgt),
+                 ptr(self._ncol_all(Bp, B, N)), ptr(rep_hi), ptr(rep_lo), ptr(tl), ptr(delta), ptr(emax), ptr(cand), cap,
+                 ptr(res[n + 2 * c:]), ptr(rk), st)
+            res[s:e] = rk[:B]
+        host = res.cpu().numpy()
+        ranks, diag = host[:n].copy(), host[n:].reshape(-1, 2)
+        over = [c for c in range(len(chunks)) if diag[c, 0] > caps[c]]
+        # the list overflowed: some undecided pairs were dropped.  The exact kernel ranks the chunk again, on the SAME session forward
+        # as this call's: the density of a host batch (which decides "auto" packing, and the packed kernels round differently) is kept
+        # for the device slices the inner call sees
+        kd, self._step.keep_density = self._step.keep_density, True
+        try:
+            for c in over:
+                s, e = chunks[c]
+                ranks[s:e] = self.rank_targets(seq[s:e], pos[s:e], N, dtype="f32")
+        finally:
+            self._step.keep_density = kd
+        self.last_rank_stats = {
+            "candidates": int(diag[:, 0].sum()), "pairs": int(n) * N, "overflowed_chunks": len(over),
+            "max_err_over_delta": float(diag[:, 1].copy().view(np.float32).max()) if len(chunks) else 0.0}
+        return ranks
 
     def row_losses(self, seq, pos, max_item):
         """Per-row cross entropy -log softmax(logits)[label] in eval mode (the quantity the reference's `loss` exemplar selector

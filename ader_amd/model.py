@@ -31,7 +31,7 @@ class Ader:
         ld = logits_dtype or getattr(args, "logits_dtype", "x3")
         self.engine = Engine(item_num, maxlen=args.maxlen, hidden_units=args.hidden_units, num_blocks=args.num_blocks,
                              num_heads=args.num_heads, seed=args.random_seed, device=device, logits_dtype=ld,
-                             dp_rank=dp_rank, dp_world=dp_world)
+                             dp_rank=dp_rank, dp_world=dp_world, rank_dtype=getattr(args, "rank_dtype", "f32"))
         # session kernels on the real positions only (packed tiles): "auto" goes by the density of the batches (engine.py)
         self.engine.pack_sessions = {"auto": "auto", "on": True, "off": False}[getattr(args, "pack_sessions", "auto")]
         for n in ("is_training", "input_seq", "pos", "exemplar_logits", "exemplar_pos", "max_item", "lr", "dropout_rate",

@@ -11,6 +11,8 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
   ader::logits_ce_fwd(rep, shadow, labels, weights, N)         -> (loss, lse, drep, off)   ADER.py:88-93 (bf16 flash forward)
   ader::adam_step(p, m, v, g, lr_t, beta1, beta2, eps)         -> ()     in place, ADER.py:96 (TF ApplyAdam)
   ader::rank_of_target(rep, emb, target, N)                    -> rank   ADER.py:99-103 + util.py:325
+  ader::rank_of_target_x3(rep, emb, target, N)                 -> rank   the same ranks; products on the bf16 matrix cores (x3 filter
+                                                                         + exact-f32 recheck of the undecided pairs)
   ader::herding_select(rep, seg, quota, max_steps)             -> (sel, cnt)   util.py:401-434
 
 Trainable surface (second half of this file; every forward has an autograd formula over its `_bwd` operator):
@@ -143,6 +145,39 @@ def rank_of_target(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, N
 
 
 @rank_of_target.register_fake
+def _(rep, emb, target, N):
+    return target.new_empty(rep.shape[0])
+
+
+@torch.library.custom_op("ader::rank_of_target_x3", mutates_args=())
+def rank_of_target_x3(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, N: int) -> torch.Tensor:
+    """rank_of_target's contract and result (ties included) through ader_rank_targets_x3.  Reads the candidate count back (one
+    synchronisation): if the list overflowed, the rows are ranked by the exact kernel instead."""
+    from .engine.infer import RANK_X3_CAND_PER_ROW, rank_x3_supports
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(target, "target", torch.int32, 1)
+    B, H = rep.shape
+    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or target.shape[0] != B or B > 1024:
+        raise RuntimeError("ader::rank_of_target_x3: bad shapes")
+    if not rank_x3_supports(H):
+        raise RuntimeError("ader::rank_of_target_x3: H must be even, 8 <= H <= 160, H mod 8 in {0, 4, 6} (got %d)" % H)
+    Bp = (B + 127) // 128 * 128
+    dev = rep.device
+    tgt, ncol = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, dtype=torch.int32, device=dev)
+    tgt[:B], ncol[:B] = target, N
+    tl, delta, emax = torch.empty(Bp, device=dev), torch.empty(Bp, device=dev), torch.empty(1, device=dev)
+    rep_hi, rep_lo = (torch.empty(Bp * 168, dtype=torch.bfloat16, device=dev) for _ in range(2))
+    cap = RANK_X3_CAND_PER_ROW * Bp
+    cand, diag = torch.empty(3 * cap, dtype=torch.int32, device=dev), torch.empty(2, dtype=torch.int32, device=dev)
+    rk = torch.empty(Bp, dtype=torch.int32, device=dev)
+    call("ader_rank_emax", ptr(emb), emb.shape[0] - 1, H, N, ptr(emax), _st())
+    call("ader_rank_targets_x3", ptr(rep), ptr(emb), emb.shape[0] - 1, B, Bp, H, N, ptr(tgt), ptr(ncol), ptr(rep_hi), ptr(rep_lo),
+         ptr(tl), ptr(delta), ptr(emax), ptr(cand), cap, ptr(diag), ptr(rk), _st())
+    if int(diag[0].item()) > cap:
+        return rank_of_target(rep, emb, target, N)
+    return rk[:B].clone()
+
+
+@rank_of_target_x3.register_fake
 def _(rep, emb, target, N):
     return target.new_empty(rep.shape[0])
 

@@ -238,6 +238,17 @@ int ader_logits_store(const float* rep, const float* emb, int B, int Bp, int H, 
  * + the host gather pred[label-1] (util.py:325). */
 int ader_rank_targets(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
                       float* tlogit, int* rank, void* stream);
+/* The same ranks (ADER.py:99-103 + util.py:323-325), ties included, with the [B,N] products on the bf16 matrix cores: the x3 kernel
+ * (k_lx3k) decides every (row, item) whose x3 logit lies outside tl[b] +- delta[b], delta[b] = 2^-13 |rep_b| emax[0], and lists the rest
+ * as (row, item, x3 logit) in cand; the listed pairs are re-evaluated through the exact-f32 MFMA chain.  emax: ader_rank_emax's output
+ * (max table-row 2-norm over items 1..N: once per ranking call, after the table is final).  diag[0] = entries the filter asked for: the
+ * ranks are valid iff diag[0] <= cap, else the list overflowed and the caller ranks these rows with ader_rank_targets; diag[1] = float
+ * bits of max |s_x3 - s_f32| / delta over the listed pairs.  Bp % 128 == 0, Bp <= 1024; H even, 8 <= H <= 160, H mod 8 in {0, 4, 6}
+ * (else -2).  Scratch: rep_hi, rep_lo Bp*168 bf16; tlogit, delta Bp floats; cand 3*cap ints.  rank [Bp] and diag [2] are zeroed here. */
+int ader_rank_emax(const float* emb, int item_num, int H, int N, float* emax, void* stream);
+int ader_rank_targets_x3(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* target,
+                         const int* ncol, void* rep_hi, void* rep_lo, float* tlogit, float* delta, const float* emax, int* cand, int cap,
+                         int* diag, int* rank, void* stream);
 
 /* ---- bf16-MFMA variant of the one-hot softmax CE (fp32 master table, fp32 accumulate/softmax): ADER.py:88-93 ------ */
 /* Bp % 128 == 0, H even.  Scratch: rep_bf Bp*168 bf16; pm, pl: R*Bp floats; pO: R*Bp*160 floats, R = ader_lbf_ranges(N,Bp).

@@ -1,0 +1,206 @@
+#!/usr/bin/env python3
+"""Evaluation ranking, "x3" against the exact-f32 kernel (Engine.rank_targets dtype= / --rank_dtype): times, candidate shares, the bound.
+
+    python tools/bench_eval.py [--check] [--reps 5] [--warmup 2] [--train_steps 200] [--out profiles/eval_x3.txt]
+
+Shapes: (a) the last test period of data/YOOCHOOSE.npz and data/DIGINETICA.npz -- the rows the product's DataLoader / Evaluator hand to
+model.rank_targets; (b) 4,096 synthetic rows at N = 10^6.  Per shape and dtype, device events around (1) the whole rank_targets call
+(session forward, rank launches, the copy back) and (2) the rank launches alone on precomputed representations; the two dtypes alternate
+inside every repetition, medians over the repetitions after a warm-up.  The rank launches are set against 2 B N H over the peak of the
+matrix arithmetic they use: 157.3 TFLOP/s (v_mfma_f32_16x16x4_f32) for "f32", three bf16 MFMAs per product at 2.5 PFLOP/s for "x3".
+--check also asserts ranks(x3) == ranks(f32) on every test period of both datasets.  The model is an Engine at its initial weights after
+--train_steps steps on the first period: enough for the table norms and target logits to leave the init symmetry, not a trained model."""
+import argparse
+import os
+import random
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from ader_amd._lib import call, ptr  # noqa: E402
+from ader_amd.data import DataLoader, Evaluator, Sampler  # noqa: E402
+from ader_amd.engine import Engine  # noqa: E402
+from ader_amd.main import ITEM_NUM  # noqa: E402
+
+PEAK_F32_MFMA, PEAK_BF16_MFMA = 157.3e12, 2.5e15
+T, H = 50, 150
+_out = []
+
+
+def say(*a):
+    line = " ".join(str(x) for x in a)
+    print(line, flush=True)
+    if _out:
+        _out[0].write(line + "\n")
+        _out[0].flush()
+
+
+class _Capture:
+    """Stands where the model does in an Evaluator: keeps the rows the Evaluator would rank."""
+
+    def rank_targets(self, seq, pos, max_item):
+        self.seq, self.pos = np.ascontiguousarray(seq, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
+        return np.zeros(len(pos), dtype=np.int32)
+
+
+def evaluator_rows(sessions, max_item, batch):
+    cap = _Capture()
+    ev = Evaluator(sessions, False, T, batch, max_item, "test", cap, None)
+    ev.evaluate(0)
+    return cap.seq, cap.pos
+
+
+def ev_time(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    r = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e-3, r
+
+
+def rank_launches(eng, rep, pos, N, dtype, emax=None):
+    """The rank launches of Engine.rank_targets alone, on precomputed representations (no forward, no copy back)."""
+    st = torch.cuda.current_stream().cuda_stream
+    n = rep.shape[0]
+    if dtype == "x3":
+        call("ader_rank_emax", eng._pp["emb"], eng.item_num, eng.H, N, ptr(emax), st)
+    for s in range(0, n, eng.MAX_ROWS):
+        e = min(n, s + eng.MAX_ROWS)
+        B = e - s
+        Bp = (B + 127) // 128 * 128 if dtype == "x3" else (B + 63) // 64 * 64
+        tgt = eng.buf("be_tgt", (Bp,), torch.int32)
+        tgt.zero_()
+        tgt[:B] = pos[s:e]
+        ncol, tl, rk = eng._ncol_all(Bp, B, N), eng.buf("be_tl", (Bp,)), eng.buf("be_rk", (Bp,), torch.int32)
+        if dtype == "x3":
+            cap = 64 * Bp
+            hi, lo = eng.buf("be_hi", (Bp * 168,), torch.bfloat16), eng.buf("be_lo", (Bp * 168,), torch.bfloat16)
+            call("ader_rank_targets_x3", ptr(rep[s:e]), eng._pp["emb"], eng.item_num, B, Bp, eng.H, N, ptr(tgt), ptr(ncol), ptr(hi), ptr(lo),
+                 ptr(tl), ptr(eng.buf("be_delta", (Bp,))), ptr(emax), ptr(eng.buf("be_cand", (3 * cap,), torch.int32)), cap,
+                 ptr(eng.buf("be_diag", (2,), torch.int32)), ptr(rk), st)
+        else:
+            call("ader_rank_targets", ptr(rep[s:e]), eng._pp["emb"], B, Bp, eng.H, N, ptr(tgt), ptr(ncol), ptr(tl), ptr(rk), st)
+
+
+def measure(name, eng, seq, pos, N, reps, warmup):
+    n = len(pos)
+    seq_d = torch.from_numpy(seq).to(eng.device)
+    pos_d = torch.from_numpy(pos).to(eng.device)
+    rep = eng.encode(seq_d)
+    emax = torch.zeros(1, device=eng.device)
+    whole, launches, fwd, ranks, stats = {"f32": [], "x3": []}, {"f32": [], "x3": []}, [], {}, None
+    for it in range(warmup + reps):
+        for dt in ("f32", "x3"):                                   # alternating inside every repetition
+            t, r = ev_time(lambda: eng.rank_targets(seq_d, pos_d, N, dtype=dt))
+            tl, _ = ev_time(lambda: rank_launches(eng, rep, pos_d, N, dt, emax))
+            if it >= warmup:
+                whole[dt].append(t)
+                launches[dt].append(tl)
+            ranks[dt] = r
+            if dt == "x3":
+                stats = dict(eng.last_rank_stats)
+        tf, _ = ev_time(lambda: eng.encode(seq_d))
+        if it >= warmup:
+            fwd.append(tf)
+    equal = bool(np.array_equal(ranks["f32"], ranks["x3"]))
+    flop = 2.0 * n * N * eng.H
+    med = statistics.median
+    say("== %s: %d rows, N = %d, H = %d; %d repetitions after %d warm-up, medians [min .. max]" % (name, n, N, eng.H, reps, warmup))
+    for dt, ideal in (("f32", flop / PEAK_F32_MFMA), ("x3", 3.0 * flop / PEAK_BF16_MFMA)):
+        w, l = whole[dt], launches[dt]
+        say("  %-3s  rank_targets %9.2f ms [%.2f .. %.2f]  %9.0f rows/s | rank launches %9.2f ms [%.2f .. %.2f] = %5.1f x the %.3f ms of "
+            "2BNH%s over the MFMA peak" % (dt, med(w) * 1e3, min(w) * 1e3, max(w) * 1e3, n / med(w), med(l) * 1e3, min(l) * 1e3, max(l) * 1e3,
+                                          med(l) / ideal, ideal * 1e3, " x 3" if dt == "x3" else ""))
+    say("  session forward (encode) %.2f ms = %.0f %% of the f32 call, %.0f %% of the x3 call" %
+        (med(fwd) * 1e3, 100 * med(fwd) / med(whole["f32"]), 100 * med(fwd) / med(whole["x3"])))
+    say("  x3 / f32: whole call %.3f, rank launches %.3f  (< 1: x3 is faster)" %
+        (med(whole["x3"]) / med(whole["f32"]), med(launches["x3"]) / med(launches["f32"])))
+    say("  last_rank_stats %r; candidate share %.3e; %.1f candidates per row (default cap 64 per padded row); ranks equal: %s" %
+        (stats, stats["candidates"] / max(stats["pairs"], 1), stats["candidates"] / max(n, 1), equal))
+    return equal
+
+
+def dataset(name, args):
+    """Measures the last test period; returns (ok, check) where check() compares the two dtypes on every earlier test period."""
+    dl = DataLoader(name)
+    periods = dl.num_periods() - 1
+    eng = Engine(ITEM_NUM[name], maxlen=T, hidden_units=H, num_blocks=2, num_heads=1, seed=0)
+    random.seed(0)
+    np.random.seed(0)
+    rows = []
+    for period in range(1, periods + 1):
+        train_sess, _ = dl.train_loader(period - 1)
+        test_sess, _ = dl.evaluate_loader(period)
+        N = dl.max_item()
+        if period == 1 and args.train_steps:
+            smp = Sampler(train_sess, T, 256)
+            for _ in range(min(args.train_steps, smp.batch_num())):
+                seq, pos = smp.next_batch()
+                if len(pos) == 256:
+                    eng.train_step(seq, pos, N, 5e-4, rate=0.3)
+            torch.cuda.synchronize()
+        if period == periods or args.check:
+            rows.append((period, N) + evaluator_rows(test_sess, N, args.eval_batch))
+    period, N, seq, pos = rows.pop()
+    ok = measure("%s, test period %d" % (name, period), eng, seq, pos, N, args.reps, args.warmup)
+
+    def check():
+        good = True
+        for period, N, seq, pos in rows:
+            a = eng.rank_targets(seq, pos, N, dtype="f32")
+            b = eng.rank_targets(seq, pos, N, dtype="x3")
+            eq = bool(np.array_equal(a, b))
+            say("  check %s period %2d: %6d rows, N = %5d, ranks equal: %s, %r" % (name, period, len(pos), N, eq, eng.last_rank_stats))
+            good &= eq
+        return good
+    return ok, check
+
+
+def synthetic(args):
+    N, B = 1_000_000, args.synthetic_rows
+    eng = Engine(N, maxlen=T, hidden_units=H, num_blocks=2, num_heads=1, seed=0)
+    rs = np.random.RandomState(0)
+    seq = np.zeros((B, T), dtype=np.int32)
+    for b in range(B):
+        ln = int(rs.randint(1, T + 1))
+        seq[b, T - ln:] = rs.randint(1, N + 1, size=ln)
+    pos = rs.randint(1, N + 1, size=B).astype(np.int32)
+    return measure("synthetic", eng, seq, pos, N, max(args.reps // 2, 2), 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--check", action="store_true", help="assert rank equality of the two dtypes on every test period of both datasets")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--train_steps", type=int, default=200)
+    ap.add_argument("--eval_batch", type=int, default=1024)
+    ap.add_argument("--synthetic_rows", type=int, default=4096)
+    ap.add_argument("--datasets", default="YOOCHOOSE,DIGINETICA")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "eval_x3.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_eval.py measures on the GPU: no device found")
+    _out.append(open(args.out, "w"))
+    say("# tools/bench_eval.py%s: Engine.rank_targets, dtype x3 (k_lx3k filter + exact recheck) against f32 (k_logits_tile<RANK>), same "
+        "process, alternating; %s" % (" --check" if args.check else "", torch.cuda.get_device_name(0)))
+    ok, checks = True, []
+    for name in [d for d in args.datasets.split(",") if d]:
+        good, check = dataset(name, args)
+        ok &= good
+        checks.append(check)
+    if args.synthetic_rows:
+        ok &= synthetic(args)
+    for check in checks:                                           # (the measurements first: the checks are the long part)
+        ok &= check()
+    say("# ranks equal everywhere: %s" % ok)
+    if args.check and not ok:
+        raise SystemExit("rank mismatch between x3 and f32")
+
+
+if __name__ == "__main__":
+    main()
