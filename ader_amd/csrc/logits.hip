@@ -9,6 +9,7 @@
 //   k_logits_tile<LSE>   per-row online (max, sum-exp, target.logit) partials      -> k_lse_loss
 //   k_logits_tile<RANK>  per-row count of items ranked before the target           (Evaluator, util.py:323-325)
 //   k_logits_tile<STORE> dense logits (teacher logits of selected exemplars, util.py:433; model.logits fetch)
+//   k_topk_tile/_merge   per-row best k items by (logit descending, id ascending), the STORE bits       (Engine.recommend)
 //   k_logits_bwd_drep    dRep[b,:] = sum_n dlogit[b,n] E[n,:]   (b-chunk x item-range workgroups, slabs)
 //   k_logits_bwd_de      dE[n,:]   = sum_b dlogit[b,n] rep[b,:] (item-tile workgroups; rows written once, no atomics)
 // with dlogit[b,n] = w_b * (softmax_b[n] - target_b[n]) for n < ncol_b, else 0.
@@ -439,6 +440,190 @@ __global__ __launch_bounds__(256) void k_pair_logit_rank(LogitArgs a, const floa
         }
 }
 
+// ============================================================================================= exact top-K items
+// ader_topk_items: for every row the k best items of 1..N by (score descending, item id ascending) -- the order of ader_rank_targets and
+// of tf.argsort (ADER.py:103) -- where the score of (b, n) is the float32 of k_logits_tile<MODE_STORE>: the same stage_tile layout, the
+// same mma_tile<2> call, the same ksteps.  A candidate is one 64-bit key: order-preserving float bits above, the complemented 1-based
+// item id below, so ONE unsigned compare is the total order and no two candidates of a row compare equal.  Key 0 = "no candidate".
+// (The MFMA chain starts from +0 and rounds to nearest, so it never yields -0; topk_key still folds -0 onto +0, as == does.)
+// The best k of a set under a total order do not depend on the order the set was visited in: that is the whole determinism argument --
+// LDS atomics only hand out buffer slots, the kept SET is the same however they land, and every output is derived from sorted keys.
+typedef unsigned long long u64;
+#define TOPK_KMAX 64
+
+struct TopkArgs {
+    const float* rep;      // [B,H]
+    const float* emb1;     // table row 1 (item 1) : [N,H]
+    int B, Bp, H, N;
+    const int* ncol;       // [Bp] N for real rows, 0 for padding rows
+    const int* seen;       // [B, seen_ld] 1-based ids never to be returned (0 = none), or NULL
+    int seen_ld, k, ranges;
+    u64* part;             // [ranges][Bp][k]
+    int* items;            // [B,k]
+    float* scores;         // [B,k]
+};
+
+__device__ __forceinline__ u64 topk_key(float s, int item1) {
+    uint32_t u = __float_as_uint(s + 0.0f);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((u64)u << 32) | (uint32_t)~(uint32_t)item1;
+}
+__device__ __forceinline__ float topk_score(u64 key) {
+    const uint32_t u = (uint32_t)(key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+__device__ __forceinline__ int topk_item(u64 key) { return (int)~(uint32_t)key; }
+
+// Workgroup = (64-row chunk, contiguous range of 64-item tiles), block -> (range, chunk) as in k_logits_bwd_drep.  The chunk's rep rows
+// are staged once; the range's table tiles stream through E_l, the next tile's loads in flight (registers) under the current tile's MFMAs.
+// Per batch row a candidate buffer of k + 64 keys in LDS:
+//   filter   a lane proposes (row, item) only if the item is a column of the row, is not marked seen, and its key beats thr[row], the
+//            row's k-th best key at its last compaction (0 before the first);
+//   append   into buf[row][cnt[row]++] (LDS atomic: hands out the slot, nothing else);
+//   compact  a row holding more than k keys is cut to its best k, sorted, and thr[row] <- its k-th.  Workgroup-uniform, decided by one
+//            __syncthreads_or per tile.
+// INVARIANT: every row enters a tile with cnt <= k, a 64-item tile proposes at most 64 keys per row, and every row with cnt > k is
+// compacted before the next tile: cnt <= k + 64 = the buffer's size, always.
+// Seen ids: per tile, 8 threads per row fold the row's ids that fall into the tile into a 64-bit mask (no over-selection, no second pass).
+#define TOPK_STAGE_REGS ((64 * LDE + 511) / 512)
+__global__ __launch_bounds__(512) void k_topk_tile(TopkArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* E_l = smem;                                       // [TI][LDE]
+    float* R_l = E_l + TI * LDE;                             // [TB][LDE]
+    u64* buf = (u64*)(R_l + TB * LDE);                       // [TB][k + 64]
+    const int k = a.k, ldb = k + TI;
+    u64* thr = buf + TB * ldb;                               // [TB]
+    u64* msk = thr + TB;                                     // [TB] bit i: item tile0 + i is in the row's seen list
+    int* cnt = (int*)(msk + TB);                             // [TB]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int mw = wave & 3, nw = wave >> 2;
+    const int H = a.H, ksteps = (H + 3) >> 2;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int nchunk = a.Bp / TB;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int range = xcd + 8 * (slot / nchunk), bc = slot % nchunk;
+    if (range >= a.ranges) return;
+    const int nsub_total = (a.N + TI - 1) / TI;
+    const int s_begin = (int)((long)range * nsub_total / a.ranges), s_end = (int)((long)(range + 1) * nsub_total / a.ranges);
+    // stage_tile's layout, written out: one more caller of stage_tile changes the code the compiler emits for the existing ones
+    // (tools/isa_digest.py), and their instruction streams are pinned
+    for (int i = tid; i < 64 * LDE; i += 512) {
+        const int r = i / LDE, c = i - r * LDE;
+        R_l[i] = (bc * TB + r < a.B && c < H) ? a.rep[(size_t)(bc * TB + r) * H + c] : 0.0f;
+    }
+    if (tid < TB) { thr[tid] = 0; msk[tid] = 0; cnt[tid] = 0; }
+    int nc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) nc[j] = a.ncol[bc * TB + nw * 32 + j * 16 + r16];
+    float pre[TOPK_STAGE_REGS];                              // the next tile, in stage_tile's element order
+    auto load_tile = [&](int tile0) {
+#pragma unroll
+        for (int n = 0; n < TOPK_STAGE_REGS; ++n) {
+            const int i = tid + n * 512, r = i / LDE, c = i - r * LDE;
+            pre[n] = (i < 64 * LDE && tile0 + r < a.N && c < H) ? a.emb1[(size_t)(tile0 + r) * H + c] : 0.0f;
+        }
+    };
+    if (s_begin < s_end) load_tile(s_begin * TI);
+    for (int s = s_begin; s < s_end; ++s) {
+        const int tile0 = s * TI;
+        __syncthreads();                                     // the previous tile's MFMA reads, filter and compaction are done
+#pragma unroll
+        for (int n = 0; n < TOPK_STAGE_REGS; ++n)
+            if (tid + n * 512 < 64 * LDE) E_l[tid + n * 512] = pre[n];
+        if (a.seen) {                                        // thread (row = tid / 8, part = tid % 8): the 8 lanes of a row are neighbours
+            const int row = tid >> 3, b = bc * TB + row;
+            u64 m = 0;
+            if (b < a.B)
+                for (int t = tid & 7; t < a.seen_ld; t += 8) {
+                    const unsigned d = (unsigned)(a.seen[(size_t)b * a.seen_ld + t] - 1 - tile0);      // id 0 -> d wraps: never < 64
+                    if (d < 64u) m |= 1ull << d;
+                }
+            m |= __shfl_xor(m, 1, 64); m |= __shfl_xor(m, 2, 64); m |= __shfl_xor(m, 4, 64);
+            if ((tid & 7) == 0) msk[row] = m;
+        }
+        __syncthreads();
+        if (s + 1 < s_end) load_tile(tile0 + TI);
+        f32x4 acc[2];
+        acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        mma_tile<2>(E_l + mw * 16 * LDE, LDE, 1, R_l + nw * 32 * LDE, 1, LDE, ksteps, acc, lane);
+        const int il0 = mw * 16 + q * 4, item0 = tile0 + il0;      // this lane's 4 consecutive items
+        int over = 0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int bl = nw * 32 + j * 16 + r16;                  // batch row within the chunk
+            const u64 t = thr[bl];
+            const unsigned sm = (unsigned)(msk[bl] >> il0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int it = item0 + r;
+                const u64 key = topk_key(acc[j][r], it + 1);
+                if (it < nc[j] && !((sm >> r) & 1u) && key > t) {
+                    const int p = atomicAdd(cnt + bl, 1);           // p < k + 64 (the invariant above)
+                    buf[bl * ldb + p] = key;
+                    over |= (p >= k);
+                }
+            }
+        }
+        if (__syncthreads_or(over)) {                               // some row holds more than k keys: wave w compacts rows 8w .. 8w+7
+            for (int rr = 0; rr < TB / 8; ++rr) {
+                const int row = wave * (TB / 8) + rr, n = cnt[row];
+                if (n <= k) continue;                               // (wave-uniform)
+                u64* bp = buf + row * ldb;
+                const u64 e0 = lane < n ? bp[lane] : 0, e1 = lane + 64 < n ? bp[lane + 64] : 0;      // n <= k + 64 <= 128
+                int r0 = 0, r1 = 0;                                 // keys of a row are distinct: rank = number of larger keys
+                for (int i = 0; i < n; ++i) { const u64 x = bp[i]; r0 += x > e0; r1 += x > e1; }
+                // in place: a rank depends on every read of the loop, and one wave's LDS operations are performed in order
+                if (lane < n && r0 < k) { bp[r0] = e0; if (r0 == k - 1) thr[row] = e0; }
+                if (lane + 64 < n && r1 < k) { bp[r1] = e1; if (r1 == k - 1) thr[row] = e1; }
+                if (lane == 0) cnt[row] = k;
+            }
+        }
+    }
+    __syncthreads();
+    u64* o = a.part + ((size_t)range * a.Bp + bc * TB) * k;
+    for (int i = tid; i < TB * k; i += 512) {
+        const int row = i / k, j = i - row * k;
+        o[i] = j < cnt[row] ? buf[row * ldb + j] : 0;               // (an empty range writes zeros: no candidate)
+    }
+}
+
+// One workgroup per real row: the best k of the row's ranges * k partial keys by the same filter / append / compact over batches of 256
+// keys (buffer k + 256), a final compaction that sorts, then unpack.  Key 0 (an empty slot of a range) never beats the threshold.
+__global__ __launch_bounds__(256) void k_topk_merge(TopkArgs a) {
+    __shared__ u64 mb[TOPK_KMAX + 256];
+    __shared__ u64 mthr;
+    __shared__ int mcnt;
+    const int tid = threadIdx.x, b = blockIdx.x, k = a.k, total = a.ranges * k;
+    if (tid == 0) { mthr = 0; mcnt = 0; }
+    __syncthreads();
+    for (int base = 0; base <= total; base += 256) {                // the pass at base >= total appends nothing: the final, sorting compaction
+        const int i = base + tid;
+        const bool last = base + 256 > total;
+        u64 key = 0;
+        if (i < total) { const int rg = i / k; key = a.part[((size_t)rg * a.Bp + b) * k + (i - rg * k)]; }
+        int over = 0;
+        if (key > mthr) { const int p = atomicAdd(&mcnt, 1); mb[p] = key; over = (p >= k); }
+        if (__syncthreads_or(over | last)) {
+            const int n = mcnt;                                     // n <= k + 256 <= 320: at most two keys per thread
+            const u64 e0 = tid < n ? mb[tid] : 0, e1 = tid + 256 < n ? mb[tid + 256] : 0;
+            int r0 = 0, r1 = 0;
+            for (int j = 0; j < n; ++j) { const u64 x = mb[j]; r0 += x > e0; r1 += x > e1; }
+            __syncthreads();
+            if (tid < n && r0 < k) { mb[r0] = e0; if (r0 == k - 1) mthr = e0; }
+            if (tid + 256 < n && r1 < k) { mb[r1] = e1; if (r1 == k - 1) mthr = e1; }
+            if (tid == 0) mcnt = min(n, k);
+            __syncthreads();
+        }
+        if (last) break;
+    }
+    const int n = mcnt;
+    for (int j = tid; j < k; j += 256) {
+        const bool real = j < n;
+        a.items[(size_t)b * k + j] = real ? topk_item(mb[j]) : 0;
+        a.scores[(size_t)b * k + j] = real ? topk_score(mb[j]) : -INFINITY;
+    }
+}
+
 // ============================================================================================= C ABI
 static const size_t kTileLds = (size_t)(2 * 64 * LDE + 4 * TB * 3 + MAXB * 3) * sizeof(float);
 static const size_t kBwdLds = (size_t)(2 * 64 * LDE + 64 * LDD) * sizeof(float);
@@ -605,6 +790,39 @@ int ader_rank_targets(const float* rep, const float* emb, int B, int Bp, int H, 
     hipLaunchKernelGGL(k_target_logit, dim3(Bp / TB), dim3(256), kTgtLds, st, a, tlogit);
     a.tlogit = tlogit; a.rank = rank;
     hipLaunchKernelGGL(k_logits_tile<MODE_RANK>, dim3((N + TI - 1) / TI), dim3(512), kTileLds, st, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// Exact top-K items of every row (kernels above).  ader_topk_ranges: item ranges per 64-row chunk -- about one workgroup per CU over the
+// Bp/64 chunks, a multiple of 8 (the block -> (range, chunk) mapping), so it may exceed the number of 64-item tiles: such ranges are empty.
+int ader_topk_kmax(void) { return TOPK_KMAX; }
+int ader_topk_ranges(int N, int Bp) {
+    const int nsub = (N + TI - 1) / TI;
+    const int nchunk = Bp / TB > 0 ? Bp / TB : 1;
+    int target = 256 / nchunk / 8 * 8;
+    if (target < 8) target = 8;
+    int r = (nsub + 7) / 8 * 8;
+    if (r > target) r = target;
+    if (r < 8) r = 8;
+    return r;
+}
+// items / scores [B,k]: the first k of items 1..N (minus the non-zero ids of seen[b, 0:seen_ld], if seen) by (score descending, id
+// ascending); fewer than k candidates: the tail is item 0, score -inf.  ncol: [Bp] = N for real rows, 0 for padding; seen: [B, seen_ld]
+// or NULL; part: ader_topk_ranges(N,Bp) * Bp * k keys of scratch.  Enqueue only.
+int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
+                    int k, unsigned long long* part, int* items, float* scores, void* stream) {
+    if (k < 1 || k > TOPK_KMAX || Bp % TB != 0 || Bp > MAXB || B > Bp || H > HP || H < 1 || N < 1 || (seen && seen_ld < 1)) return -2;
+    if (B <= 0) return 0;
+    TopkArgs a;
+    a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ncol = ncol; a.seen = seen; a.seen_ld = seen_ld; a.k = k;
+    a.ranges = ader_topk_ranges(N, Bp); a.part = part; a.items = items; a.scores = scores;
+    const size_t lds = (size_t)(2 * 64 * LDE) * sizeof(float) + (size_t)TB * (k + TI) * sizeof(u64) + TB * (2 * sizeof(u64) + sizeof(int));
+    const int rc = ader_dyn_lds<k_topk_tile>(lds);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_topk_tile, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, a);
+    hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, st, a);
     HIP_LAUNCH_CHECK();
     return 0;
 }

@@ -1,4 +1,4 @@
-"""Inference paths: encode, logits, ranks (util.py:323-325), row losses, herding selection (util.py:436-461)."""
+"""Inference paths: encode, logits, ranks (util.py:323-325), top-K items, row losses, herding selection (util.py:436-461)."""
 import numpy as np
 import torch
 
@@ -148,6 +148,35 @@ class _Infer:
             "candidates": int(diag[:, 0].sum()), "pairs": int(n) * N, "overflowed_chunks": len(over),
             "max_err_over_delta": float(diag[:, 1].copy().view(np.float32).max()) if len(chunks) else 0.0}
         return ranks
+
+    def recommend(self, seq, k, max_item=None, exclude_seen=False):
+        """The k best items of 1..max_item for every row, fused with the catalog logits (ader_topk_items): (items int32 [n,k], 1-based;
+        scores float32 [n,k]) as numpy.  Order: (score descending, item id ascending) -- the tie rule of rank_targets -- on the very
+        float32 logits() returns, so items == stable_argsort(-logits)[:, :k] + 1 and rank_targets(seq_b, items[b, j]) == j.
+        exclude_seen removes the non-zero ids of the row's own seq from its candidates (off by default: a repeated item is a legitimate
+        target, and the reference's evaluation does not exclude).  Fewer than k candidates: the tail is item 0, score -inf.
+        max_item=None: the whole catalog.  Chunks of MAX_ROWS rows, one device -> host copy."""
+        kmax = call("ader_topk_kmax")
+        k = int(k)
+        N = self.item_num if max_item is None else int(max_item)
+        _check(1 <= k <= kmax, "recommend: k must be in 1..%d (got %d)" % (kmax, k))
+        _check(1 <= N <= self.item_num, "recommend: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        self._refresh_stream()
+        self.sync_table()
+        seq = self._seq_in(seq)
+        n = seq.shape[0]
+        res = torch.empty((2, n, k), dtype=torch.int32, device=self.device)      # items | score bits: one copy back
+        scores = res[1].view(torch.float32)
+        for s in range(0, n, self.MAX_ROWS):
+            e = min(n, s + self.MAX_ROWS)
+            B = e - s
+            Bp = (B + 63) // 64 * 64
+            rep = self.forward(seq[s:e], training=False)
+            part = self.buf("tk_part", (call("ader_topk_ranges", N, Bp) * Bp * k,), torch.int64)
+            call("ader_topk_items", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
+                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, ptr(part), ptr(res[0, s:e]), ptr(scores[s:e]), self._stream())
+        host = res.cpu().numpy()
+        return host[0], host[1].view(np.float32)
 
     def row_losses(self, seq, pos, max_item):
         """Per-row cross entropy -log softmax(logits)[label] in eval mode (the quantity the reference's `loss` exemplar selector

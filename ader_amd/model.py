@@ -74,6 +74,10 @@ class Ader:
     def rank_targets(self, seq, pos, max_item):
         return self.engine.rank_targets(seq, pos, max_item)
 
+    def recommend(self, seq, k, max_item=None, exclude_seen=False):
+        """The k best items per session, (items int32 [n,k], scores float32 [n,k]): Engine.recommend."""
+        return self.engine.recommend(seq, k, max_item, exclude_seen)
+
     def predict(self, sess, seq, item_idx):
         """Rank of every candidate item (ADER.py:140-150).  Kept for API parity; the Evaluator uses rank_targets."""
         return sess.run(self.pred_last, {self.input_seq: seq, self.test_item: item_idx, self.is_training: False,

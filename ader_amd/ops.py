@@ -13,6 +13,8 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
   ader::rank_of_target(rep, emb, target, N)                    -> rank   ADER.py:99-103 + util.py:325
   ader::rank_of_target_x3(rep, emb, target, N)                 -> rank   the same ranks; products on the bf16 matrix cores (x3 filter
                                                                          + exact-f32 recheck of the undecided pairs)
+  ader::topk_items(rep, emb, seen, N, k)                       -> (items, scores)   the k best items per row, fused with the logits:
+                                                                         order and bits of argsort(-logits) (ADER.py:92, 103)
   ader::herding_select(rep, seg, quota, max_steps)             -> (sel, cnt)   util.py:401-434
 
 Trainable surface (second half of this file; every forward has an autograd formula over its `_bwd` operator):
@@ -24,6 +26,7 @@ Trainable surface (second half of this file; every forward has an autograd formu
 """
 
 import os
+from typing import Optional
 
 import torch
 
@@ -180,6 +183,37 @@ def rank_of_target_x3(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor
 @rank_of_target_x3.register_fake
 def _(rep, emb, target, N):
     return target.new_empty(rep.shape[0])
+
+
+@torch.library.custom_op("ader::topk_items", mutates_args=())
+def topk_items(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor], N: int, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """rep [B,H], emb [V,H] (row 0 = padding item), seen int32 [B,S] ids to leave out (0 = none, ids above N ignored) or None ->
+    (items int32 [B,k], scores float32 [B,k]): the first k of items 1..N by (logit descending, id ascending), the logits of
+    ader_logits_store bit for bit; fewer than k candidates: item 0, score -inf."""
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
+    B, H = rep.shape
+    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
+        raise RuntimeError("ader::topk_items: bad shapes")
+    if not (1 <= k <= call("ader_topk_kmax")):
+        raise RuntimeError("ader::topk_items: k must be in 1..%d (got %d)" % (call("ader_topk_kmax"), k))
+    if seen is not None:
+        _chk(seen, "seen", torch.int32, 2)
+        if seen.shape[0] != B or seen.shape[1] < 1:
+            raise RuntimeError("ader::topk_items: seen must be [B, S] with S >= 1")
+    Bp = (B + 63) // 64 * 64
+    dev = rep.device
+    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
+    ncol[:B] = N
+    part = torch.empty(call("ader_topk_ranges", N, Bp) * Bp * k, dtype=torch.int64, device=dev)
+    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
+    call("ader_topk_items", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen.shape[1] if seen is not None else 0, k,
+         ptr(part), ptr(items), ptr(scores), _st())
+    return items, scores
+
+
+@topk_items.register_fake
+def _(rep, emb, seen, N, k):
+    return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
 
 
 @torch.library.custom_op("ader::herding_select", mutates_args=())

@@ -249,6 +249,16 @@ int ader_rank_emax(const float* emb, int item_num, int H, int N, float* emax, vo
 int ader_rank_targets_x3(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* target,
                          const int* ncol, void* rep_hi, void* rep_lo, float* tlogit, float* delta, const float* emax, int* cand, int cap,
                          int* diag, int* rank, void* stream);
+/* Exact top-K recommendation fused with the catalog logits: items / scores [B,k] = the first k of items 1..N ordered by (score descending,
+ * item id ascending) -- the tie rule of ader_rank_targets -- where the score of (b, n) is bit for bit the float32 ader_logits_store writes.
+ * seen: [B, seen_ld] int32 ids removed from row b's candidates (0 = none; ids above N are ignored), or NULL.  Fewer than k candidates: the
+ * tail is item 0, score -inf.  A pure function of (rep row, table, N, k, seen ids): no dependence on the other rows or on scheduling.
+ * ncol: [Bp] = N for real rows, 0 for padding.  part: ader_topk_ranges(N,Bp)*Bp*k 64-bit keys of scratch.  Enqueue only.
+ * -2 when k < 1, k > ader_topk_kmax() (= 64), Bp % 64 != 0, Bp > 1024, B > Bp or H > 160. */
+int ader_topk_kmax(void);
+int ader_topk_ranges(int N, int Bp);
+int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
+                    int k, unsigned long long* part, int* items, float* scores, void* stream);
 
 /* ---- bf16-MFMA variant of the one-hot softmax CE (fp32 master table, fp32 accumulate/softmax): ADER.py:88-93 ------ */
 /* Bp % 128 == 0, H even.  Scratch: rep_bf Bp*168 bf16; pm, pl: R*Bp floats; pO: R*Bp*160 floats, R = ader_lbf_ranges(N,Bp).

@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Top-K recommendation, fused (Engine.recommend) against the composition a caller had to write before it existed.
+
+    python tools/bench_topk.py [--check] [--reps 3] [--warmup 1] [--rows 1024] [--k 20] [--out profiles/topk.txt]
+
+(A) Engine.recommend(seq, k, N): ader_topk_items -- k_topk_tile (logit tiles + per-row selection in LDS) and k_topk_merge;
+(B) Engine.logits(seq, N) followed by torch.topk(.., k): dense [n, N] logits in HBM, then torch's selection.  (B) is the yardstick.
+Shapes: --rows sessions at the catalog sizes of the two datasets (N = 25,750 and 43,105) and at N = 10^6, each on an Engine of that
+catalog size at its initial weights with synthetic sessions (random lengths, uniform ids), as tools/bench_eval.py builds its synthetic
+shape.  One process; after a warm-up (A) and (B) alternate inside every repetition; device events around the whole call (session
+forward, launches, the copy back), medians.  The kernels of (A) are timed by torch.profiler over one more call; k_topk_tile is set
+against its two bounds: 2 n N H over the f32 MFMA peak (157.3 TFLOP/s, v_mfma_f32_16x16x4_f32) and N H 4 bytes per 64-row chunk over
+the HBM peak (8 TB/s) -- the larger one binds.  --check asserts that the items of (A) and (B) agree on every row whose k-th and (k+1)-th
+scores of (B) differ (torch.topk does not promise an order among ties) and that the scores agree bitwise there."""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from ader_amd._lib import call  # noqa: E402
+from ader_amd.engine import Engine  # noqa: E402
+
+PEAK_F32_MFMA, PEAK_HBM = 157.3e12, 8.0e12
+T, H = 50, 150
+_out = []
+
+
+def say(*a):
+    line = " ".join(str(x) for x in a)
+    print(line, flush=True)
+    if _out:
+        _out[0].write(line + "\n")
+        _out[0].flush()
+
+
+def ev_time(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    r = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e-3, r
+
+
+def composed(eng, seq, N, k):
+    """What a caller writes without Engine.recommend: dense logits, torch.topk, the copy back.  k + 1 columns: --check needs the next score."""
+    lg = eng.logits(seq, N)
+    v, i = torch.topk(lg, min(k + 1, N), dim=1)
+    return (i + 1).to(torch.int32).cpu().numpy(), v.cpu().numpy()
+
+
+def kernel_times(fn):
+    """Device time per kernel name over one call of fn (torch.profiler); {} if the profiler reports no kernels."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    out = {}
+    for e in prof.key_averages():
+        t = getattr(e, "device_time_total", None)
+        if t is None:
+            t = getattr(e, "cuda_time_total", 0.0)
+        if t:
+            out[e.key] = out.get(e.key, 0.0) + t * 1e-6
+    return out
+
+
+def measure(N, args):
+    n, k = args.rows, args.k
+    eng = Engine(N, maxlen=T, hidden_units=H, num_blocks=2, num_heads=1, seed=0)
+    rs = np.random.RandomState(0)
+    seq = np.zeros((n, T), dtype=np.int32)
+    for b in range(n):
+        ln = int(rs.randint(1, T + 1))
+        seq[b, T - ln:] = rs.randint(1, N + 1, size=ln)
+    seq_d = torch.from_numpy(seq).to(eng.device)
+    tA, tB, a, b = [], [], None, None
+    for it in range(args.warmup + args.reps):
+        ta, a = ev_time(lambda: eng.recommend(seq_d, k, N))
+        tb, b = ev_time(lambda: composed(eng, seq_d, N, k))
+        if it >= args.warmup:
+            tA.append(ta)
+            tB.append(tb)
+    tf = statistics.median(ev_time(lambda: eng.encode(seq_d))[0] for _ in range(args.reps))
+    med = statistics.median
+    rows = min(n, eng.MAX_ROWS)
+    Bp = (rows + 63) // 64 * 64
+    ranges = call("ader_topk_ranges", N, Bp)
+    say("== N = %d: %d rows, k = %d, H = %d; %d repetitions after %d warm-up, medians [min .. max]" % (N, n, k, H, args.reps, args.warmup))
+    say("  (A) Engine.recommend       %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (%d ranges x %d rows x k keys of 8 B)" %
+        (med(tA) * 1e3, min(tA) * 1e3, max(tA) * 1e3, n / med(tA), ranges * Bp * k * 8, ranges, Bp))
+    say("  (B) logits + torch.topk    %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (the [n, N] float32 logits)" %
+        (med(tB) * 1e3, min(tB) * 1e3, max(tB) * 1e3, n / med(tB), n * ((N + 3) // 4 * 4) * 4))
+    say("  (A) / (B) whole call %.3f  (< 1: the fused path is faster); session forward (encode) alone %.2f ms" % (med(tA) / med(tB), tf * 1e3))
+    kt = kernel_times(lambda: eng.recommend(seq_d, k, N))
+    tile = sum(t for name, t in kt.items() if "k_topk_tile" in name)
+    merge = sum(t for name, t in kt.items() if "k_topk_merge" in name)
+    nchunk = sum((min(n, s + eng.MAX_ROWS) - s + 63) // 64 for s in range(0, n, eng.MAX_ROWS))
+    b_mfma, b_hbm = 2.0 * n * N * H / PEAK_F32_MFMA, float(nchunk) * N * H * 4 / PEAK_HBM
+    bound, which = max((b_mfma, "MFMA"), (b_hbm, "HBM"))
+    if tile:
+        say("  k_topk_tile %.3f ms, k_topk_merge %.3f ms (torch.profiler, one call); bounds: 2nNH over the f32 MFMA peak %.3f ms, N H 4 B x %d "
+            "chunks over the HBM peak %.3f ms -> %s binds; k_topk_tile = %.1f x its bound" %
+            (tile * 1e3, merge * 1e3, b_mfma * 1e3, nchunk, b_hbm * 1e3, which, tile / bound))
+    else:
+        say("  torch.profiler reported no k_topk_tile rows (kernels seen: %d): kernel time NOT measured; bounds: MFMA %.3f ms, HBM %.3f ms "
+            "-> %s binds" % (len(kt), b_mfma * 1e3, b_hbm * 1e3, which))
+    ok = True
+    if args.check:
+        ib, vb = b
+        decided = vb[:, k - 1] != vb[:, k] if vb.shape[1] > k else np.ones(n, dtype=bool)
+        kk = min(k, vb.shape[1])
+        same_items = np.array_equal(a[0][decided, :kk], ib[decided, :kk])
+        same_bits = np.array_equal(np.ascontiguousarray(a[1][decided, :kk]).view(np.int32), np.ascontiguousarray(vb[decided, :kk]).view(np.int32))
+        ok = bool(same_items and same_bits)
+        say("  check: %d of %d rows have distinct k-th and (k+1)-th scores; on those, items equal: %s, scores bitwise equal: %s" %
+            (int(decided.sum()), n, same_items, same_bits))
+    del eng
+    torch.cuda.empty_cache()
+    return ok
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--check", action="store_true", help="assert that (A) and (B) return the same items wherever (B)'s order is decided")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--rows", type=int, default=1024)
+    ap.add_argument("--k", type=int, default=20)
+    ap.add_argument("--catalogs", default="25750,43105,1000000")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "topk.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_topk.py measures on the GPU: no device found")
+    _out.append(open(args.out, "w"))
+    say("# tools/bench_topk.py%s: (A) Engine.recommend (k_topk_tile + k_topk_merge) against (B) Engine.logits + torch.topk, same process, "
+        "alternating; %s" % (" --check" if args.check else "", torch.cuda.get_device_name(0)))
+    ok = True
+    for N in [int(x) for x in args.catalogs.split(",") if x]:
+        ok &= measure(N, args)
+    say("# items equal wherever the yardstick's order is decided: %s" % (ok if args.check else "not checked"))
+    if args.check and not ok:
+        raise SystemExit("top-K mismatch between Engine.recommend and logits + torch.topk")
+
+
+if __name__ == "__main__":
+    main()
