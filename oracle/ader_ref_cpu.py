@@ -223,8 +223,14 @@ def loss_fn(params, seq, pos, max_item, L, num_heads, *, ex_logits=None, ex_pos=
     rep = forward_rep(params, seq, L, num_heads, training=training, rate=rate, seed=seed, step=step, row0=row0,
                       relu_masks=relu_masks)
     logits = logits_from_rep(params, rep, max_item, logits_bf16)
+    return loss_tail(logits, pos, ex_logits=ex_logits, ex_pos=ex_pos, lambda_=lambda_, n_train_global=n_train_global,
+                     n_ex_global=n_ex_global)
+
+
+def loss_tail(logits, pos, *, ex_logits=None, ex_pos=None, lambda_=0.0, n_train_global=None, n_ex_global=None):
+    """The loss of ADER.py:93 / 108-137 from the logits [rows, max_item] (train rows first, exemplar rows after)."""
     n_ex = 0 if (ex_logits is None and ex_pos is None) else (len(ex_logits) if ex_logits is not None else len(ex_pos))
-    n_train = seq.shape[0] - n_ex
+    n_train = logits.shape[0] - n_ex
     pos = torch.as_tensor(pos).long()
     lsm = torch.log_softmax(logits[:n_train], -1)
     ce = -lsm[torch.arange(n_train), pos - 1]                                # one_hot(pos-1)
