@@ -14,10 +14,14 @@ class _Backward:
         """dW = A^T.G, db = colsum(G).  In x3 mode the products are queued (A and G stay untouched until the end of the
         backward pass) and issued as one batched launch by _atb_flush.  pack: the operands are in tile order (packed session
         kernels): the plan tells the product which rows exist."""
+        self._atb_item((A, G, self._gp[wname], self._gp[bname], M, pack), slab)
+
+    def _atb_item(self, it, slab):
+        """_atb of a prepared product (A, G, dW, db, M, pack), the form the queue holds."""
         if self.gemm_x3:
-            self._atb_put((A, G, self._gp[wname], self._gp[bname], M, pack))
+            self._atb_put(it)
             return
-        call("ader_gemm_atb", ptr(A), ptr(G), ptr(slab), self._gp[wname], self._gp[bname], M, self.H, self._stream())
+        call("ader_gemm_atb", ptr(it[0]), ptr(it[1]), ptr(slab), it[2], it[3], it[4], self.H, self._stream())
 
     def _settle_loss(self):
         """The loss sum a deferred step still owes (StepState.pending_loss), on the current stream."""
@@ -457,10 +461,7 @@ class _Backward:
             #  addresses dx through the id lists, which leave the padding out)
             self._late_call("ader_pos_grad_packed", ptr(dx), ptr(pk["slen"]), gp["pos"], B, T, H)
             if not defer and sx.early is None:
-                lab0 = self.buf("dp_lab0", (1,), torch.int32, zero=True)
-                ids_s, order, sp_start, _, _, _, _ = self._sparse_lists(seq, lab0, self.item_num)
-                call("ader_scatter_rows_ordered", ptr(ids_s), ptr(order), ptr(sp_start), sp_start.numel() - 1, ptr(dx), H, self.V,
-                     float(np.sqrt(np.float32(H))), ptr(demb), st)
+                self._scatter_dx(seq, dx, demb)
         elif defer and fused_emb:
             # (block 0's ader_seq_bwd_qkv has already applied the prologue mask / dropout to the rows: seq = NULL)
             self._late_call("ader_embed_bwd_rows", None, ptr(dx), gp["pos"], B, T, H, self.V, *A["d_emb"].args())
@@ -471,47 +472,42 @@ class _Backward:
             # reproducible too (the reference sets TF_DETERMINISTIC_OPS, main.py:121-122)
             call("ader_embed_bwd_rows", None if fused_emb else ptr(seq), ptr(dx), gp["pos"], B, T, H, self.V, *A["d_emb"].args(), st)
             if not defer and sx.early is None:
-                lab0 = self.buf("dp_lab0", (1,), torch.int32, zero=True)
-                ids_s, order, sp_start, _, _, _, _ = self._sparse_lists(seq, lab0, self.item_num)
-                call("ader_scatter_rows_ordered", ptr(ids_s), ptr(order), ptr(sp_start), sp_start.numel() - 1, ptr(dx), H, self.V,
-                     float(np.sqrt(np.float32(H))), ptr(demb), st)
+                self._scatter_dx(seq, dx, demb)
         tb.__exit__(None, None, None)
         sx.late_on = False
         return dx
 
-    def _bwd_block_fused(self, l, S, seq, dxo, dxn, M, B, emb_bwd, d_emb):
-        """Backward of block l with the session-tiled chains (seq_bwd.hip) around the attention backward; queues the five
-        weight-gradient products.  dxo: gradient of the block output ([B*T,H], or [B,H] for the pruned last block);
-        dxn [B*T,H] receives the gradient of the block input."""
+    def _scatter_dx(self, seq, dx, demb):
+        """The input-gradient rows dx [B*T,H] added into the table gradient, bucket by bucket in position order."""
+        lab0 = self.buf("dp_lab0", (1,), torch.int32, zero=True)
+        ids_s, order, sp_start, _, _, _, _ = self._sparse_lists(seq, lab0, self.item_num)
+        call("ader_scatter_rows_ordered", ptr(ids_s), ptr(order), ptr(sp_start), sp_start.numel() - 1, ptr(dx), self.H, self.V,
+             float(np.sqrt(np.float32(self.H))), ptr(demb), self._stream())
+
+    def _bwd_block_desc(self, l, S, pre, sfx, B, M, rows, slab_rows, seq, dxo, dxn, emb_bwd, d_emb, pack_m, pack_rows):
+        """Descriptors and workspace of block l's backward for the session-tiled chains, one workgroup per session (seq_bwd.hip) or
+        packed tiles (seqp_bwd.hip).  The buffers are named pre + "bw_.." / "ln_slab.." (+ sfx); M = rows of the query / FFN side,
+        `rows` of the K / V side, slab_rows = LayerNorm partial rows that a chain writes; seq = the batch (None: the chain has no
+        padding rows to mask); dxo / dxn: gradient of the block output / input.  Returns (f, q, (dh2, da, dx1, dQ, dK, dV), red2,
+        red1, atbs2, atbs1): AderSeqBwdFfn, AderSeqBwdQkv, the gradient tensors between the chains, the reduction (name, args) of
+        each chain's slab, and the weight-gradient products (A, G, dW, db, M, pack) that follow each chain: w2, w1 / wq, wk, wv."""
         T, H = self.T, self.H
-        rows = B * T
-        st = self._stream()
         p = "b%d." % l
         pp, gp = self._pp, self._gp
         pruned = 1 if S["pruned"] else 0
         wp = lambda w: self.wbf.data_ptr() + self._widx[p + w] * self._wplane     # noqa: E731
-        dh2, da_ = self.buf("bw_dh2%d" % l, (M, H), zero=True), self.buf("bw_da%d" % l, (M, H), zero=True)
-        dx1, dQ = self.buf("bw_dx1%d" % l, (M, H), zero=True), self.buf("bw_dQ%d" % l, (M, H), zero=True)
-        dK, dV = self.buf("bw_dK%d" % l, (rows, H), zero=True), self.buf("bw_dV%d" % l, (rows, H), zero=True)
-        slab2, slab1 = self.buf("ln_slab%d_2" % l, (B * 2 * H,)), self.buf("ln_slab%d_1" % l, (B * 2 * H,))
+        n = lambda s: "%sbw_%s%d%s" % (pre, s, l, sfx)     # noqa: E731
+        dh2, da_ = self.buf(n("dh2"), (M, H), zero=True), self.buf(n("da"), (M, H), zero=True)
+        dx1, dQ = self.buf(n("dx1"), (M, H), zero=True), self.buf(n("dQ"), (M, H), zero=True)
+        dK, dV = self.buf("%sbw_dK%d" % (pre, l), (rows, H), zero=True), self.buf("%sbw_dV%d" % (pre, l), (rows, H), zero=True)
+        slab2 = self.buf("%sln_slab%d_2" % (pre, l), (slab_rows * 2 * H,))
+        slab1 = self.buf("%sln_slab%d_1" % (pre, l), (slab_rows * 2 * H,))
         f = _lib.AderSeqBwdFfn()
         f.seq, f.dx2, f.h1d, f.x1, f.mean2, f.std2 = ptr(seq), ptr(dxo), ptr(S["h1d"]), ptr(S["x1"]), ptr(S["mean2"]), ptr(S["std2"])
         f.ln2_g, f.w2, f.w1 = pp[p + "ln2_g"], wp("w2"), wp("w1")
         f.dh2, f.da, f.dx1, f.slab = ptr(dh2), ptr(da_), ptr(dx1), ptr(slab2)
         f.d_ffn1, f.d_ffn2 = S["d1"].c, S["d2"].c
         f.B, f.T, f.H, f.pruned = B, T, H, pruned
-        call("ader_seq_bwd_ffn", ctypes.byref(f), st)
-        self._late_call("ader_reduce_slabs", ptr(slab2), 2 * H, B, H, 1, H, gp[p + "ln2_g"], gp[p + "ln2_b"])
-        wslab = self._ws["w_slab"]
-        self._atb(S["h1d"], dh2, p + "w2", p + "b2", wslab, M)
-        self._atb(S["y"], da_, p + "w1", p + "b1", wslab, M)
-        if pruned:
-            call("ader_attn_last_bwd", ptr(dx1), ptr(S["Q"]), ptr(S["K"]), ptr(S["V"]), ptr(S["P"]), ptr(S["kmask"]),
-                 ptr(S["qmask"]), ptr(dQ), ptr(dK), ptr(dV), B, T, H, self.heads, *S["da"].args(), st)
-        else:
-            call("ader_attn_x3_bwd" if self.attn_x3 else "ader_attn_bwd", ptr(dx1), ptr(S["Q"]), ptr(S["K"]), ptr(S["V"]),
-                 ptr(S["P"]), ptr(S["kmask"]), ptr(S["qmask"]), ptr(dQ), ptr(dK), ptr(dV), B, T, H, self.heads,
-                 *S["da"].args(), st)
         q = _lib.AderSeqBwdQkv()
         q.seq, q.dQ, q.dx1, q.dK, q.dV, q.x = ptr(seq), ptr(dQ), ptr(dx1), ptr(dK), ptr(dV), ptr(S["x"])
         q.mean1, q.std1, q.ln1_g = ptr(S["mean1"]), ptr(S["std1"]), pp[p + "ln1_g"]
@@ -519,11 +515,37 @@ class _Backward:
         q.dx, q.slab = ptr(dxn), ptr(slab1)
         q.d_emb = d_emb.c
         q.B, q.T, q.H, q.pruned, q.emb_bwd = B, T, H, pruned, 1 if emb_bwd else 0
+        red2 = ("ader_reduce_slabs", (ptr(slab2), 2 * H, slab_rows, H, 1, H, gp[p + "ln2_g"], gp[p + "ln2_b"]))
+        red1 = ("ader_reduce_slabs", (ptr(slab1), 2 * H, slab_rows, H, 1, H, gp[p + "ln1_g"], gp[p + "ln1_b"]))
+        atbs2 = [(S["h1d"], dh2, gp[p + "w2"], gp[p + "b2"], M, pack_m), (S["y"], da_, gp[p + "w1"], gp[p + "b1"], M, pack_m)]
+        atbs1 = [(S["q_in"], dQ, gp[p + "wq"], gp[p + "bq"], M, pack_m), (S["x"], dK, gp[p + "wk"], gp[p + "bk"], rows, pack_rows),
+                 (S["x"], dV, gp[p + "wv"], gp[p + "bv"], rows, pack_rows)]
+        return f, q, (dh2, da_, dx1, dQ, dK, dV), red2, red1, atbs2, atbs1
+
+    def _bwd_block_fused(self, l, S, seq, dxo, dxn, M, B, emb_bwd, d_emb):
+        """Backward of block l with the session-tiled chains (seq_bwd.hip) around the attention backward; queues the five
+        weight-gradient products.  dxo: gradient of the block output ([B*T,H], or [B,H] for the pruned last block);
+        dxn [B*T,H] receives the gradient of the block input."""
+        T, H = self.T, self.H
+        st = self._stream()
+        f, q, (_, _, dx1, dQ, dK, dV), red2, red1, atbs2, atbs1 = self._bwd_block_desc(
+            l, S, "", "", B, M, B * T, B, seq, dxo, dxn, emb_bwd, d_emb, None, None)
+        wslab = self._ws["w_slab"]
+        call("ader_seq_bwd_ffn", ctypes.byref(f), st)
+        self._late_call(red2[0], *red2[1])
+        for it in atbs2:
+            self._atb_item(it, wslab)
+        if S["pruned"]:
+            call("ader_attn_last_bwd", ptr(dx1), ptr(S["Q"]), ptr(S["K"]), ptr(S["V"]), ptr(S["P"]), ptr(S["kmask"]),
+                 ptr(S["qmask"]), ptr(dQ), ptr(dK), ptr(dV), B, T, H, self.heads, *S["da"].args(), st)
+        else:
+            call("ader_attn_x3_bwd" if self.attn_x3 else "ader_attn_bwd", ptr(dx1), ptr(S["Q"]), ptr(S["K"]), ptr(S["V"]),
+                 ptr(S["P"]), ptr(S["kmask"]), ptr(S["qmask"]), ptr(dQ), ptr(dK), ptr(dV), B, T, H, self.heads,
+                 *S["da"].args(), st)
         call("ader_seq_bwd_qkv", ctypes.byref(q), st)
-        self._late_call("ader_reduce_slabs", ptr(slab1), 2 * H, B, H, 1, H, gp[p + "ln1_g"], gp[p + "ln1_b"])
-        self._atb(S["q_in"], dQ, p + "wq", p + "bq", wslab, M)
-        self._atb(S["x"], dK, p + "wk", p + "bk", wslab, rows)
-        self._atb(S["x"], dV, p + "wv", p + "bv", wslab, rows)
+        self._late_call(red1[0], *red1[1])
+        for it in atbs1:
+            self._atb_item(it, wslab)
 
     def _bwd_block_packed(self, l, S, pk, dxo, dxn, B, emb_bwd, d_emb):
         """_bwd_block_fused on packed tiles (seqp_bwd.hip): dxo = gradient of the block output (tile order, or compact [B,H] for the
@@ -531,67 +553,32 @@ class _Backward:
         T, H = self.T, self.H
         rows, mt = pk["rows"], pk["max_tiles"]
         st = self._stream()
-        p = "b%d." % l
-        pp, gp = self._pp, self._gp
-        pruned = 1 if S["pruned"] else 0
-        M = B if pruned else rows
-        mpk = None if pruned else pk           # the compact tensors of a pruned block are plain [B, H]
+        pruned = S["pruned"]
         # (cached only on the default training path: small launches queued for the side stream, weight gradients batched)
         cacheable = bool(self.cache_descriptors and self._step.late_on and self.gemm_x3)
         ck = ("bwdp", l, B, ptr(dxo), ptr(dxn), bool(emb_bwd))
         ent = self._dc(ck) if cacheable else None
-        if ent is not None and ent[0] is S and ent[1] is pk and ent[2] is d_emb:
-            # same saved-activation dict (a cached forward's): the descriptors stand, the dropout keys are this step's
-            _, _, _, f, q, attn_name, attn_args, late2, late1, atbs2, atbs1 = ent
-            f.d_ffn1, f.d_ffn2 = S["d1"].c, S["d2"].c
-            q.d_emb = d_emb.c
-            call("ader_seqp_bwd_ffn", ctypes.byref(f), pk["ref"], mt, st)
-            self._step.late.append(late2)
-            for it in atbs2:
-                self._atb_put(it)
-            call(attn_name, *attn_args, st)
-            call("ader_seqp_bwd_qkv", ctypes.byref(q), pk["ref"], mt, st)
-            self._step.late.append(late1)
-            for it in atbs1:
-                self._atb_put(it)
-            return
-        wp = lambda w: self.wbf.data_ptr() + self._widx[p + w] * self._wplane     # noqa: E731
-        sfx = "L" if pruned else ""
-        dh2, da_ = self.buf("pbw_dh2%d%s" % (l, sfx), (M, H), zero=True), self.buf("pbw_da%d%s" % (l, sfx), (M, H), zero=True)
-        dx1, dQ = self.buf("pbw_dx1%d%s" % (l, sfx), (M, H), zero=True), self.buf("pbw_dQ%d%s" % (l, sfx), (M, H), zero=True)
-        dK, dV = self.buf("pbw_dK%d" % l, (rows, H), zero=True), self.buf("pbw_dV%d" % l, (rows, H), zero=True)
-        slab2, slab1 = self.buf("pln_slab%d_2" % l, (mt * 2 * H,)), self.buf("pln_slab%d_1" % l, (mt * 2 * H,))
-        f = _lib.AderSeqBwdFfn()
-        f.seq, f.dx2, f.h1d, f.x1, f.mean2, f.std2 = None, ptr(dxo), ptr(S["h1d"]), ptr(S["x1"]), ptr(S["mean2"]), ptr(S["std2"])
-        f.ln2_g, f.w2, f.w1 = pp[p + "ln2_g"], wp("w2"), wp("w1")
-        f.dh2, f.da, f.dx1, f.slab = ptr(dh2), ptr(da_), ptr(dx1), ptr(slab2)
+        if not (ent is not None and ent[0] is S and ent[1] is pk and ent[2] is d_emb):
+            # (no batch to mask by: the tiles hold real positions only.  The compact tensors of a pruned block are plain [B, H])
+            f, q, (_, _, dx1, dQ, dK, dV), red2, red1, atbs2, atbs1 = self._bwd_block_desc(
+                l, S, "p", "L" if pruned else "", B, B if pruned else rows, rows, mt, None, dxo, dxn, emb_bwd, d_emb,
+                None if pruned else pk, pk)
+            attn_args = (ptr(dx1), ptr(S["Q"]), ptr(S["K"]), ptr(S["V"]), ptr(S["P"]), ptr(S["kmask"]), ptr(S["qmask"]), ptr(dQ), ptr(dK),
+                         ptr(dV), B, T, H, *S["da"].args(), pk["ref"]) + (() if pruned else (mt,))
+            ent = (S, pk, d_emb, f, q, "ader_attnp_last_bwd" if pruned else "ader_attnp_bwd", attn_args, red2, red1, atbs2, atbs1)
+            if cacheable:
+                self._dc_put(ck, ent)
+        # (an entry stands while the saved-activation dict is the same, a cached forward's: only the dropout keys are this step's)
+        f, q, attn_name, attn_args, red2, red1, atbs2, atbs1 = ent[3:]
         f.d_ffn1, f.d_ffn2 = S["d1"].c, S["d2"].c
-        f.B, f.T, f.H, f.pruned = B, T, H, pruned
-        call("ader_seqp_bwd_ffn", ctypes.byref(f), pk["ref"], mt, st)
-        self._late_call("ader_reduce_slabs", ptr(slab2), 2 * H, mt, H, 1, H, gp[p + "ln2_g"], gp[p + "ln2_b"])
-        wslab = self._ws["w_slab"]
-        self._atb(S["h1d"], dh2, p + "w2", p + "b2", wslab, M, mpk)
-        self._atb(S["y"], da_, p + "w1", p + "b1", wslab, M, mpk)
-        attn_args = (ptr(dx1), ptr(S["Q"]), ptr(S["K"]), ptr(S["V"]), ptr(S["P"]), ptr(S["kmask"]), ptr(S["qmask"]), ptr(dQ), ptr(dK),
-                     ptr(dV), B, T, H, *S["da"].args(), pk["ref"]) + (() if pruned else (mt,))
-        attn_name = "ader_attnp_last_bwd" if pruned else "ader_attnp_bwd"
-        call(attn_name, *attn_args, st)
-        q = _lib.AderSeqBwdQkv()
-        q.seq, q.dQ, q.dx1, q.dK, q.dV, q.x = None, ptr(dQ), ptr(dx1), ptr(dK), ptr(dV), ptr(S["x"])
-        q.mean1, q.std1, q.ln1_g = ptr(S["mean1"]), ptr(S["std1"]), pp[p + "ln1_g"]
-        q.wq, q.wk, q.wv = wp("wq"), wp("wk"), wp("wv")
-        q.dx, q.slab = ptr(dxn), ptr(slab1)
         q.d_emb = d_emb.c
-        q.B, q.T, q.H, q.pruned, q.emb_bwd = B, T, H, pruned, 1 if emb_bwd else 0
+        wslab = self._ws["w_slab"]
+        call("ader_seqp_bwd_ffn", ctypes.byref(f), pk["ref"], mt, st)
+        self._late_call(red2[0], *red2[1])
+        for it in atbs2:
+            self._atb_item(it, wslab)
+        call(attn_name, *attn_args, st)
         call("ader_seqp_bwd_qkv", ctypes.byref(q), pk["ref"], mt, st)
-        self._late_call("ader_reduce_slabs", ptr(slab1), 2 * H, mt, H, 1, H, gp[p + "ln1_g"], gp[p + "ln1_b"])
-        self._atb(S["q_in"], dQ, p + "wq", p + "bq", wslab, M, mpk)
-        self._atb(S["x"], dK, p + "wk", p + "bk", wslab, rows, pk)
-        self._atb(S["x"], dV, p + "wv", p + "bv", wslab, rows, pk)
-        if cacheable:
-            late2 = ("ader_reduce_slabs", (ptr(slab2), 2 * H, mt, H, 1, H, gp[p + "ln2_g"], gp[p + "ln2_b"]))
-            late1 = ("ader_reduce_slabs", (ptr(slab1), 2 * H, mt, H, 1, H, gp[p + "ln1_g"], gp[p + "ln1_b"]))
-            atbs2 = [(S["h1d"], dh2, gp[p + "w2"], gp[p + "b2"], M, mpk), (S["y"], da_, gp[p + "w1"], gp[p + "b1"], M, mpk)]
-            atbs1 = [(S["q_in"], dQ, gp[p + "wq"], gp[p + "bq"], M, mpk), (S["x"], dK, gp[p + "wk"], gp[p + "bk"], rows, pk),
-                     (S["x"], dV, gp[p + "wv"], gp[p + "bv"], rows, pk)]
-            self._dc_put(ck, (S, pk, d_emb, f, q, attn_name, attn_args, late2, late1, atbs2, atbs1))
+        self._late_call(red1[0], *red1[1])
+        for it in atbs1:
+            self._atb_item(it, wslab)

@@ -142,18 +142,20 @@ class _Forward:
             self._act = A
         return rep
 
-    def _forward_fused(self, seq, training, rate, step, save):
-        """forward() as one launch of ader_seq_fwd (seq_fwd.hip): same buffers, layouts and saved-activation dict as the
-        per-op path above, so the backward pass does not care which one ran."""
+    def _stack_desc(self, tag, seq, rows, p_elems, training, rate, step):
+        """AderSeqFwd of the whole stack with its workspace, for both session kernels: `rows` activation rows per block (B*T, or
+        the 64*B tile rows of the packed form) under the workspace names of `tag`; p_elems(pruned) = elements of a block's
+        probability buffer.  (Pruned, both forms keep B*heads*T: seq_fused is only set with num_heads == 1, state.py.)
+        Returns (d, A, drops): the descriptor, the saved-activation dict of the per-op path (same buffers, layouts and keys, so
+        the backward pass does not care which forward ran), and the (descriptor, site) pairs that _rekey takes."""
         B, T, H, L = seq.shape[0], self.T, self.H, self.L
-        rows = B * T
-        tag = "t" if save else "e"
         A = {"B": B, "seq": seq, "rate": rate, "training": training, "step": step}
         per_row = T * H
         pp = self._pp
         d = _lib.AderSeqFwd()
         d0 = self._drop(step, SITE_EMB, rate, training, per_row)
         A["d_emb"] = d0
+        drops = [(d0, SITE_EMB)]
         x = self.buf(tag + "x0", (rows, H), zero=True)
         rep = self.buf(tag + "rep", (B, H))
         meanf, stdf = self.buf(tag + "mf", (B,)), self.buf(tag + "sf", (B,))
@@ -170,13 +172,14 @@ class _Forward:
             da = self._drop(step, site_attn(l), rate, training, self.heads * T * T)
             d1 = self._drop(step, site_ffn1(l), rate, training, per_row)
             d2 = self._drop(step, site_ffn2(l), rate, training, per_row)
+            drops += [(da, site_attn(l)), (d1, site_ffn1(l)), (d2, site_ffn2(l))]
             M, sfx = (B, "L") if pruned else (rows, "")
             kmask = self.buf(n("km"), (rows,), zero=True)
             K, Vv = self.buf(n("K"), (rows, H), zero=True), self.buf(n("V"), (rows, H), zero=True)
             q_in = self.buf(n("qin" + sfx), (M, H), zero=True)
             mean1, std1, qmask = self.buf(n("m1" + sfx), (M,), zero=True), self.buf(n("s1" + sfx), (M,), zero=True), self.buf(n("qm" + sfx), (M,), zero=True)
             Q, x1, y = self.buf(n("Q" + sfx), (M, H), zero=True), self.buf(n("x1" + sfx), (M, H), zero=True), self.buf(n("y" + sfx), (M, H), zero=True)
-            Pm = self.buf(n("P" + sfx), (B * self.heads * T * (1 if pruned else T),), zero=True)
+            Pm = self.buf(n("P" + sfx), (p_elems(pruned),), zero=True)
             mean2, std2 = self.buf(n("m2" + sfx), (M,), zero=True), self.buf(n("s2" + sfx), (M,), zero=True)
             h1d, x2 = self.buf(n("h1" + sfx), (M, H), zero=True), self.buf(n("x2" + sfx), (M, H), zero=True)
             k = d.blk[l]
@@ -193,11 +196,18 @@ class _Forward:
             A[l] = dict(pruned=pruned, x=x, q_in=q_in, mean1=mean1, std1=std1, kmask=kmask, qmask=qmask, Q=Q, K=K, V=Vv, P=Pm,
                         x1=x1, y=y, mean2=mean2, std2=std2, h1d=h1d, da=da, d1=d1, d2=d2)
             x = x2
-        call("ader_seq_fwd", ctypes.byref(d), self._stream())
         A.update(xL=x, rep=rep, meanf=meanf, stdf=stdf)
+        return d, A, drops
+
+    def _forward_fused(self, seq, training, rate, step, save):
+        """forward() as one launch of ader_seq_fwd (seq_fwd.hip), one workgroup per session."""
+        B, T = seq.shape[0], self.T
+        d, A, _ = self._stack_desc("t" if save else "e", seq, B * T, lambda pruned: B * self.heads * T * (1 if pruned else T),
+                                   training, rate, step)
+        call("ader_seq_fwd", ctypes.byref(d), self._stream())
         if save:
             self._act = A
-        return rep
+        return A["rep"]
 
     # ---------------------------------------------------------------------------------------- packed session tiles
     PACK_DENSITY_MAX = 0.45      # "auto": pack when at most this fraction of the [B,T] positions is real
@@ -273,7 +283,7 @@ class _Forward:
     def _forward_packed(self, seq, training, rate, step, save):
         """forward() on packed tiles (ader_seq_pack_plan + ader_seqp_fwd): the saved-activation dict has the keys of the unpacked
         path, the tensors of the K / V side and of unpruned blocks in tile order ([B*64, ..], see include/ader_hip.h)."""
-        B, T, H, L = seq.shape[0], self.T, self.H, self.L
+        B, T, L = seq.shape[0], self.T, self.L
         tag = "pt" if save else "pe"
         ck = ("fwdp", (tag, B, bool(training), float(rate), self.split_rows), self._mode_key())     # (split_rows: set per step from its shape)
         ent = self._dc(ck) if self.cache_descriptors else None
@@ -296,60 +306,14 @@ class _Forward:
             return A["rep"]
         pk = self._pack_plan(seq, tag)
         rows = pk["rows"]
-        A = {"B": B, "seq": seq, "rate": rate, "training": training, "step": step, "pack": pk}
-        per_row = T * H
-        pp = self._pp
-        d = _lib.AderSeqFwd()
-        d0 = self._drop(step, SITE_EMB, rate, training, per_row)
-        A["d_emb"] = d0
-        drops = [(d0, SITE_EMB)]
-        x = self.buf(tag + "x0", (rows, H), zero=True)
-        rep = self.buf(tag + "rep", (B, H))
-        meanf, stdf = self.buf(tag + "mf", (B,)), self.buf(tag + "sf", (B,))
-        d.seq, d.emb, d.pos, d.x0, d.status = ptr(seq), pp["emb"], pp["pos"], ptr(x), ptr(self.status)
-        d.lnf_g, d.lnf_b, d.rep, d.meanf, d.stdf = pp["lnf_g"], pp["lnf_b"], ptr(rep), ptr(meanf), ptr(stdf)
-        d.B, d.T, d.H, d.V, d.L = B, T, H, self.V, L
-        d.sqrtH = float(np.sqrt(np.float32(H)))
-        d.sqrt_dh = float(np.sqrt(np.float32(H // self.heads)))
-        d.d_emb = d0.c
-        for l in range(L):
-            p = "b%d." % l
-            n = lambda s: "%s%d%s" % (tag, l, s)   # noqa: E731
-            pruned = self.prune_last and l == L - 1
-            da = self._drop(step, site_attn(l), rate, training, self.heads * T * T)
-            d1 = self._drop(step, site_ffn1(l), rate, training, per_row)
-            d2 = self._drop(step, site_ffn2(l), rate, training, per_row)
-            drops += [(da, site_attn(l)), (d1, site_ffn1(l)), (d2, site_ffn2(l))]
-            M, sfx = (B, "L") if pruned else (rows, "")
-            kmask = self.buf(n("km"), (rows,), zero=True)
-            K, Vv = self.buf(n("K"), (rows, H), zero=True), self.buf(n("V"), (rows, H), zero=True)
-            q_in = self.buf(n("qin" + sfx), (M, H), zero=True)
-            mean1, std1, qmask = self.buf(n("m1" + sfx), (M,), zero=True), self.buf(n("s1" + sfx), (M,), zero=True), self.buf(n("qm" + sfx), (M,), zero=True)
-            Q, x1, y = self.buf(n("Q" + sfx), (M, H), zero=True), self.buf(n("x1" + sfx), (M, H), zero=True), self.buf(n("y" + sfx), (M, H), zero=True)
-            Pm = self.buf(n("P" + sfx), (B * T if pruned else rows * 64,), zero=True)
-            mean2, std2 = self.buf(n("m2" + sfx), (M,), zero=True), self.buf(n("s2" + sfx), (M,), zero=True)
-            h1d, x2 = self.buf(n("h1" + sfx), (M, H), zero=True), self.buf(n("x2" + sfx), (M, H), zero=True)
-            k = d.blk[l]
-            for i, w in enumerate(("wq", "wk", "wv", "w1", "w2")):
-                k.w[i] = self.wbf.data_ptr() + self._widx[p + w] * self._wplane
-            for i, bn in enumerate(("bq", "bk", "bv", "b1", "b2")):
-                k.bias[i] = pp[p + bn]
-            k.ln1_g, k.ln1_b, k.ln2_g, k.ln2_b = pp[p + "ln1_g"], pp[p + "ln1_b"], pp[p + "ln2_g"], pp[p + "ln2_b"]
-            k.q_in, k.mean1, k.std1, k.kmask, k.qmask = ptr(q_in), ptr(mean1), ptr(std1), ptr(kmask), ptr(qmask)
-            k.Q, k.K, k.V, k.P, k.x1, k.y = ptr(Q), ptr(K), ptr(Vv), ptr(Pm), ptr(x1), ptr(y)
-            k.mean2, k.std2, k.h1d, k.x2 = ptr(mean2), ptr(std2), ptr(h1d), ptr(x2)
-            k.d_attn, k.d_ffn1, k.d_ffn2 = da.c, d1.c, d2.c
-            k.pruned = 1 if pruned else 0
-            A[l] = dict(pruned=pruned, x=x, q_in=q_in, mean1=mean1, std1=std1, kmask=kmask, qmask=qmask, Q=Q, K=K, V=Vv, P=Pm,
-                        x1=x1, y=y, mean2=mean2, std2=std2, h1d=h1d, da=da, d1=d1, d2=d2)
-            x = x2
+        d, A, drops = self._stack_desc(tag, seq, rows, lambda pruned: B * T if pruned else rows * 64, training, rate, step)
+        A["pack"] = pk
         call("ader_seqp_fwd", ctypes.byref(d), pk["ref"], pk["max_tiles"], self._stream())
-        A.update(xL=x, rep=rep, meanf=meanf, stdf=stdf)
         if save:
             self._act = A
         if self.cache_descriptors:
             self._dc_put(ck, (d, A, pk, drops, pk["plan_args"]))
-        return rep
+        return A["rep"]
 
     def _lnf_desc(self, B):
         """AderLnfBwd of the forward just saved (prune_last: xL / meanf / stdf are compact [B, ..]), or None when not fused."""
