@@ -6,7 +6,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr
-from .common import EPI_ADD, EPI_BIAS, EPI_RELUDROPGRAD, _check
+from .common import EPI_ADD, EPI_BIAS, EPI_RELUDROPGRAD, HP, TableJob, _check, flash_sizes
 
 
 class _Backward:
@@ -72,16 +72,24 @@ class _Backward:
             Md = VP(*[(it[5]["hdr"].data_ptr() + 4 if it[5] is not None else None) for it in q])
             Tr = VP(*[(it[5]["trows"].data_ptr() if it[5] is not None else None) for it in q])
             slabs = call("ader_gemm_atb_batch_slabs", Mp, n)
-            slab = self.buf("atb_slab", (slabs * 160 * 160,))
+            slab = self.buf("atb_slab", (slabs * HP * HP,))
             call("ader_gemm_atb_x3_batch_pk", VP(*[it[0].data_ptr() for it in q]), VP(*[it[1].data_ptr() for it in q]),
                  VP(*[it[2] for it in q]), VP(*[it[3] for it in q]), Ms, Mp, Md, Tr, n, ptr(slab), self.H, self._stream())
             return
         slabs = call("ader_gemm_atb_batch_slabs", Ms, n)
-        slab = self.buf("atb_slab", (slabs * 160 * 160,))
+        slab = self.buf("atb_slab", (slabs * HP * HP,))
         call("ader_gemm_atb_x3_batch", VP(*[it[0].data_ptr() for it in q]), VP(*[it[1].data_ptr() for it in q]),
              VP(*[it[2] for it in q]), VP(*[it[3] for it in q]), Ms, n, ptr(slab), self.H, self._stream())
 
     # ---------------------------------------------------------------------------------------- loss rows
+    def _flash_ws(self, z):
+        """Workspace of the flash logit forward for the sizes z (common.flash_sizes); rep_lo: x3 only, pO2: a distilled step's only."""
+        rep_bf = self.buf("lbf_rep", (z.plane,), torch.bfloat16)
+        rep_lo = self.buf("lbf_rep_lo", (z.plane,), torch.bfloat16) if self.lx3 else None
+        part = self.buf("lbf_pm", (z.pm,)), self.buf("lbf_pl", (z.pl,)), self.buf("lbf_pO", (z.pO,))
+        pO2 = self.buf("lbf_pO2", (z.pO2,)) if z.pO2 else None
+        return rep_bf, rep_lo, part, pO2, self.buf("lg_lse", (z.row,)), self.buf("lbf_off", (z.row,)), self.buf("lg_rowloss", (z.row,))
+
     def _rowinfo(self, B, pos, n_train, ex_pos, ex_trow, N, Np, w_train, w_ex, teacher, tag="ri_"):
         Bp = (B + 63) // 64 * 64
         st = self._stream()
@@ -215,12 +223,7 @@ class _Backward:
         drep = self.buf("drep", (B, H))
         extra = None
         if use_bf16:
-            R = call("ader_lbf_ranges", N, Bp)
-            rep_bf = self.buf("lbf_rep", (Bp * 168,), torch.bfloat16)
-            rep_lo = self.buf("lbf_rep_lo", (Bp * 168,), torch.bfloat16) if self.lx3 else None
-            pm, pl = self.buf("lbf_pm", (R * Bp,)), self.buf("lbf_pl", (R * Bp,))
-            pO = self.buf("lbf_pO", (R * Bp * 160,))
-            lse, off, rowloss = self.buf("lg_lse", (Bp,)), self.buf("lbf_off", (Bp,)), self.buf("lg_rowloss", (Bp,))
+            rep_bf, rep_lo, (pm, pl, pO), _, lse, off, rowloss = self._flash_ws(flash_sizes(call("ader_lbf_ranges", N, Bp), Bp))
             with self._sec("logits_fwd"):
                 if self.lx3:
                     # the loss scalar feeds nothing in the backward pass: with the fused update deferred, its (single-workgroup) sum
@@ -249,7 +252,7 @@ class _Backward:
                     call("ader_logits_loss_fwd", ptr(rep_x), emb, n_ex, Bpx, H, N, *rix, ptr(part), ptr(lse_x), ptr(rowloss_x),
                          ptr(loss_x), st)
                     ranges = call("ader_logits_ranges", N, Bpx)
-                    slab = self.buf("lg_slab", (ranges * Bpx * 160,))
+                    slab = self.buf("lg_slab", (ranges * Bpx * HP,))
                     call("ader_logits_bwd_drep", ptr(rep_x), emb, n_ex, Bpx, H, N, *rix, ptr(lse_x), ptr(slab), ptr(drep_x), st)
                     call("ader_logits_bwd_demb", ptr(rep_x), emb, n_ex, Bpx, H, N, *rix, ptr(lse_x), ptr(demb), st)
                     self.loss.add_(loss_x)
@@ -267,7 +270,7 @@ class _Backward:
             with self._sec("logits_fwd"):
                 call("ader_logits_loss_fwd", ptr(rep), emb, B, Bp, H, N, *ri, ptr(part), ptr(lse), ptr(rowloss), ptr(self.loss), st)
             ranges = call("ader_logits_ranges", N, Bp)
-            slab = self.buf("lg_slab", (ranges * Bp * 160,))
+            slab = self.buf("lg_slab", (ranges * Bp * HP,))
             with self._sec("logits_bwd_drep"):
                 call("ader_logits_bwd_drep", ptr(rep), emb, B, Bp, H, N, *ri, ptr(lse), ptr(slab), ptr(drep), st)
             with self._sec("logits_bwd_demb"):
@@ -279,8 +282,7 @@ class _Backward:
         if sx.early is not None:
             sx.dp_rows = (seq, dx)                            # per-position input-gradient rows: exchanged and scattered in the hook
         if defer:
-            sx.deferred = dict(seq=seq, g=dx, B=(n_train if split_kd else B), Bp=Bp, N=N, rep_bf=rep_bf, rep_lo=rep_lo, off=off,
-                                  lab=lab, wrow=wrow, extra=extra)
+            sx.deferred = TableJob(rep_bf, rep_lo, n_train if split_kd else B, Bp, N, off, lab, wrow, dx, seq, extra)
         return self.loss
 
     def _loss_and_grad_kd_fast(self, seq, pos, rep, n_train, n_ex, N, Np, teacher, ex_trow, w_train, w_ex, fused=True):
@@ -288,7 +290,7 @@ class _Backward:
         exemplar rows padded to 128]; ader_lbf_fwd_kd gives the student log-sum-exp of every row (exemplar rows: over the first Np
         items), the softmax-weighted readout O1 and, for exemplar rows, the teacher readout O2 = sum_j softmax(t)_j E_j, from which
         loss = w (lse - rep.O2) and dRep = w (O1/l - O2); the table gradient w (softmax(s) - softmax(t))^T rep is formed inside the
-        fused update (ader_tab_update_sh_kd), which reads the teacher tile a second time.  Nothing [rows, N]-sized is materialised."""
+        fused update (issue_table_job), which reads the teacher tile a second time.  Nothing [rows, N]-sized is materialised."""
         st = self._stream()
         sx = self._step
         H = self.H
@@ -302,11 +304,7 @@ class _Backward:
             R, R2 = call("ader_lbf_ranges", N, Bp), call("ader_lx3_readout_ranges", Np, Bk)
         else:
             R, R2 = call("ader_lbf_ranges_kd", N, Bp, Bt), call("ader_lbf_readout_ranges", N, Bp, Bt)
-        rep_bf = self.buf("lbf_rep", (Bp * 168,), torch.bfloat16)
-        rep_lo = self.buf("lbf_rep_lo", (Bp * 168,), torch.bfloat16) if self.lx3 else None
-        pm, pl = self.buf("lbf_pm", (R * Bp,)), self.buf("lbf_pl", (R * Bp,))
-        pO, pO2 = self.buf("lbf_pO", (R * Bp * 160,)), self.buf("lbf_pO2", (R2 * Bk * 160,))
-        lse, off, rowloss = self.buf("lg_lse", (Bp,)), self.buf("lbf_off", (Bp,)), self.buf("lg_rowloss", (Bp,))
+        rep_bf, rep_lo, (pm, pl, pO), pO2, lse, off, rowloss = self._flash_ws(flash_sizes(R, Bp, R2, Bk))
         drep = self.buf("drep", (B, H))
         with self._sec("logits_fwd"):
             if self.lx3:
@@ -341,8 +339,8 @@ class _Backward:
             return self.loss
         self._lists_async(seq, lab, N)            # one-hot targets in the padded row numbering (label 0 = none)
         dx = self._blocks_backward(seq, drep, True, None)
-        sx.deferred = dict(seq=seq, g=dx, B=Bp, Bp=Bp, N=N, rep_bf=rep_bf, rep_lo=rep_lo, off=off, lab=lab, wrow=wrow, extra=None,
-                              kd=dict(row0=Bt, Np=Np, teacher=teacher, trow=trow, tlse2=tlse2))
+        sx.deferred = TableJob(rep_bf, rep_lo, Bp, Bp, N, off, lab, wrow, dx, seq, kd_row0=Bt, Np=Np, teacher=teacher, trow=trow,
+                               tlse2=tlse2)
         return self.loss
 
     def _blocks_backward(self, seq, drep, defer, demb, late=False):
@@ -356,7 +354,7 @@ class _Backward:
         st = self._stream()
         tb = self._sec("blocks_bwd")
         tb.__enter__()
-        wslab = self.buf("w_slab", (max(call("ader_gemm_atb_slabs", rows) * 160 * 160, call("ader_ln_bwd_slabs", rows) * 2 * H),))
+        wslab = self.buf("w_slab", (max(call("ader_gemm_atb_slabs", rows) * HP * HP, call("ader_ln_bwd_slabs", rows) * 2 * H),))
         pp, gp = self._pp, self._gp
         xL = A["xL"]
         pk = A.get("pack")

@@ -1,5 +1,6 @@
 """Shared pieces of the engine modules: epilogue / dropout-site ids, the host half of the dropout counter spec, the HIP-event section
 timer, the flat parameter layout and the side-stream probe."""
+import collections
 import ctypes
 import time as _time
 
@@ -7,6 +8,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._lib import call, ptr
 
 EPI_BIAS, EPI_BIAS_RELU_DROP, EPI_BIAS_DROP_RES_MASK, EPI_RELUDROPGRAD, EPI_ADD = range(5)
 SITE_EMB = 0
@@ -91,7 +93,7 @@ class StepState:
                  "dp_rows", "density", "keep_density", "held")
 
     def __init__(self):
-        self.deferred = None        # fused update still owed: the operands loss_and_grad(_defer_table=True) leaves for _fused_table_adam*
+        self.deferred = None        # the fused update still owed, a TableJob: loss_and_grad(_defer_table=True) -> _fused_table_adam*
         # (rowloss, rows) of the loss sum that rides beside the table update.  SURVIVES: if the fused update never ran, the next entry
         # point settles it (loss_and_grad)
         self.pending_loss = None
@@ -109,6 +111,64 @@ class StepState:
         # re-enters with the device copy of that batch
         self.density, self.keep_density = None, False
         self.held = None            # SURVIVES: inputs of a replayed step, alive until the next step is enqueued behind it (_plan_run)
+
+
+class TableJob:
+    """A fused table update that is owed (issue_table_job): of the local batch (StepState.deferred), or of the all-gathered global one.
+    "Padded rows": the logit forward's layout, the batch padded to 128 -- distilled: [train rows padded | exemplar rows padded]."""
+    __slots__ = ("hi", "lo", "B", "Bp", "N", "off", "lab", "wrow", "g", "seq", "extra", "kd_row0", "Np", "teacher", "trow", "tlse2")
+
+    def __init__(self, hi, lo, B, Bp, N, off, lab, wrow, g, seq, extra=None, kd_row0=0, Np=0, teacher=None, trow=None, tlse2=None):
+        self.hi, self.lo = hi, lo   # bf16 operand planes [Bp, LDR] by padded row; lo = None: bf16 logits (one plane)
+        self.B, self.Bp, self.N = B, Bp, N      # real rows (not read when distilled), padded rows; items 1..N are updated
+        self.off, self.lab, self.wrow = off, lab, wrow      # [Bp] by padded row: exponent offset, 1-based label (0 = none), loss weight
+        # g [n, H], seq [n]: gradient rows of the input embeddings and their item ids (0 = padding) by position, row * T + t (packed
+        # catalog exchange: the rows a rank received, by (source, position)); extra: dense table gradient [V, H] by item (split-kd), or None
+        self.g, self.seq, self.extra = g, seq, extra
+        # distilled (None / 0: not): padded rows [kd_row0, Bp) are exemplar rows; their softmax runs over items 1..Np against
+        # teacher [*, Np] (by teacher row); trow [Bp] = teacher row of a padded row (-1 = none), tlse2 [Bp] = its log2-domain lse
+        self.kd_row0, self.Np, self.teacher, self.trow, self.tlse2 = kd_row0, Np, teacher, trow, tlse2
+
+
+def issue_table_job(job, lists, table, item_num, H, shadow, rep_img, lr_t, b1, b2, eps, stream, tile_begin=0, tile_count=-1, bf16="sh"):
+    """Launch the fused table update of `job`: picks the launcher of include/ader_hip.h and marshals its arguments.  lists: the
+    7-tuple of Engine._sparse_lists; table: (theta, adam_m, adam_v) tensors that start at table row 0; rep_img: the operand images
+    of an x3 job (job.lo given), shadow: the bf16 table of a bf16 job; tiles [tile_begin, tile_begin + tile_count): a rank's 128-item
+    tiles (tile_count < 0: all); bf16 = "sh" | "resident": the bf16 kernel (the resident one has no distilled form: the shadow kernel)."""
+    ids, order, sp_start, tids, torder, tg_start, tmeta = lists
+    x3, kd, ranged = job.lo is not None, job.teacher is not None, tile_count >= 0
+    _check(kd or not job.kd_row0, "table job: kd_row0 without a teacher")
+    _check(not kd or (job.trow is not None and job.tlse2 is not None and job.extra is None and (x3 or not ranged)),
+           "table job: a distilled update needs trow and tlse2, takes no dense extra gradient and, with bf16 logits, no tile range")
+    _check(bf16 in ("sh", "resident") and (rep_img if x3 else shadow) is not None, "table job: bf16 form / second operand missing")
+    bucketed = not x3 and (kd or bf16 == "sh")      # the shadow kernels address the lists through their 64-id bucket offsets
+    if x3:
+        name = ("ader_tab_update_x3_kd_range" if ranged else "ader_tab_update_x3_kd") if kd else "ader_tab_update_x3"
+    else:
+        name = ("ader_tab_update_sh_kd" if kd else "ader_tab_update_sh") if bucketed else "ader_tab_update"
+    scale = float(np.sqrt(np.float32(H)))           # float32 sqrt(H) (ADER.py:38), not the double one
+    head = (ptr(job.hi), ptr(job.lo), ptr(rep_img)) if x3 else (ptr(job.hi), ptr(shadow))
+    dims = (item_num, job.Bp, job.kd_row0, H, job.N, job.Np) if kd else (item_num, job.B, job.Bp, H, job.N)
+    sps, tgs, meta = ((ptr(sp_start),), (ptr(tg_start),), ()) if bucketed else ((), (), (ptr(tmeta),))
+    sparse = (ptr(job.off), ptr(ids), ptr(order), *sps, ids.numel(), ptr(job.g), scale, ptr(tids), ptr(torder), *tgs, tids.numel(),
+              *meta, ptr(job.wrow))
+    teach = (ptr(job.teacher), job.teacher.stride(0), ptr(job.trow), ptr(job.tlse2)) if kd else ()
+    adam = (ptr(table[0]), ptr(table[1]), ptr(table[2]), lr_t, b1, b2, eps)
+    tail = ((tile_begin, tile_count) if ranged else ()) if kd else (tile_begin, tile_count, ptr(job.extra))
+    call(name, *head, *dims, *sparse, *teach, *adam, *tail, stream)
+
+
+LDR = 168           # bf16 elements of an operand-plane / shadow row (csrc/lbf_common.h)
+HP = 160            # padded hidden width: floats of a readout / slab row (csrc/lbf_common.h; gemm.hip and logits.hip define the same)
+PART_LD = 152       # floats of a shard partial {max, sum, O[H]} per row (csrc/logits_bf16.hip)
+X3_IMG_ROW_B = 22528 // 32      # x3 operand image bytes per batch row: X3_IMG_B (csrc/x3_image.h) per X3_CH rows (csrc/table_update_x3.hip)
+FlashSizes = collections.namedtuple("FlashSizes", "plane pm pl pO pO2 row part")
+
+
+def flash_sizes(R, Bp, R2=0, Bk=0):
+    """Element counts of the flash-loss workspace (k_lx3p / k_lbf_combine write it) for Bp padded rows and R item ranges: an operand plane;
+    range partials pm, pl, pO; pO2: teacher readout of Bk exemplar rows over R2 ranges; a per-row vector; the shard partials."""
+    return FlashSizes(Bp * LDR, R * Bp, R * Bp, R * Bp * HP, R2 * Bk * HP, Bp, Bp * PART_LD)
 
 
 class SectionTimer:

@@ -1,8 +1,6 @@
 """Data parallel, replicated table: row-sharded fused table update."""
-import numpy as np
-import torch
-
 from .._lib import call, ptr
+from .common import TableJob
 
 
 class _DpReplicated:
@@ -25,33 +23,21 @@ class _DpReplicated:
         self._refresh_stream()
         D = self._step.deferred
         st = self._stream()
-        W, r, grp = self.dp_world, self.dp_rank, self.dp_group
-        H, B, Bp, N = self.H, D["B"], D["Bp"], D["N"]
+        W, r, grp, H = self.dp_world, self.dp_rank, self.dp_group, self.H
         lr_t = self._lr_t(lr)
-
-        def ag(t):                      # [W, *t.shape]; moved as raw bytes (any dtype, any backend)
-            t = t.contiguous()
-            out = torch.empty((W,) + tuple(t.shape), dtype=t.dtype, device=t.device)
-            self._guard("sharded-update:inputs", "all_gather", t.shape, t.dtype)
-            dist.all_gather_into_tensor(out.view(torch.uint8).view(-1), t.view(torch.uint8).view(-1), group=grp)
-            return out
-
+        ag = lambda t: self._ag(t, "sharded-update:inputs")      # noqa: E731  ([W, *t.shape])
         with self._sec("grad_exchange"):
-            rep_g, off_g = ag(D["rep_bf"]), ag(D["off"])
-            lab_g, w_g = ag(D["lab"]), ag(D["wrow"])
-            seq_g, g_g = ag(D["seq"]), ag(D["g"])
+            # the global batch: rank d's padded rows are rows [d * Bp, (d + 1) * Bp), its positions follow rank d - 1's
+            G = TableJob(ag(D.hi), None, W * D.Bp, W * D.Bp, D.N, ag(D.off), ag(D.lab), ag(D.wrow), seq=ag(D.seq), g=ag(D.g))
             span = self.layout["pos"][0]
             self._guard("sharded-update:small-gradients", "all_reduce", (self.P - span,), self.grad.dtype)
             dist.all_reduce(self.grad[span:], group=grp)
             self._guard("sharded-update:loss", "all_reduce", self.loss.shape, self.loss.dtype)
             dist.all_reduce(self.loss, group=grp)
-        ids, order, sp_start, tids, torder, tg_start, tmeta = self._sparse_lists(seq_g, lab_g, N)
+        lists = self._sparse_lists(G.seq, G.lab, G.N)
         tiles = self.shard_items // 128
         with self._sec("logits_bwd_adam"):
-            call("ader_tab_update_sh", ptr(rep_g), ptr(self.shadow), self.item_num, W * Bp, W * Bp, H, N, ptr(off_g),
-                 ptr(ids), ptr(order), ptr(sp_start), ids.numel(), ptr(g_g), float(np.sqrt(np.float32(H))), ptr(tids),
-                 ptr(torder), ptr(tg_start), tids.numel(), ptr(w_g), ptr(self.theta), ptr(self.adam_m), ptr(self.adam_v), lr_t,
-                 self.beta1, self.beta2, self.eps, r * tiles, tiles, None, st)
+            self._table_update(G, lists, lr_t, r * tiles, tiles)
         with self._sec("param_allgather"):
             S = self.shard_items * H
             table = self.theta[H:H + W * S]                       # rows 1 .. W*shard_items
@@ -60,10 +46,7 @@ class _DpReplicated:
             dist.all_gather_into_tensor(table, own, group=grp)
             if self.shadow is not None:                           # bf16 shadow rows of the other shards
                 call("ader_lbf_shadow_refresh", self._pp["emb"], ptr(self.shadow), self.V, H, st)
-        with self._sec("adam"):
-            call("ader_adam_step", self.theta.data_ptr() + 4 * span, self.adam_m.data_ptr() + 4 * span,
-                 self.adam_v.data_ptr() + 4 * span, self.grad.data_ptr() + 4 * span, self.P - span, lr_t, self.beta1, self.beta2,
-                 self.eps, None, 0, H, st)
+        self._small_adam(lr_t)
         self._step.deferred = None
         self._mv_sharded = True
         self._advance_adam()

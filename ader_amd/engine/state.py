@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr
-from .common import _NULL, StepState, _check, param_layout, side_stream
+from .common import _NULL, LDR, StepState, _check, param_layout, side_stream
 from .infer import _check_rank_dtype
 
 
@@ -51,8 +51,8 @@ class _State:
         self.adam_m = torch.zeros(self.P, **f32)
         self.adam_v = torch.zeros(self.P, **f32)
         self.grad = torch.zeros(self.P, **f32)
-        # bf16 shadow of the item table streamed by the bf16 logit GEMMs ([V][168], 336-B rows); Adam keeps it in sync
-        self.shadow = (torch.zeros(self.V_alloc * 168, dtype=torch.bfloat16, device=self.device)
+        # bf16 shadow of the item table streamed by the bf16 logit GEMMs ([V][LDR], 336-B rows); Adam keeps it in sync
+        self.shadow = (torch.zeros(self.V_alloc * LDR, dtype=torch.bfloat16, device=self.device)
                        if logits_dtype == "bf16" and hidden_units % 2 == 0 else None)
         # block GEMMs: "x3" = bf16 hi/lo split on the bf16 matrix cores (float32-grade accuracy), "f32" = exact f32 MFMA
         _check(gemm in ("x3", "f32"), "gemm must be 'x3' or 'f32' (got %r)" % (gemm,))

@@ -3,7 +3,7 @@ import numpy as np
 import torch
 
 from .._lib import call, ptr
-from .common import IN_LR, StepF
+from .common import IN_LR, StepF, issue_table_job
 
 
 class _Update:
@@ -76,26 +76,38 @@ class _Update:
         self._edge(self._main, self._side)       # (the lists live in persistent workspace buffers: no record_stream needed)
         return out
 
+    def _table_update(self, job, lists, lr_t, tile_begin=0, tile_count=-1, bf16="sh"):
+        """issue_table_job for this engine's table, on the current stream (the data-parallel updates always take the shadow kernel).  x3:
+        the operand rows go as the LDS images k_tab32x3 streams by LDS-DMA, cut here unless this step's logit forward did (img_ready)."""
+        img = self.buf("lbf_rep_img", (call("ader_x3_rep_image_bytes", job.Bp),), torch.uint8, zero=True) if self.lx3 else None
+        if self.lx3 and not self._step.img_ready:
+            call("ader_x3_rep_image", ptr(job.hi), ptr(job.lo), job.Bp, ptr(img), self._stream())
+        self._step.img_ready = False
+        issue_table_job(job, lists, (self.theta, self.adam_m, self.adam_v), self.item_num, self.H, self.shadow, img, lr_t, self.beta1,
+                        self.beta2, self.eps, self._stream(), tile_begin, tile_count, bf16)
+
+    def _small_adam(self, lr_t):
+        """Adam on every parameter behind the item table: the flat kernel on the tail of the buffer, on the current stream."""
+        span = self.layout["pos"][0]
+        with self._sec("adam"):
+            call("ader_adam_step", self.theta.data_ptr() + 4 * span, self.adam_m.data_ptr() + 4 * span,
+                 self.adam_v.data_ptr() + 4 * span, self.grad.data_ptr() + 4 * span, self.P - span, lr_t, self.beta1,
+                 self.beta2, self.eps, None, 0, self.H, self._stream())
+
     def _fused_table_adam(self, lr):
         """Table rows 1..N: gradient GEMM + sparse terms + Adam in one pass (ader_lbf_bwd_adam); all other parameters:
         the flat Adam kernel on the tail of the buffer.  Rows 0 and > N have zero gradient and zero Adam state (the
         catalog only grows), so leaving them untouched equals the dense update."""
         sx = self._step
-        D, st = sx.deferred, self._stream()
-        H, T = self.H, self.T
         lr_t = self._lr_t(lr)
-        ids, order, sp_start, tids, torder, tg_start, tmeta = self._lists_wait()
-        span = self.layout["pos"][0]
+        lists = self._lists_wait()
 
         def small_update():     # everything that feeds / is the update of the non-table parameters
             if sx.pending_loss is not None:
                 self._settle_loss()
             self._flush_late()
             self._atb_flush()
-            with self._sec("adam"):
-                call("ader_adam_step", self.theta.data_ptr() + 4 * span, self.adam_m.data_ptr() + 4 * span,
-                     self.adam_v.data_ptr() + 4 * span, self.grad.data_ptr() + 4 * span, self.P - span, lr_t, self.beta1,
-                     self.beta2, self.eps, None, 0, H, self._stream())
+            self._small_adam(lr_t)
             self._advance_adam()
 
         main = self._main
@@ -109,39 +121,7 @@ class _Update:
             # (profiles/r5_packed/timeline_cfgY_update_late.txt)
             self._edge(self._side_lane(), main)
         with self._sec("logits_bwd_adam"):
-            if self.lx3:        # operand rows as the LDS images k_tab32x3 streams by LDS-DMA
-                img = self.buf("lbf_rep_img", (call("ader_x3_rep_image_bytes", D["Bp"]),), torch.uint8, zero=True)
-                if not sx.img_ready:
-                    call("ader_x3_rep_image", ptr(D["rep_bf"]), ptr(D["rep_lo"]), D["Bp"], ptr(img), st)
-                sx.img_ready = False
-            if self.lx3 and D.get("kd"):
-                K = D["kd"]
-                call("ader_tab_update_x3_kd", ptr(D["rep_bf"]), ptr(D["rep_lo"]), ptr(img), self.item_num, D["Bp"], K["row0"], H, D["N"],
-                     K["Np"], ptr(D["off"]), ptr(ids), ptr(order), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))), ptr(tids),
-                     ptr(torder), tids.numel(), ptr(tmeta), ptr(D["wrow"]), ptr(K["teacher"]), K["teacher"].stride(0), ptr(K["trow"]),
-                     ptr(K["tlse2"]), ptr(self.theta), ptr(self.adam_m), ptr(self.adam_v), lr_t, self.beta1, self.beta2, self.eps, st)
-            elif self.lx3:
-                call("ader_tab_update_x3", ptr(D["rep_bf"]), ptr(D["rep_lo"]), ptr(img), self.item_num, D["B"], D["Bp"], H, D["N"],
-                     ptr(D["off"]), ptr(ids), ptr(order), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))), ptr(tids),
-                     ptr(torder), tids.numel(), ptr(tmeta), ptr(D["wrow"]), ptr(self.theta), ptr(self.adam_m), ptr(self.adam_v), lr_t,
-                     self.beta1, self.beta2, self.eps, 0, -1, ptr(D.get("extra")), st)
-            elif self.bf16_update == "resident" and not D.get("kd"):
-                call("ader_tab_update", ptr(D["rep_bf"]), ptr(self.shadow), self.item_num, D["B"], D["Bp"], H, D["N"],
-                     ptr(D["off"]), ptr(ids), ptr(order), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))), ptr(tids),
-                     ptr(torder), tids.numel(), ptr(tmeta), ptr(D["wrow"]), ptr(self.theta), ptr(self.adam_m), ptr(self.adam_v), lr_t,
-                     self.beta1, self.beta2, self.eps, 0, -1, ptr(D.get("extra")), st)
-            elif D.get("kd"):
-                K = D["kd"]
-                call("ader_tab_update_sh_kd", ptr(D["rep_bf"]), ptr(self.shadow), self.item_num, D["Bp"], K["row0"], H, D["N"], K["Np"],
-                     ptr(D["off"]), ptr(ids), ptr(order), ptr(sp_start), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))),
-                     ptr(tids), ptr(torder), ptr(tg_start), tids.numel(), ptr(D["wrow"]), ptr(K["teacher"]), K["teacher"].stride(0),
-                     ptr(K["trow"]), ptr(K["tlse2"]), ptr(self.theta), ptr(self.adam_m), ptr(self.adam_v), lr_t, self.beta1, self.beta2,
-                     self.eps, st)
-            else:
-                call("ader_tab_update_sh", ptr(D["rep_bf"]), ptr(self.shadow), self.item_num, D["B"], D["Bp"], H, D["N"],
-                     ptr(D["off"]), ptr(ids), ptr(order), ptr(sp_start), ids.numel(), ptr(D["g"]), float(np.sqrt(np.float32(H))),
-                     ptr(tids), ptr(torder), ptr(tg_start), tids.numel(), ptr(D["wrow"]), ptr(self.theta), ptr(self.adam_m),
-                     ptr(self.adam_v), lr_t, self.beta1, self.beta2, self.eps, 0, -1, ptr(D.get("extra")), st)
+            self._table_update(sx.deferred, lists, lr_t, bf16=self.bf16_update)
         if overlap:
             with self._OnStream(self, self._side):
                 small_update()

@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
+from .engine.common import HP, LDR, X3_IMG_ROW_B, TableJob, flash_sizes, issue_table_job
 
 _lib.load()
 
@@ -98,7 +99,7 @@ def logits_ce_fwd(rep: torch.Tensor, shadow: torch.Tensor, labels: torch.Tensor,
     _chk(rep, "rep", torch.float32, 2), _chk(shadow, "shadow", torch.bfloat16, 1)
     _chk(labels, "labels", torch.int32, 1), _chk(weights, "weights", torch.float32, 1)
     B, H = rep.shape
-    item_num = shadow.numel() // 168 - 1
+    item_num = shadow.numel() // LDR - 1
     if not (1 <= N <= item_num) or labels.shape[0] != B or weights.shape[0] != B or H % 2:
         raise RuntimeError("ader::logits_ce_fwd: bad shapes (N=%d, item_num=%d, B=%d)" % (N, item_num, B))
     _check_labels(labels, "logits_ce_fwd labels", N)
@@ -106,10 +107,9 @@ def logits_ce_fwd(rep: torch.Tensor, shadow: torch.Tensor, labels: torch.Tensor,
     dev = rep.device
     lab, w = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, device=dev)
     lab[:B], w[:B] = labels, weights
-    R = call("ader_lbf_ranges", N, Bp)
-    rep_bf = torch.empty(Bp * 168, dtype=torch.bfloat16, device=dev)
-    pm, pl, pO = torch.empty(R * Bp, device=dev), torch.empty(R * Bp, device=dev), torch.empty(R * Bp * 160, device=dev)
-    lse, off, rowloss = torch.empty(Bp, device=dev), torch.empty(Bp, device=dev), torch.empty(Bp, device=dev)
+    z = flash_sizes(call("ader_lbf_ranges", N, Bp), Bp)
+    rep_bf = torch.empty(z.plane, dtype=torch.bfloat16, device=dev)
+    pm, pl, pO, lse, off, rowloss = (torch.empty(n, device=dev) for n in (z.pm, z.pl, z.pO, z.row, z.row, z.row))
     loss, drep = torch.zeros(1, device=dev), torch.empty(B, H, device=dev)
     call("ader_lbf_fwd", ptr(rep), ptr(shadow), item_num, B, Bp, H, N, ptr(lab), ptr(w), ptr(rep_bf), ptr(pm), ptr(pl), ptr(pO),
          ptr(lse), ptr(off), ptr(rowloss), ptr(loss), ptr(drep), _st())
@@ -168,7 +168,7 @@ def rank_of_target_x3(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor
     tgt, ncol = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, dtype=torch.int32, device=dev)
     tgt[:B], ncol[:B] = target, N
     tl, delta, emax = torch.empty(Bp, device=dev), torch.empty(Bp, device=dev), torch.empty(1, device=dev)
-    rep_hi, rep_lo = (torch.empty(Bp * 168, dtype=torch.bfloat16, device=dev) for _ in range(2))
+    rep_hi, rep_lo = (torch.empty(Bp * LDR, dtype=torch.bfloat16, device=dev) for _ in range(2))
     cap = RANK_X3_CAND_PER_ROW * Bp
     cand, diag = torch.empty(3 * cap, dtype=torch.int32, device=dev), torch.empty(2, dtype=torch.int32, device=dev)
     rk = torch.empty(Bp, dtype=torch.int32, device=dev)
@@ -256,7 +256,7 @@ def _drop(key, thr, scale):
 def _atb(A, G):
     """dW = A^T G [H,H], db = colsum(G) [H]"""
     M, H = A.shape
-    slab = torch.empty(call("ader_gemm_atb_slabs", M) * 160 * 160, device=A.device)
+    slab = torch.empty(call("ader_gemm_atb_slabs", M) * HP * HP, device=A.device)
     dW, db = torch.empty(H, H, device=A.device), torch.empty(H, device=A.device)
     call("ader_gemm_atb", ptr(A), ptr(G), ptr(slab), ptr(dW), ptr(db), M, H, _st())
     return dW, db
@@ -537,7 +537,7 @@ def logits_ce_bwd(rep: torch.Tensor, emb: torch.Tensor, labels: torch.Tensor, we
     Bp, lab, ncol, w, trow, tlse = _rowinfo(labels, weights, N, dev)
     lse_p = torch.zeros(Bp, device=dev)
     lse_p[:B] = lse
-    slab = torch.empty(call("ader_logits_ranges", N, Bp) * Bp * 160, device=dev)
+    slab = torch.empty(call("ader_logits_ranges", N, Bp) * Bp * HP, device=dev)
     drep, demb = torch.empty(B, H, device=dev), torch.zeros_like(emb)
     call("ader_logits_bwd_drep", ptr(rep), ptr(emb), B, Bp, H, N, ptr(lab), ptr(ncol), ptr(w), ptr(trow), ptr(tlse), None, 0,
          ptr(lse_p), ptr(slab), ptr(drep), _st())
@@ -618,10 +618,9 @@ def check_status():
 
 
 def _x3_fwd_scratch(N, Bp, dev):
-    R = call("ader_lbf_ranges", N, Bp)
-    bf = dict(dtype=torch.bfloat16, device=dev)
-    return (torch.empty(Bp * 168, **bf), torch.empty(Bp * 168, **bf), torch.empty(R * Bp, device=dev), torch.empty(R * Bp, device=dev),
-            torch.empty(R * Bp * 160, device=dev), torch.empty(Bp, device=dev), torch.empty(Bp, device=dev), torch.empty(Bp, device=dev))
+    z = flash_sizes(call("ader_lbf_ranges", N, Bp), Bp)
+    return (*(torch.empty(z.plane, dtype=torch.bfloat16, device=dev) for _ in range(2)),
+            *(torch.empty(n, device=dev) for n in (z.pm, z.pl, z.pO, z.row, z.row, z.row)))
 
 
 @torch.library.custom_op("ader::logits_ce_x3", mutates_args=())
@@ -663,9 +662,10 @@ def logits_ce_x3(rep: torch.Tensor, emb: torch.Tensor, pos: torch.Tensor, ex_pos
 def _(rep, emb, pos, ex_pos, N, w_train, w_ex):
     B = rep.shape[0]
     Bp = (B + 127) // 128 * 128
-    bf = rep.new_empty(Bp * 168, dtype=torch.bfloat16)
+    bf = rep.new_empty(flash_sizes(0, Bp).plane, dtype=torch.bfloat16)
+    # (the image: X3_IMG_B bytes per chunk of 32 rows, csrc/x3_image.h -- what ader_x3_rep_image_bytes(Bp) returns)
     return (rep.new_empty(1), rep.new_empty(B), torch.empty_like(rep), bf, torch.empty_like(bf), rep.new_empty(Bp),
-            pos.new_empty(Bp), rep.new_empty(Bp), rep.new_empty(Bp * 704, dtype=torch.uint8))
+            pos.new_empty(Bp), rep.new_empty(Bp), rep.new_empty(Bp * X3_IMG_ROW_B, dtype=torch.uint8))
 
 
 def _x3_setup(ctx, inputs, output):
@@ -710,7 +710,7 @@ def logits_ce_x3_kd(rep: torch.Tensor, emb: torch.Tensor, pos: torch.Tensor, ex_
     lab, trow = torch.empty(Bp, **i32), torch.empty(Bp, **i32)
     wrow, tlse2 = torch.empty(Bp, device=dev), torch.empty(Bp, device=dev)
     rep_hi, rep_lo, pm, pl, pO, lse, off, rowloss = _x3_fwd_scratch(N, Bp, dev)
-    pO2 = torch.empty(call("ader_lx3_readout_ranges", Np, Bk) * Bk * 160, device=dev)
+    pO2 = torch.empty(flash_sizes(0, Bp, call("ader_lx3_readout_ranges", Np, Bk), Bk).pO2, device=dev)
     loss, drep = torch.zeros(1, device=dev), torch.empty(B, H, device=dev)
     call("ader_lx3_fwd_kd", ptr(rep), ptr(emb), item_num, n_train, n_ex, Bt, Bp, H, N, Np, ptr(pos), ptr(ex_trow), ptr(teacher),
          teacher.stride(0), ptr(tlse_all), float(w_train), float(w_ex), ptr(lab), ptr(wrow), ptr(trow), ptr(tlse2), ptr(rep_hi),
@@ -723,7 +723,7 @@ def logits_ce_x3_kd(rep: torch.Tensor, emb: torch.Tensor, pos: torch.Tensor, ex_
 def _(rep, emb, pos, ex_trow, teacher, N, w_train, w_ex):
     B = rep.shape[0]
     Bp = (pos.shape[0] + 127) // 128 * 128 + (ex_trow.shape[0] + 127) // 128 * 128
-    bf = rep.new_empty(Bp * 168, dtype=torch.bfloat16)
+    bf = rep.new_empty(flash_sizes(0, Bp).plane, dtype=torch.bfloat16)
     return (rep.new_empty(1), rep.new_empty(B), torch.empty_like(rep), bf, torch.empty_like(bf), rep.new_empty(Bp), pos.new_empty(Bp),
             rep.new_empty(Bp), pos.new_empty(Bp), rep.new_empty(Bp))
 
@@ -745,7 +745,7 @@ def _sparse_lists_x3(seq, lab, N):
          ptr(tg_start), _st())
     meta = torch.empty(call("ader_tab_meta_ints", N), **i32)
     call("ader_tab_tile_meta", ptr(ids), ptr(order), ptr(sp_start), ptr(tids), ptr(torder), ptr(tg_start), N, ptr(meta), _st())
-    return ids, order, tids, torder, meta
+    return ids, order, sp_start, tids, torder, tg_start, meta
 
 
 def _chk_table(emb, m, v, seq, g_rows, name):
@@ -769,10 +769,8 @@ def table_update_x3(emb: torch.Tensor, m: torch.Tensor, v: torch.Tensor, seq: to
     Bp = off.shape[0]
     if not (0 < n_rows <= Bp) or seq.shape[0] != n_rows:
         raise RuntimeError("ader::table_update_x3: n_rows must be the batch's row count (seq rows = %d, Bp = %d)" % (seq.shape[0], Bp))
-    ids, order, tids, torder, meta = _sparse_lists_x3(seq, lab, N)
-    call("ader_tab_update_x3", ptr(rep_hi), ptr(rep_lo), ptr(img), emb.shape[0] - 1, n_rows, Bp, H, N, ptr(off), ptr(ids), ptr(order),
-         ids.numel(), ptr(g_rows), _sqrt_f32(H),
-         ptr(tids), ptr(torder), tids.numel(), ptr(meta), ptr(wrow), ptr(emb), ptr(m), ptr(v), lr_t, beta1, beta2, eps, 0, -1, None, _st())
+    job = TableJob(rep_hi, rep_lo, n_rows, Bp, N, off, lab, wrow, g_rows, seq)
+    issue_table_job(job, _sparse_lists_x3(seq, lab, N), (emb, m, v), emb.shape[0] - 1, H, None, img, lr_t, beta1, beta2, eps, _st())
 
 
 @torch.library.custom_op("ader::table_update_x3_kd", mutates_args=("emb", "m", "v"))
@@ -789,8 +787,6 @@ def table_update_x3_kd(emb: torch.Tensor, m: torch.Tensor, v: torch.Tensor, seq:
     Bt = (n_train + 127) // 128 * 128
     img = torch.zeros(call("ader_x3_rep_image_bytes", Bp), dtype=torch.uint8, device=emb.device)
     call("ader_x3_rep_image", ptr(rep_hi), ptr(rep_lo), Bp, ptr(img), _st())
-    ids, order, tids, torder, meta = _sparse_lists_x3(seq, lab, N)
-    call("ader_tab_update_x3_kd", ptr(rep_hi), ptr(rep_lo), ptr(img), emb.shape[0] - 1, Bp, Bt, H, N, teacher.shape[1], ptr(off), ptr(ids),
-         ptr(order), ids.numel(), ptr(g_rows), _sqrt_f32(H), ptr(tids), ptr(torder),
-         tids.numel(), ptr(meta), ptr(wrow), ptr(teacher), teacher.stride(0), ptr(trow), ptr(tlse2), ptr(emb), ptr(m), ptr(v), lr_t, beta1,
-         beta2, eps, _st())
+    job = TableJob(rep_hi, rep_lo, Bp, Bp, N, off, lab, wrow, g_rows, seq, kd_row0=Bt, Np=teacher.shape[1], teacher=teacher, trow=trow,
+                   tlse2=tlse2)
+    issue_table_job(job, _sparse_lists_x3(seq, lab, N), (emb, m, v), emb.shape[0] - 1, H, None, img, lr_t, beta1, beta2, eps, _st())
