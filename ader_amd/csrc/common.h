@@ -34,6 +34,7 @@ template <auto Kern> static int ader_dyn_lds(size_t bytes) {
 
 // status bits written by kernels into the engine's status word
 #define ADER_ST_BAD_ID 1
+#define ADER_ST_BAD_TROW 2      // a teacher row index >= the number of stored teacher representations (ader_teacher_rows)
 
 // ---------------------------------------------------------------- counter-based dropout mask
 // keep(idx) = (lowbias32(idx ^ key) >> 8) >= thr ; key = f(seed, step, site) computed on the host.

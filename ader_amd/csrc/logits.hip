@@ -10,6 +10,7 @@
 //   k_logits_tile<RANK>  per-row count of items ranked before the target           (Evaluator, util.py:323-325)
 //   k_logits_tile<STORE> dense logits (teacher logits of selected exemplars, util.py:433; model.logits fetch)
 //   k_topk_tile/_merge   per-row best k items by (logit descending, id ascending), the STORE bits       (Engine.recommend)
+//   k_teacher_rows       the STORE bits of a step's exemplar rows from stored teacher representations  (TeacherRep, util.py:433)
 //   k_logits_bwd_drep    dRep[b,:] = sum_n dlogit[b,n] E[n,:]   (b-chunk x item-range workgroups, slabs)
 //   k_logits_bwd_de      dE[n,:]   = sum_b dlogit[b,n] rep[b,:] (item-tile workgroups; rows written once, no atomics)
 // with dlogit[b,n] = w_b * (softmax_b[n] - target_b[n]) for n < ncol_b, else 0.
@@ -624,6 +625,97 @@ __global__ __launch_bounds__(256) void k_topk_merge(TopkArgs a) {
     }
 }
 
+// ============================================================================================= teacher rows from stored representations
+// ader_teacher_rows: the teacher logits of one step's exemplar rows (util.py:433, consumed by ADER.py:134-135), regenerated from the
+// teacher's representations trep [E,H] and the item table as it stood when the teacher was taken, instead of being kept as an [E, Np]
+// tensor.  rows[e, n] is the float32 k_logits_tile<MODE_STORE> writes for representation trep[ex_trow[e]] against item n + 1: the same
+// [64][LDE] operand layout, the same mma_tile<2> call, the same ksteps -- and a (row, item) result of that chain does not depend on
+// which other rows or items share the tile, so the bits are the stored teacher's.  k_topk_tile's shape: workgroup = (64-row chunk,
+// contiguous range of 64-item tiles); the chunk's representations are gathered by ex_trow into LDS once, the range's table tiles
+// stream through E_l with the next tile's loads in flight (registers) under the current tile's MFMAs.  Every (row, item) is written by
+// exactly one lane: no atomics on floats, no reduction across workgroups.  Padding rows (ex_trow < 0, e >= n_ex) are written as 0.0f
+// whatever the table holds; a teacher row >= E is never read: the row is written as padding and the status word flagged.
+struct TeachArgs {
+    const float* trep;     // [E,H]
+    const float* emb1;     // snapshot table row 1 (item 1) : [N,H]
+    const int* ex_trow;    // [n_ex] teacher row or -1
+    int n_ex, Bk, E, H, N, ranges;
+    float* rows;           // [Bk, ldr]
+    long ldr;
+    int* trow_local;       // [Bk]
+    int* status;           // engine status word, or NULL
+};
+
+__global__ __launch_bounds__(512) void k_teacher_rows(TeachArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* E_l = smem;                                       // [TI][LDE]
+    float* R_l = E_l + TI * LDE;                             // [TB][LDE]
+    int* tr_l = (int*)(R_l + TB * LDE);                      // [TB] teacher row of the chunk's rows, -1 = padding
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int mw = wave & 3, nw = wave >> 2;
+    const int H = a.H, ksteps = (H + 3) >> 2;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int nchunk = a.Bk / TB;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int range = xcd + 8 * (slot / nchunk), bc = slot % nchunk;
+    if (range >= a.ranges) return;
+    const int nsub_total = (a.N + TI - 1) / TI;
+    const int s_begin = (int)((long)range * nsub_total / a.ranges), s_end = (int)((long)(range + 1) * nsub_total / a.ranges);
+    if (tid < TB) {
+        const int e = bc * TB + tid;
+        int t = (e < a.n_ex) ? a.ex_trow[e] : -1;
+        if (t >= a.E) { if (a.status) atomicOr(a.status, ADER_ST_BAD_TROW); t = -1; }
+        if (t < 0) t = -1;
+        tr_l[tid] = t;
+        if (range == 0) a.trow_local[e] = (t >= 0) ? e : -1;          // (range 0 exists for every chunk, with or without tiles)
+    }
+    __syncthreads();
+    for (int i = tid; i < 64 * LDE; i += 512) {                        // stage_tile's layout, the rows gathered
+        const int r = i / LDE, c = i - r * LDE;
+        const int t = tr_l[r];
+        R_l[i] = (t >= 0 && c < H) ? a.trep[(size_t)t * H + c] : 0.0f;
+    }
+    bool real[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) real[j] = tr_l[nw * 32 + j * 16 + r16] >= 0;
+    const bool vec_ok = (((uintptr_t)a.rows) & 15) == 0;               // (ldr % 4 == 0 and item0 % 4 == 0: a lane's 4 items are one 16-byte piece)
+    float pre[TOPK_STAGE_REGS];                                        // the next tile, in stage_tile's element order
+    auto load_tile = [&](int tile0) {
+#pragma unroll
+        for (int n = 0; n < TOPK_STAGE_REGS; ++n) {
+            const int i = tid + n * 512, r = i / LDE, c = i - r * LDE;
+            pre[n] = (i < 64 * LDE && tile0 + r < a.N && c < H) ? a.emb1[(size_t)(tile0 + r) * H + c] : 0.0f;
+        }
+    };
+    if (s_begin < s_end) load_tile(s_begin * TI);
+    for (int s = s_begin; s < s_end; ++s) {
+        const int tile0 = s * TI;
+        __syncthreads();                                               // the previous tile's MFMA reads are done (first pass: R_l is staged)
+#pragma unroll
+        for (int n = 0; n < TOPK_STAGE_REGS; ++n)
+            if (tid + n * 512 < 64 * LDE) E_l[tid + n * 512] = pre[n];
+        __syncthreads();
+        if (s + 1 < s_end) load_tile(tile0 + TI);
+        f32x4 acc[2];
+        acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        mma_tile<2>(E_l + mw * 16 * LDE, LDE, 1, R_l + nw * 32 * LDE, 1, LDE, ksteps, acc, lane);
+        const int item0 = tile0 + mw * 16 + q * 4;                     // this lane's 4 consecutive items
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int e = bc * TB + nw * 32 + j * 16 + r16;            // e < Bk: every row of the chunk is written
+            const f32x4 v = real[j] ? acc[j] : (f32x4){0.f, 0.f, 0.f, 0.f};
+            float* o = a.rows + (size_t)e * a.ldr + item0;
+            if (vec_ok && item0 + 3 < a.N) {
+                *(f32x4*)o = v;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (item0 + r < a.N) o[r] = v[r];
+            }
+        }
+    }
+}
+
 // ============================================================================================= C ABI
 static const size_t kTileLds = (size_t)(2 * 64 * LDE + 4 * TB * 3 + MAXB * 3) * sizeof(float);
 static const size_t kBwdLds = (size_t)(2 * 64 * LDE + 64 * LDD) * sizeof(float);
@@ -823,6 +915,40 @@ int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, in
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_topk_tile, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, a);
     hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, st, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// Teacher logits of a step's exemplar rows from stored representations (kernel above).  ader_teacher_ranges: item ranges per 64-row
+// chunk -- about one workgroup per CU over the Bk/64 chunks, at most one range per four 64-item tiles (the tile stream is what hides the
+// table loads), a multiple of 8 (the block -> (range, chunk) mapping), so a small catalog leaves some ranges empty.
+int ader_teacher_ranges(int Np, int Bk) {
+    const int nsub = (Np + TI - 1) / TI;
+    const int nchunk = Bk / TB > 0 ? Bk / TB : 1;
+    int target = 256 / nchunk / 8 * 8;
+    if (target < 8) target = 8;
+    int r = ((nsub + 3) / 4 + 7) / 8 * 8;
+    if (r > target) r = target;
+    if (r < 8) r = 8;
+    return r;
+}
+// rows[e, 0:Np] = the bits ader_logits_store writes for trep[ex_trow[e]] against items 1..Np of temb (row 0 = the padding item), e < n_ex
+// and ex_trow[e] >= 0: trow_local[e] = e; padding rows (ex_trow[e] < 0, or n_ex <= e < Bk): rows[e, 0:Np] = 0.0f, trow_local[e] = -1.
+// Columns [Np, ldr) are not written.  lse (NULL: none) [Bk] <- ader_row_lse(rows, ldr, Np, trow_local, Bk): the same kernel, hence the
+// same bits; 0.0 for padding rows.  ex_trow[e] >= E is the caller's error: the row becomes a padding row and status (NULL: none) gets
+// ADER_ST_BAD_TROW.  Enqueue only.  -2 when H > 160, Bk % 64 != 0, n_ex > Bk, Np < 1, ldr < Np or ldr % 4 != 0.
+int ader_teacher_rows(const float* trep, const float* temb, const int* ex_trow, int n_ex, int Bk, int E, int H, int Np, float* rows,
+                      long ldr, int* trow_local, float* lse, int* status, void* stream) {
+    if (H > HP || H < 1 || Bk <= 0 || Bk % TB != 0 || n_ex < 0 || n_ex > Bk || E < 0 || Np < 1 || ldr < Np || ldr % 4 != 0) return -2;
+    TeachArgs a;
+    a.trep = trep; a.emb1 = temb + H; a.ex_trow = ex_trow; a.n_ex = n_ex; a.Bk = Bk; a.E = E; a.H = H; a.N = Np;
+    a.ranges = ader_teacher_ranges(Np, Bk); a.rows = rows; a.ldr = ldr; a.trow_local = trow_local; a.status = status;
+    const size_t lds = (size_t)(2 * 64 * LDE) * sizeof(float) + TB * sizeof(int);
+    const int rc = ader_dyn_lds<k_teacher_rows>(lds);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_teacher_rows, dim3(a.ranges * (Bk / TB)), dim3(512), lds, st, a);
+    if (lse) hipLaunchKernelGGL(k_row_lse, dim3(Bk), dim3(256), 0, st, rows, ldr, Np, trow_local, lse);
     HIP_LAUNCH_CHECK();
     return 0;
 }

@@ -60,7 +60,7 @@ const FnEntry kFns[] = {
     ADER_PLAN_FN(ader_pos_grad_packed),    ADER_PLAN_FN(ader_gemm_atb_x3_batch),   ADER_PLAN_FN(ader_gemm_atb_x3_batch_pk),
     ADER_PLAN_FN(ader_gemm_atb_x3),        ADER_PLAN_FN(ader_adam_step),           ADER_PLAN_FN(ader_wprep),
     ADER_PLAN_FN(ader_ln_bwd),             ADER_PLAN_FN(ader_fill),                ADER_PLAN_FN(ader_feed_step),
-    ADER_PLAN_FN(ader_concat_i32),
+    ADER_PLAN_FN(ader_concat_i32),         ADER_PLAN_FN(ader_teacher_rows),
 };
 constexpr int kNumFns = sizeof(kFns) / sizeof(kFns[0]);
 

@@ -6,7 +6,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr
-from .common import EPI_ADD, EPI_BIAS, EPI_RELUDROPGRAD, HP, TableJob, _check, flash_sizes
+from .common import EPI_ADD, EPI_BIAS, EPI_RELUDROPGRAD, HP, TableJob, TeacherRep, _check, flash_sizes
 
 
 class _Backward:
@@ -115,6 +115,9 @@ class _Backward:
         """Natural log-sum-exp of every stored teacher row over its Np columns ([E_all]).  The teacher logits of an exemplar are
         fixed for a whole period: computed once per teacher tensor (Engine._tlse_key outlives the steps), gathered per step.  The result
         is WORKSPACE: plans hold its address, so an equal-size teacher lands in the same memory and a new size retires them (_ws_gen)."""
+        tw = self._step.teacher_ws
+        if tw is not None and teacher is tw[0]:
+            return tw[1]            # rows materialised from a TeacherRep for this step: their lse came with them (_teacher_rows)
         key = (teacher.data_ptr(), tuple(teacher.shape), teacher._version)
         E_all = teacher.shape[0]
         tlse_all = self.buf("tlse_all", (E_all,))
@@ -128,20 +131,47 @@ class _Backward:
         """The form of a distilled batch: (ex_trow as an int32 device tensor, default one teacher row per exemplar row in order; the
         complaint about a teacher the kernels cannot read, or None; whether ALL rows fit the flash path and the catalog has not shrunk)."""
         ex_trow = self._dev_i32(ex_trow if ex_trow is not None else np.arange(n_ex))
-        err = (None if teacher.dtype == torch.float32 and teacher.stride(1) == 1 and teacher.shape[1] <= N else
-               "exemplar_logits must be float32 [*, Np <= max_item], unit stride along the items")
+        if isinstance(teacher, TeacherRep):
+            err = (None if teacher.rep.device == self.device and teacher.rep.shape[1] == self.H and teacher.Np <= N else
+                   "TeacherRep must live on the engine's device with H = %d and Np <= max_item" % self.H)
+        else:
+            err = (None if teacher.dtype == torch.float32 and teacher.stride(1) == 1 and teacher.shape[1] <= N else
+                   "exemplar_logits must be float32 [*, Np <= max_item], unit stride along the items")
         cap = self.MAX_ROWS_FAST if self.lfast else self.MAX_ROWS
         return ex_trow, err, err is None and ((n_train + 127) // 128 + (n_ex + 127) // 128) * 128 <= cap and N >= self._grad_hi
+
+    def _check_teacher(self, teacher):
+        """A teacher argument of a public entry point: the dense [*, Np] tensor or a TeacherRep -- which the catalog-sharded scheme
+        does not take (its readout reads teacher COLUMNS by item shard: the rows would have to be materialised shard by shard)."""
+        if isinstance(teacher, TeacherRep) and self.dp_world > 1 and self.dp_mode == "catalog":
+            raise RuntimeError("dp_mode='catalog' does not take a TeacherRep: the sharded teacher readout reads the dense [E, Np] "
+                               "logits by item shard -- pass Engine.teacher_logits' tensor, or use dp_mode='replicated'")
+
+    def _teacher_rows(self, trep, ex_trow, n_ex):
+        """The teacher of this step from a TeacherRep: the rows of its n_ex exemplar rows are regenerated into workspace (the bits
+        ader_logits_store gave the dense form) together with their log-sum-exps (ader_row_lse's kernel), on the current stream ahead
+        of everything that reads them.  Returns (teacher [Bk, Np], ex_trow = the rows' own numbers, -1 for padding rows): from here the
+        step is the dense-teacher step.  The workspace is Engine.buf's: a new size retires plans and descriptors (_ws_gen)."""
+        Bk, Np = (n_ex + 63) // 64 * 64, trep.Np
+        ldr = (Np + 3) // 4 * 4                 # 16-byte row stride, as Engine.logits_from_rep gives the dense form
+        rows = self.buf("trep_rows", (Bk, ldr))
+        trl, lse = self.buf("trep_trow", (Bk,), torch.int32), self.buf("trep_lse", (Bk,))
+        call("ader_teacher_rows", ptr(trep.rep), ptr(trep.table), ptr(ex_trow), n_ex, Bk, trep.rep.shape[0], self.H, Np, ptr(rows), ldr,
+             ptr(trl), ptr(lse), ptr(self.status), self._stream())
+        teacher = rows[:, :Np]
+        self._step.teacher_ws = (teacher, lse)
+        return teacher, trl[:n_ex]
 
     # ---------------------------------------------------------------------------------------- train step
     def loss_and_grad(self, seq, pos, max_item, *, ex_pos=None, teacher=None, ex_trow=None, lambda_=0.0, rate=0.0,
                       n_train_global=None, n_ex_global=None, _defer_table=False):
         """Forward + backward of one step (no optimiser).  seq [B,T] holds the train rows first and the exemplar rows
-        after (main.py:229); pos [n_train]; exemplars are either distilled (teacher [*,Np] + ex_trow [n_ex] row indices,
-        ADER.py:132-137) or one-hot (ex_pos [n_ex], ADER.py:126-131).  Leaves the loss in self.loss (device scalar) and
+        after (main.py:229); pos [n_train]; exemplars are either distilled (teacher [*,Np], or a TeacherRep, + ex_trow [n_ex] row
+        indices, ADER.py:132-137) or one-hot (ex_pos [n_ex], ADER.py:126-131).  Leaves the loss in self.loss (device scalar) and
         the gradient of every parameter in self.grad.  (_defer_table, the fused-update form train_step uses: the loss scalar is
         summed beside the table update, so self.loss is final only after _fused_table_adam -- or the next call here.)"""
         self._refresh_stream()
+        self._check_teacher(teacher)
         sx = self._step if self._in_step else self._begin_step()
         if sx.pending_loss is not None:
             # a deferred step whose fused update never ran (an exception between the two calls, or loss_and_grad(_defer_table=True)
@@ -163,6 +193,9 @@ class _Backward:
             if teacher is not None:
                 ex_trow, err, kd_flash = self._kd_form(teacher, ex_trow, n_train, n_ex, N)
                 _check(err is None, err)
+                if isinstance(teacher, TeacherRep):
+                    _check(ex_trow.shape[0] == n_ex, "ex_trow has %d rows, the batch %d exemplar rows" % (ex_trow.shape[0], n_ex))
+                    teacher, ex_trow = self._teacher_rows(teacher, ex_trow, n_ex)
                 Np = teacher.shape[1]
             else:
                 ex_pos = self._dev_i32(ex_pos)

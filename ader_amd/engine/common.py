@@ -90,7 +90,7 @@ class StepState:
     dist.DataParallel).  Engine._step holds the current one; every public entry point that starts a step replaces it with a fresh
     record (_State._begin_step), so a step never sees its predecessor's leftovers -- except the two fields marked SURVIVES."""
     __slots__ = ("deferred", "pending_loss", "img_ready", "lists", "lists_seq", "late", "late_on", "atb_q", "lnf_done", "early",
-                 "dp_rows", "density", "keep_density", "held")
+                 "dp_rows", "density", "keep_density", "held", "teacher_ws")
 
     def __init__(self):
         self.deferred = None        # the fused update still owed, a TableJob: loss_and_grad(_defer_table=True) -> _fused_table_adam*
@@ -111,6 +111,9 @@ class StepState:
         # re-enters with the device copy of that batch
         self.density, self.keep_density = None, False
         self.held = None            # SURVIVES: inputs of a replayed step, alive until the next step is enqueued behind it (_plan_run)
+        # a step distilled from a TeacherRep: (teacher rows [Bk, Np] of the step's exemplar rows, their log-sum-exps [Bk]), both workspace
+        # (_teacher_rows); _teacher_lse answers from here for that tensor and leaves the per-tensor cache of the dense form alone
+        self.teacher_ws = None
 
 
 class TableJob:
@@ -128,6 +131,54 @@ class TableJob:
         # distilled (None / 0: not): padded rows [kd_row0, Bp) are exemplar rows; their softmax runs over items 1..Np against
         # teacher [*, Np] (by teacher row); trow [Bp] = teacher row of a padded row (-1 = none), tlse2 [Bp] = its log2-domain lse
         self.kd_row0, self.Np, self.teacher, self.trow, self.tlse2 = kd_row0, Np, teacher, trow, tlse2
+
+
+class TeacherRep:
+    """The teacher of a distilled period in its small form: instead of the logits [E, Np] of every stored exemplar
+    (util.py:433), what they are a pure function of -- rep [E, H], the teacher's representation of each exemplar, and table [>= Np+1, H],
+    a COPY of the item table as it stood when the teacher was taken (row 0 = the padding item; never a view of the live parameters, which
+    move with every step).  The rows a step needs are regenerated by ader_teacher_rows with the bits ader_logits_store gave them."""
+    __slots__ = ("rep", "table", "Np")
+
+    def __init__(self, rep, table, Np):
+        Np = int(Np)
+        for t, name in ((rep, "rep"), (table, "table")):
+            _check(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous(),
+                   "TeacherRep: %s must be a contiguous float32 [*, H] tensor" % name)
+        _check(rep.shape[1] == table.shape[1] and rep.device == table.device and 1 <= Np <= table.shape[0] - 1,
+               "TeacherRep: rep [E, H] and table [>= Np+1, H] on one device, Np >= 1 (got %s, %s, Np = %d)"
+               % (tuple(rep.shape), tuple(table.shape), Np))
+        self.rep, self.table, self.Np = rep, table, Np
+
+    def __len__(self):
+        return int(self.rep.shape[0])
+
+    def to(self, device):
+        return TeacherRep(self.rep.to(device), self.table.to(device), self.Np)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.rep, self.table))
+
+    def key(self):
+        """What a launch plan that holds the two pointers is keyed by (a raw pointer that is neither workspace nor a
+        parameter buffer is an input)."""
+        return ("rep", self.rep.data_ptr(), tuple(self.rep.shape), self.table.data_ptr(), tuple(self.table.shape), self.Np)
+
+    def rows(self, idx):
+        """Teacher logits [len(idx), Np] of the stored exemplars `idx` (the reference-shaped views; a step never calls this)."""
+        _check(self.rep.is_cuda, "TeacherRep.rows: the teacher rows are computed on the GPU (no CPU fallback): move the record there")
+        E, H = self.rep.shape
+        dev = self.rep.device
+        ex = torch.as_tensor(idx, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+        n = ex.shape[0]
+        Bk, ldr = (n + 63) // 64 * 64, (self.Np + 3) // 4 * 4
+        out = torch.empty((max(Bk, 64), ldr), dtype=torch.float32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if n:
+            call("ader_teacher_rows", ptr(self.rep), ptr(self.table), ptr(ex), n, Bk, E, H, self.Np, ptr(out), ldr,
+                 ptr(torch.empty(Bk, dtype=torch.int32, device=dev)), None, ptr(status), torch.cuda.current_stream().cuda_stream)
+            _check(int(status.item()) == 0, "TeacherRep.rows: a row index >= %d" % E)
+        return out[:n, :self.Np]
 
 
 def issue_table_job(job, lists, table, item_num, H, shadow, rep_img, lr_t, b1, b2, eps, stream, tile_begin=0, tile_count=-1, bf16="sh"):

@@ -3,7 +3,7 @@ import numpy as np
 import torch
 
 from .._lib import call, ptr
-from .common import _check
+from .common import TeacherRep, _check
 
 # Half-width of the undecided band of the x3 rank filter, as a share of |rep_b| * max_n |E_n|: the SAME value as KAPPA of k_lx3k
 # (csrc/logits_x3.hip, where the bound is derived).  |s_x3 - s_f32| stays below half of it; tests/test_rank_x3_host.py emulates that.
@@ -68,6 +68,15 @@ class _Infer:
     def teacher_logits(self, seq, max_item):
         self._refresh_stream()
         return self.logits(seq, max_item)
+
+    def teacher_rep(self, seq, max_item):
+        """teacher_logits' small form: TeacherRep(the eval-mode representations [n, H], a copy of table rows 0..max_item, max_item) --
+        what the logits [n, max_item] are a pure function of; a distilled step regenerates the rows it needs (ader_teacher_rows)."""
+        self._refresh_stream()
+        rep = self.encode(seq)
+        N = int(max_item)
+        _check(1 <= N <= self.item_num, "max_item must be in [1, item_num = %d] (got %d)" % (self.item_num, N))
+        return TeacherRep(rep, self.param("emb")[:N + 1].detach().clone(), N)
 
     def rank_targets(self, seq, pos, max_item, dtype=None, cand_cap=None):
         """0-based rank of pos[b] among items 1..N for every row (Evaluator path, util.py:323-325) -> int32 numpy [n].

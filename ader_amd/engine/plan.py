@@ -19,7 +19,7 @@ import torch
 
 from .. import _lib
 from .._lib import AderDrop, AderStepBlob, AderStepKey, AderStepOp, AderStepPatch, call, ptr
-from .common import IN_EXPOS, IN_EXTROW, IN_IDX_E, IN_IDX_T, IN_LR, IN_POS, IN_SEQ, IN_TEACHER, N_INPUTS, StepF, _check, dropout_key
+from .common import IN_EXPOS, IN_EXTROW, IN_IDX_E, IN_IDX_T, IN_LR, IN_POS, IN_SEQ, IN_TEACHER, N_INPUTS, StepF, TeacherRep, _check, dropout_key
 
 _M64 = 0xFFFFFFFFFFFFFFFF
 
@@ -211,7 +211,9 @@ class _Native:
                 and not (kw.get("teacher") is not None and kw.get("ex_pos") is not None))
 
     def _plan_key(self, tag, seq, n_train, N, rate, lambda_, teacher, has_expos, n_tg, n_eg, extra=()):
-        tk = None if teacher is None else (teacher.data_ptr(), tuple(teacher.shape), teacher.stride(0))
+        # (a TeacherRep's two tensors reach ader_teacher_rows by pointer and are no patched input: pointers, shapes and Np are the key)
+        tk = (None if teacher is None else teacher.key() if isinstance(teacher, TeacherRep) else
+              (teacher.data_ptr(), tuple(teacher.shape), teacher.stride(0)))
         return (tag, (seq.shape[0], n_train, N, float(rate), float(lambda_), tk, has_expos, n_tg, n_eg, bool(self._use_pack(seq)), extra),
                 self._mode_key())
 
@@ -232,7 +234,8 @@ class _Native:
                 ex_trow, _, flash = self._kd_form(teacher, ex_trow, n_train, n_ex, N)
                 if not flash or ex_trow.shape[0] != n_ex:
                     return None
-                self._teacher_lse(teacher, teacher.shape[1])           # (once per teacher tensor: outside the plan)
+                if not isinstance(teacher, TeacherRep):
+                    self._teacher_lse(teacher, teacher.shape[1])       # (once per teacher tensor: outside the plan)
                 ex_pos = None
             elif ex_pos is not None:
                 ex_pos = self._dev_i32(ex_pos)
@@ -249,7 +252,8 @@ class _Native:
         kw2.pop("ids_host", None)
         kw2.pop("pack_counts", None)
         ins = tuple((slot, t.data_ptr(), t) for slot, t in ((IN_SEQ, seq), (IN_POS, pos), (IN_EXPOS, ex_pos), (IN_EXTROW, ex_trow),
-                                                            (IN_TEACHER, teacher)) if t is not None)
+                                                            (IN_TEACHER, None if isinstance(teacher, TeacherRep) else teacher))
+                    if t is not None)
         return self._plan_run(key, ins, lr, lambda: self._train_step(seq, pos, N, lr, **kw2))
 
     def _fill_inputs(self, plan, ins, lr_bits):
@@ -330,10 +334,11 @@ class _Native:
         """One train step whose batch is cut on the device (csrc/feed.hip) from the GPU-resident packed rows of the Samplers:
         feed = (rows_t, idx_t, o_t, n_t, Bt, rows_e, idx_e, o_e, n_e, Be) -- rows_* [*, T+1] int32 packed rows; idx_* int64 device
         index arrays of the epoch plan, the batch being idx[o : o + n]; Bt / Be the nominal row counts the batch is padded to with
-        weight-0 rows (main.py --fixed_batches).  Exemplar rows are distilled against `teacher` [*, Np] (teacher row = exemplar index,
-        main.py:220-221) or, onehot, replayed with their labels (ADER.py:126-131).  Same step as
+        weight-0 rows (main.py --fixed_batches).  Exemplar rows are distilled against `teacher` [*, Np] or a TeacherRep (teacher row =
+        exemplar index, main.py:220-221) or, onehot, replayed with their labels (ADER.py:126-131).  Same step as
         train_step(cat(seq_t, seq_e), pos_t, ..., n_train_global=n_t, n_ex_global=n_e) with the dropout counters of the unpadded batch."""
         self._refresh_stream()
+        self._check_teacher(teacher)
         rows_t, idx_t, o_t, n_t, Bt, rows_e, idx_e, o_e, n_e, Be = feed
         if n_e <= 0 or Be <= 0 or (teacher is None and not onehot):
             n_e, Be, rows_e, idx_e, o_e = 0, 0, None, None, 0
@@ -367,7 +372,7 @@ class _Native:
                 return self._train_step(seq, pos, max_item, lr, **kw)
 
             N = int(max_item)
-            if kd:
+            if kd and not isinstance(teacher, TeacherRep):
                 self._teacher_lse(teacher, teacher.shape[1])
             if not (self._native_ok(kw) and 1 <= N <= self.item_num and N >= self._grad_hi
                     and (not kd or self._kd_form(teacher, ex_trow, Bt, Be, N)[2])):

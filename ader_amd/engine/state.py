@@ -241,7 +241,8 @@ class _State:
     def _mode_key(self):
         """Every engine switch and placement value that a step's launch arguments depend on: the mode part of a launch plan's key and of
         the packed forward's descriptor-cache key.  A raw device pointer that enters a launch is workspace (Engine.buf: a reallocation
-        bumps _ws_gen and retires plans and descriptors), a flat parameter buffer (never moves), or an input the plan patches."""
+        bumps _ws_gen and retires plans and descriptors), a flat parameter buffer (never moves), an input the plan patches, or part of
+        the plan's key (a dense teacher of the fed step, a TeacherRep's two tensors: plan.py, _plan_key)."""
         return (self.seed, self.row0, self.row0_ex, self._ex_row0_set, self.prune_last, self.late_side_stream, self.cache_descriptors,
                 self.pack_window, self.pack_density, self.beta1, self.beta2, self.eps)
 
@@ -359,4 +360,5 @@ class _State:
         s = int(self.status.item())
         if s:
             self.status.zero_()
-            raise _lib.AderHipError("device status %d: item id outside [0, item_num] in input_seq" % s)
+            raise _lib.AderHipError("device status %d:%s%s" % (s, " item id outside [0, item_num] in input_seq" if s & 1 else "",
+                                                               " teacher row >= the TeacherRep's row count in ex_trow" if s & 2 else ""))

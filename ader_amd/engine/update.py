@@ -134,6 +134,7 @@ class _Update:
         """One `sess.run(train_op)` (main.py:233-256): forward, loss, backward, [gradient exchange], Adam.
         Returns the loss as a 1-element device tensor (no host sync)."""
         self._refresh_stream()
+        self._check_teacher(kw.get("teacher"))
         self._begin_step()
         self._in_step = True
         try:

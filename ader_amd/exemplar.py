@@ -5,7 +5,8 @@ The reference issues one ``sess.run`` per distinct label (~17k per DIGINETICA pe
 and runs the greedy herding loop in numpy on the host.  Here all candidates go through ONE batched
 eval-mode encode on the GPU, the herding loop runs as one segmented HIP kernel launch over all label
 groups (csrc/herding.hip), and the teacher logits of the selected rows stay on the device as one
-[E, N] tensor instead of Python float lists (util.py:433).
+[E, N] tensor instead of Python float lists (util.py:433) -- or, in the "rep" form, as what those logits are a
+function of: the teacher's representations [E, H] and a copy of the item table (engine.TeacherRep).
 """
 from collections import defaultdict
 
@@ -38,14 +39,51 @@ def herding_max_steps(m):
     return k
 
 
-class ExemplarStore:
-    """Selected exemplars of one period: sessions as [E, maxlen+1] int32 rows (inputs ‖ label) and
-    their teacher logits [E, N] (float32, device tensor when produced by the GPU path)."""
+class _RepRows:
+    """`logits[i]` of a store in the rep form: the teacher row of exemplar i, computed when somebody asks (in chunks of 256 rows)."""
 
-    def __init__(self, rows, logits, max_item):
+    def __init__(self, trep):
+        self.trep, self._lo, self._chunk = trep, -1, None
+
+    def __len__(self):
+        return len(self.trep)
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not 0 <= i < len(self.trep):
+            raise IndexError(i)
+        lo = i // 256 * 256
+        if lo != self._lo:
+            self._chunk, self._lo = self.trep.rows(np.arange(lo, min(lo + 256, len(self.trep)))), lo
+        return self._chunk[i - lo]
+
+
+class ExemplarStore:
+    """Selected exemplars of one period: sessions as [E, maxlen+1] int32 rows (inputs ‖ label) and their teacher -- `teacher` is
+    either the logits [E, N] (float32, device tensor when produced by the GPU path) or a TeacherRep (representations [E, H] + the
+    table snapshot [N+1, H]): what a distilled step takes as `teacher=`."""
+
+    def __init__(self, rows, teacher, max_item):
         self.rows = rows
-        self.logits = logits
+        self.teacher = teacher
         self.max_item = max_item
+
+    @property
+    def form(self):
+        return "rep" if _is_rep(self.teacher) else "logits"
+
+    @property
+    def logits(self):
+        """Teacher logits by exemplar: the [E, N] tensor, or (rep form) a view that computes a row when it is indexed."""
+        return _RepRows(self.teacher) if _is_rep(self.teacher) else self.teacher
+
+    @logits.setter
+    def logits(self, value):
+        self.teacher = value
+
+    def tensors(self):
+        """Every tensor / array the store holds."""
+        return [self.rows] + ([self.teacher.rep, self.teacher.table] if _is_rep(self.teacher) else [self.teacher])
 
     def __len__(self):
         return int(self.rows.shape[0])
@@ -59,8 +97,13 @@ class ExemplarStore:
     # the period's checkpoint and read back (rows + teacher logits + the catalog size they were computed for).
     def save(self, path):
         import torch
-        lg = self.logits.detach().cpu().contiguous() if hasattr(self.logits, "detach") else torch.as_tensor(np.asarray(self.logits))
         rows = torch.as_tensor(np.ascontiguousarray(np.asarray(self.rows), dtype=np.int32))
+        if _is_rep(self.teacher):
+            t = self.teacher
+            torch.save({"rows": rows, "rep": t.rep.detach().cpu().contiguous(), "table": t.table.detach().cpu().contiguous(),
+                        "Np": int(t.Np), "max_item": int(self.max_item)}, path)
+            return path
+        lg = self.logits.detach().cpu().contiguous() if hasattr(self.logits, "detach") else torch.as_tensor(np.asarray(self.logits))
         torch.save({"rows": rows, "logits": lg, "max_item": int(self.max_item)}, path)
         return path
 
@@ -68,6 +111,10 @@ class ExemplarStore:
     def load(cls, path, device=None):
         import torch
         d = torch.load(path, weights_only=True)        # tensors and plain numbers only: nothing is unpickled
+        if "rep" in d:
+            from .engine.common import TeacherRep
+            t = TeacherRep(d["rep"], d["table"], int(d["Np"]))
+            return cls(d["rows"].numpy(), t if device is None else t.to(device), int(d["max_item"]))
         lg = d["logits"]
         if device is not None:          # on the device the rows keep the 16-byte aligned stride Engine.teacher_logits gives them
             pad = torch.empty((lg.shape[0], (lg.shape[1] + 3) // 4 * 4), dtype=lg.dtype, device=device)[:, :lg.shape[1]]
@@ -78,15 +125,24 @@ class ExemplarStore:
     def by_label(self):
         """{item: [[session, logits_row], ...]} -- the reference's `fast_exemplar` view (util.py:433), rows in store order."""
         out = defaultdict(list)
+        logits = self.logits            # (rep form: ONE row view, so that its chunk of computed rows is reused)
         for i, r in enumerate(np.asarray(self.rows)):
-            out[int(r[-1])].append([r[r != 0].tolist(), self.logits[i]])
+            out[int(r[-1])].append([r[r != 0].tolist(), logits[i]])
         return out
 
 
-class ExemplarGenerator:
-    """Same constructor arguments as the reference (util.py:366-374)."""
+def _is_rep(teacher):
+    return hasattr(teacher, "rep") and hasattr(teacher, "table")          # (engine.TeacherRep, without importing the engine here)
 
-    def __init__(self, data, exemplar_size, disable_m, batch_size, maxlen, dropout_rate, max_item, shard=(0, 1)):
+
+class ExemplarGenerator:
+    """Same constructor arguments as the reference (util.py:366-374); teacher_form: "logits" = the store keeps the teacher logits
+    [E, N] (util.py:433), "rep" = the teacher's representations and a table snapshot (engine.TeacherRep)."""
+
+    def __init__(self, data, exemplar_size, disable_m, batch_size, maxlen, dropout_rate, max_item, shard=(0, 1), teacher_form="logits"):
+        if teacher_form not in ("logits", "rep"):
+            raise ValueError("teacher_form must be 'logits' or 'rep' (got %r)" % (teacher_form,))
+        self.teacher_form = teacher_form
         self.shard = shard          # (rank, world): label groups are independent herding units (SURVEY 8e)
         self._exemplars, self._view = defaultdict(list), None
         self.m = exemplar_size
@@ -114,6 +170,13 @@ class ExemplarGenerator:
     def _set_view(self, labels, counts, sel_rows, logits, keep_empty=False):
         self._keep_empty = set(labels) if keep_empty else set()
         self._view = (list(labels), [int(c) for c in counts], sel_rows, logits)
+
+    def _make_store(self, model, sel_rows):
+        """self.store <- the selected rows with their teacher in the form asked for; returns the logits-by-exemplar of the views."""
+        seq = sel_rows[:, :self.maxlen]
+        teacher = (model.engine.teacher_rep if self.teacher_form == "rep" else model.engine.teacher_logits)(seq, self.max_item)
+        self.store = ExemplarStore(sel_rows, teacher, self.max_item)
+        return self.store.logits
 
     def _segments(self):
         g = self.sess_by_item
@@ -150,8 +213,7 @@ class ExemplarGenerator:
             keep.append(ids)
         keep = np.concatenate(keep) if keep else np.zeros(0, np.int64)
         sel_rows = rows[keep]
-        logits = model.engine.teacher_logits(sel_rows[:, :self.maxlen], self.max_item)
-        self.store = ExemplarStore(sel_rows, logits, self.max_item)
+        logits = self._make_store(model, sel_rows)
         # reference-shaped view {item: [[session, logits_row], ...]} (logits rows are views of the store): built on demand
         self._set_view(labels, sel_cnt[:len(labels)], sel_rows, logits, keep_empty=True)
         return int(len(keep))
@@ -183,8 +245,7 @@ class ExemplarGenerator:
             counts.append(c)
         keep = np.concatenate(keep) if keep else np.zeros(0, np.int64)
         sel_rows = rows[keep]
-        logits = model.engine.teacher_logits(sel_rows[:, :self.maxlen], self.max_item)
-        self.store = ExemplarStore(sel_rows, logits, self.max_item)
+        logits = self._make_store(model, sel_rows)
         self._set_view(labels, counts, sel_rows, logits)
         return int(len(keep))
 
@@ -203,7 +264,6 @@ class ExemplarGenerator:
             counts.append(c)
         keep = np.concatenate(keep) if keep else np.zeros(0, np.int64)
         sel_rows = rows[keep]
-        logits = model.engine.teacher_logits(sel_rows[:, :self.maxlen], self.max_item)
-        self.store = ExemplarStore(sel_rows, logits, self.max_item)
+        logits = self._make_store(model, sel_rows)
         self._set_view(labels, counts, sel_rows, logits)
         return int(len(keep))

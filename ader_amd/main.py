@@ -7,7 +7,7 @@ Differences from the reference that do not change results: booleans are parsed w
 batches and teacher logits stay on the GPU (the reference feeds Python float lists every step, util.py:254);
 the best-epoch checkpoint is kept in memory and written to disk only with --save_ckpt.
 Extra flags: --logits_dtype, --max_periods, --data_root, --save_ckpt, --eval_batch (--test_batch is accepted and ignored:
-ranks do not depend on the evaluation batch size), --dist_backend, --device_feed.
+ranks do not depend on the evaluation batch size), --dist_backend, --device_feed, --teacher_form.
 
 Data parallel: launched as `python -m torch.distributed.run --nproc-per-node W -m ader_amd.main ...` every
 rank builds the same batches from the same RNG streams, trains on its slice of the train rows and of the exemplar rows
@@ -58,6 +58,9 @@ _BUILD_FLAGS = (
     ("eval_batch", 1024, int, "rows per evaluation launch (results do not depend on it)"),
     ("pack_sessions", "auto", str, ("auto", "on", "off")),
     ("dp_mode", "auto", str, ("auto", "replicated", "catalog")),
+    # what the exemplar store keeps of the previous period's model: "logits" = its logits [E, Np] (util.py:433), "rep" = its
+    # representations [E, H] and a copy of its item table; the rows a step needs are regenerated, bit for bit (engine.TeacherRep)
+    ("teacher_form", "logits", str, ("logits", "rep")),
     ("fed_steps", True, bool, "single GPU with --device_feed and --fixed_batches: the batch is cut on the GPU by the step's first launch "
                               "and the step is one native call (Engine.train_step_fed); False: batches assembled by torch, as data-parallel runs do"),
     ("fixed_batches", True, bool, "pad every train / exemplar batch to its nominal row count with weight-0 rows: the feeder drops "
@@ -197,7 +200,7 @@ def run(args, log=print):
                                 exemplar_sampler.rows_dev(), idx_e, o_e, n_e, exemplar_sampler.batch_size)
                     else:
                         feed = (train_sampler.rows_dev(), idx_t, o_t, n_t, train_sampler.batch_size, None, None, 0, 0, 0)
-                    model.train_step_fed(feed, max_item, args.lr, args.dropout_rate, teacher=store.logits if use_ex else None)
+                    model.train_step_fed(feed, max_item, args.lr, args.dropout_rate, teacher=store.teacher if use_ex else None)
                 for _ in range(0 if fed else batch_num):
                     seq, pos = train_sampler.next_batch()
                     kw = {}
@@ -241,7 +244,7 @@ def run(args, log=print):
                         if args.disable_distillation:
                             model.train_step(seq_l, pos_t, max_item, args.lr, args.dropout_rate, ex_pos=ex_pos, **kw)
                         else:
-                            model.train_step(seq_l, pos_t, max_item, args.lr, args.dropout_rate, teacher=store.logits,
+                            model.train_step(seq_l, pos_t, max_item, args.lr, args.dropout_rate, teacher=store.teacher,
                                              ex_trow=idx if idx_dev is None else idx_dev, **kw)
                     else:
                         model.train_step(seq_t, pos_t, max_item, args.lr, args.dropout_rate, **kw)
@@ -284,7 +287,8 @@ def run(args, log=print):
                 exemplar_candidate.extend(valid_subseq)
                 exemplar_candidate.extend(exemplar_subseq)
                 exemplar = ExemplarGenerator(exemplar_candidate, args.exemplar_size, args.equal_exemplar, args.batch_size,
-                                             args.maxlen, args.dropout_rate, max_item, shard)
+                                             args.maxlen, args.dropout_rate, max_item, shard,
+                                             teacher_form=getattr(args, "teacher_form", "logits"))
                 if args.selection == 'herding':
                     saved_num = exemplar.herding_selection(sess, model)
                 elif args.selection == 'loss':

@@ -15,6 +15,9 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
                                                                          + exact-f32 recheck of the undecided pairs)
   ader::topk_items(rep, emb, seen, N, k)                       -> (items, scores)   the k best items per row, fused with the logits:
                                                                          order and bits of argsort(-logits) (ADER.py:92, 103)
+  ader::teacher_rows(trep, temb, ex_trow, Np)                  -> (rows, trow_local)   teacher logits of a step's exemplar rows from
+                                                                         stored representations + a table snapshot: the bits of
+                                                                         ader_logits_store (util.py:433, ADER.py:134-135)
   ader::herding_select(rep, seg, quota, max_steps)             -> (sel, cnt)   util.py:401-434
 
 Trainable surface (second half of this file; every forward has an autograd formula over its `_bwd` operator):
@@ -214,6 +217,33 @@ def topk_items(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor
 @topk_items.register_fake
 def _(rep, emb, seen, N, k):
     return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
+
+
+@torch.library.custom_op("ader::teacher_rows", mutates_args=())
+def teacher_rows(trep: torch.Tensor, temb: torch.Tensor, ex_trow: torch.Tensor, Np: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """trep [E,H] teacher representations, temb [>= Np+1, H] the table snapshot (row 0 = padding item), ex_trow int32 [n] teacher row per
+    exemplar row (-1 = padding row) -> (rows float32 [Bk, Np], Bk = n padded to 64, a view of a buffer with a 16-byte row stride;
+    trow_local int32 [Bk]): rows[e] = the logits ader_logits_store gives trep[ex_trow[e]] over items 1..Np, bit for bit, and
+    trow_local[e] = e; padding rows are 0.0 with trow_local = -1.  A teacher row >= E raises (one synchronisation to read the status)."""
+    _chk(trep, "trep", torch.float32, 2), _chk(temb, "temb", torch.float32, 2), _chk(ex_trow, "ex_trow", torch.int32, 1)
+    E, H = trep.shape
+    n = ex_trow.shape[0]
+    if temb.shape[1] != H or H > HP or not (1 <= Np <= temb.shape[0] - 1) or n < 1:
+        raise RuntimeError("ader::teacher_rows: bad shapes (trep %s, temb %s, Np = %d, n = %d)" % (tuple(trep.shape), tuple(temb.shape), Np, n))
+    Bk, ldr = (n + 63) // 64 * 64, (Np + 3) // 4 * 4
+    dev = trep.device
+    rows, trl = torch.empty(Bk, ldr, device=dev), torch.empty(Bk, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    call("ader_teacher_rows", ptr(trep), ptr(temb), ptr(ex_trow), n, Bk, E, H, Np, ptr(rows), ldr, ptr(trl), None, ptr(status), _st())
+    if int(status.item()):
+        raise RuntimeError("ader::teacher_rows: a teacher row >= E = %d in ex_trow" % E)
+    return rows[:, :Np], trl
+
+
+@teacher_rows.register_fake
+def _(trep, temb, ex_trow, Np):
+    Bk = (ex_trow.shape[0] + 63) // 64 * 64
+    return trep.new_empty((Bk, (Np + 3) // 4 * 4))[:, :Np], ex_trow.new_empty(Bk)
 
 
 @torch.library.custom_op("ader::herding_select", mutates_args=())

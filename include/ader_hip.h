@@ -260,6 +260,19 @@ int ader_topk_ranges(int N, int Bp);
 int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
                     int k, unsigned long long* part, int* items, float* scores, void* stream);
 
+/* Teacher logits of a step's exemplar rows, regenerated from stored teacher representations (util.py:433 computes them, ADER.py:134-135
+ * consumes them as softmax(exemplar_logits)): trep [E,H] = the teacher's representations, temb = the item table as it stood when the
+ * teacher was taken (row 0 = the padding item), ex_trow [n_ex] = teacher row per exemplar row of the step (-1 = padding row), Bk = n_ex
+ * padded to a multiple of 64.  rows [Bk, ldr] float32, ldr >= Np and a multiple of 4: for ex_trow[e] = r >= 0, rows[e, 0:Np] = bit for bit
+ * what ader_logits_store writes for trep[r] against items 1..Np of temb, and trow_local[e] = e; padding rows (ex_trow[e] < 0, e >= n_ex):
+ * rows[e, 0:Np] = 0.0f, trow_local[e] = -1.  Columns [Np, ldr) are not written.  lse [Bk] (NULL: none) = ader_row_lse(rows, ldr, Np,
+ * trow_local, Bk, lse): the same kernel and bits, issued behind the rows.  A pure function of (trep row, temb, Np) per row.  r >= E is the
+ * caller's error: never read, the row is written as a padding row and bit 2 of *status (NULL: none) is set.  Enqueue only.
+ * -2 when H > 160, Bk % 64 != 0, n_ex > Bk, Np < 1, ldr < Np or ldr % 4 != 0.  ader_teacher_ranges: item ranges per 64-row chunk. */
+int ader_teacher_ranges(int Np, int Bk);
+int ader_teacher_rows(const float* trep, const float* temb, const int* ex_trow, int n_ex, int Bk, int E, int H, int Np, float* rows,
+                      long ldr, int* trow_local, float* lse, int* status, void* stream);
+
 /* ---- bf16-MFMA variant of the one-hot softmax CE (fp32 master table, fp32 accumulate/softmax): ADER.py:88-93 ------ */
 /* Bp % 128 == 0, H even.  Scratch: rep_bf Bp*168 bf16; pm, pl: R*Bp floats; pO: R*Bp*160 floats, R = ader_lbf_ranges(N,Bp).
  * Outputs: lse/off/rowloss [Bp], loss [1], drep [B,H] (complete: includes the one-hot target term). */
