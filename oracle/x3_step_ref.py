@@ -22,6 +22,11 @@ restates the sharded forward -- per-shard {M, L, O} partials merged in rank orde
 global batch explicitly, padded_layout maps the compact row numbering to [W blocks of Bp | W blocks of Bk] and back, and
 range_update_emulate / check_range_untouched state which table rows a rank's range launch may write (SHARD_CASES / make_shard_batch).
 
+The table gradient WRITTEN OUT to Engine.grad (tests/test_gpu_table_grad_rowwise.py) is held to the same reference by two more
+emulations: emulate_f32 restates the exact-f32 kernels of logits.hip, emulate(unfused=True) the gradient-only form of the x3 table
+kernel (k_tab_upd<X3, ADAM = false> + k_tab_target_fix), both followed by the ordered scatter of the input rows; GRAD_CASES are
+their input families, check_rows_zero / grad_buffer_emulate the exact statement about a catalog that shrinks between two calls.
+
 The input families of tests/test_gpu_x3_rowwise.py are built here too (CASES / make_batch), so that the host tests assert their
 conditions -- enough rows that ONLY the gradient GEMM writes -- on the very inputs the GPU tests run."""
 import numpy as np
@@ -207,8 +212,71 @@ def _sharded_forward(inp, s2, shards, fault, frow):
     return M, L, O, O2, tlse2, parts
 
 
-def emulate(inp, chunk=None, ncol=None, shards=None, fault=None, frow=None):
+def _scatter_ordered(g, inp):
+    """The input rows added into g [N,H] (numpy, in place) in (id, position) order, each dx * sqrt(H) rounded to float32 and then
+    added: the order of the fused kernel's sparse lists and of k_scatter_rows_ordered (rowwise.hip:197-208: one workgroup per 64-id
+    bucket, thread c adds the bucket's entries one after the other, `demb += rows * scale` -- which the compiler may contract into one
+    fma: half an ulp of the product, far below the measure)."""
+    ids = inp["seq"].numpy()
+    dxs = (inp["dx"] * torch.tensor(np.float32(inp["sqrtH"]))).numpy()
+    for k in np.argsort(ids, kind="stable"):
+        if ids[k] > 0:
+            g[ids[k] - 1] += dxs[k]
+    return g
+
+
+def label_groups(y):
+    """[(label, rows ascending)] of the labels > 0 of y [B], in the order of each label's FIRST row."""
+    yn = np.asarray(torch.as_tensor(y).numpy())
+    out, seen = [], set()
+    for b in range(len(yn)):
+        lb = int(yn[b])
+        if lb > 0 and lb not in seen:
+            seen.add(lb)
+            out.append((lb, [int(j) for j in np.nonzero(yn == lb)[0]]))
+    return out
+
+
+def _unfused_table_gradient(inp, c, rep_q, w, label_shift):
+    """The table gradient as the gradient-only x3 launch writes it (ader_tab_grad / ader_tab_grad_kd, table_update.hip:472-512):
+      tile     k_tab_upd<X3 = true, ADAM = false> (table_update.hip:162-236): per 64-row chunk of the batch, wave (ih, bh) takes the
+               chunk's rows 32 bh .. 32 bh + 31 (b0 = c * 64 + bh * 32, line 165) and accumulates P^T . rep in the three-product form
+               (P and rep split hi / lo, lines 202-229) over ALL chunks in its own registers; the two batch halves are then summed in
+               LDS, bh = 0 first (lines 262-283), and the tile is WRITTEN to the gradient rows (lines 284-291).  A distilled step's
+               exemplar rows start a chunk of their own (kd_row0 is a multiple of 128: chunks do not straddle it, line 189).
+      labels   k_tab_target_fix (table_update.hip:398-437): per distinct label ONE row is added: acc = 0, then acc -= w_b (rep_hi +
+               rep_lo)_b over the rows that share the label in batch order (lines 413-431), formed in registers by the wave of the
+               first such row and added ONCE to the written tile (lines 432-436).
+      inputs   then the ordered scatter (_scatter_ordered; Engine._scatter_dx runs behind the blocks' backward).
+    This order differs from the fused kernel's (emulate(unfused=False): tile, input positions, then every label row subtracted on
+    its own): a row that is both a label and an input sums the same terms in another order.
+    label_shift (b, d): planted fault -- the row of batch row b's label lands d table rows off."""
+    N, H, B, n_train = inp["N"], inp["H"], inp["B"], inp["n_train"]
+    rep = inp["rep"]
+    blocks = [(0, B)] if inp["tl"] is None else [(0, n_train), (n_train, B)]
+    halves = [torch.zeros(N, H), torch.zeros(N, H)]
+    for lo, hi in blocks:
+        for b0 in range(lo, hi, 64):
+            for h in (0, 1):
+                r0, r1 = b0 + 32 * h, min(b0 + 32 * h + 32, hi)
+                if r1 > r0:
+                    halves[h] += _x3mm(c[r0:r1].t().contiguous(), rep[r0:r1])
+    g = (halves[0] + halves[1]).numpy()
+    lab = (w[:, None] * rep_q).numpy()
+    for lb, rows in label_groups(inp["y"]):
+        acc = np.zeros(H, dtype=np.float32)
+        for b in rows:
+            acc -= lab[b]
+        t = lb - 1 + (label_shift[1] if label_shift is not None and label_shift[0] in rows else 0)
+        g[t] += acc
+    return _scatter_ordered(g, inp)
+
+
+def emulate(inp, chunk=None, ncol=None, shards=None, fault=None, frow=None, unfused=False, no_teacher=None, label_shift=None):
     """The kernels' arithmetic in float32.  chunk: accumulate the gradient GEMM in batch-row chunks of that size (the device: 32).
+    unfused: the table gradient g as the gradient-only launch and the ordered scatter leave it in Engine.grad
+    (_unfused_table_gradient; the forward outputs are the same kernels').  no_teacher (batch row) / label_shift (batch row, d):
+    planted faults of the table tile -- the teacher term of one distilled row left out; a label's row written d rows off (unfused).
     ncol [B]: override of the number of softmax columns per row (the planted-fault tests).  Returns the outputs of reference() in
     float32 (lse, rowloss, loss, drep, g) plus c, the logit gradient the table update formed, and rep_q = rep_hi + rep_lo.
     shards = [(item_begin, item_count), ...]: the catalog-sharded forward (_sharded_forward) -- the gradient and Adam half is the
@@ -262,10 +330,16 @@ def emulate(inp, chunk=None, ncol=None, shards=None, fault=None, frow=None):
     off = torch.log2(w) - lse2
     c = torch.exp2(s2 + off[:, None])
     if tl is not None:
-        c[n_train:, :Np] -= torch.exp2(t2 + toff[:, None])
+        tsub = torch.exp2(t2 + toff[:, None])
+        if no_teacher is not None:
+            tsub[no_teacher - n_train] = 0.0
+        c[n_train:, :Np] -= tsub
         c[n_train:, Np:] = 0.0
     rh, rl = _split(rep)
     rep_q = rh + rl
+    if unfused:
+        g = torch.from_numpy(_unfused_table_gradient(inp, c, rep_q, w, label_shift))
+        return dict(lse=lse, rowloss=rowloss, loss=rowloss.sum(), drep=drep, g=g, c=c, rep_q=rep_q, parts=parts, off=off)
     if chunk:
         g = torch.zeros(N, inp["H"], dtype=f32)
         for b0 in range(0, B, chunk):
@@ -288,8 +362,156 @@ def emulate(inp, chunk=None, ncol=None, shards=None, fault=None, frow=None):
                 off=off)
 
 
+# =============================================================================================== exact-f32 kernels (logits.hip)
+def logits_ranges(N, Bp):
+    """ader_logits_ranges (logits.hip:775-781): item ranges of the dRep launch -- 8, doubled while the launch stays within ~1024
+    workgroups and every range can hold a 64-item sub-tile."""
+    nsub = (N + TI - 1) // TI
+    target = 1024 // (Bp // 64)
+    r = 8
+    while r * 2 <= target and r * 2 <= nsub:
+        r *= 2
+    return r
+
+
+def _chain_mm(A, Bm):
+    """A [M,K] @ Bm [K,N] as mma_tile forms it: per output ONE float32 accumulator, acc = fmaf(a_k, b_k, acc) for k in order.  (The
+    product of two float32 is exact in float64; the sum is rounded to float64 and from there to float32: fmaf, except for a rare
+    double rounding of half a float32 ulp of that one step.)"""
+    A, Bm = A.to(torch.float64), Bm.to(torch.float64)
+    acc = torch.zeros(A.shape[0], Bm.shape[1], dtype=torch.float32)
+    for k in range(A.shape[1]):
+        acc = (acc.to(torch.float64) + A[:, k, None] * Bm[None, k, :]).to(torch.float32)
+    return acc
+
+
+def emulate_f32(inp, ncol=None, no_teacher=None, label_shift=None):
+    """The arithmetic logits.hip states, in float32 (Engine.loss_and_grad with logits_dtype = "f32": ader_logits_loss_fwd,
+    ader_logits_bwd_drep, ader_logits_bwd_demb, then the ordered scatter):
+      s        = rep . E^T in float32 (mma_tile on v_mfma_f32_16x16x4_f32: logits.hip:103, 288, 353).  mma_tile (common.h:93-107)
+               is ONE accumulator per output carried through the k steps in order, and the f32 MFMA is a chain of fmaf: every product
+               of these kernels is emulated as that chain (_chain_mm), not as a blocked sum;
+      lse      from per-row online (max, sum-exp) partials, merged by merge_ml (logits.hip:69-74, 128-164, 199-221) -- here one
+               partial per 64-item sub-tile, merged in tile order -- lse = m + logf(l) (line 217);
+      target   dot = s at the label column + sum_n expf(t_n - tlse) s_n over a distilled row's teacher columns (lines 139-140),
+               tlse = m + logf(sum expf(t - m)) (k_row_lse, lines 238-257); rowloss = w (lse - dot) (line 219), loss = their sum;
+      dlogit   (lines 259-265) p = expf(s - lse); p -= 1 at the label column; p -= expf(t - tlse) for a distilled row; every
+               column >= ncol is 0; c = w p;
+      dE       = c^T rep accumulated in 64-row batch chunks (k_logits_bwd_de, lines 282-302) into accumulators that live across the
+               chunks (line 279): one fmaf chain over ALL batch rows in order; every row written once (303-312);
+      dRep     = c . E over logits_ranges(N, Bp) item ranges of per = ceil(sub-tiles / ranges) sub-tiles each -- a range beyond the
+               catalog holds none and contributes zeros -- accumulated tile by tile (lines 327-365), the ranges then summed;
+      inputs   added in (id, position) order with the factor sqrt(H) as float32 (_scatter_ordered).
+    The first GPU run found this emulation short of that stated step: with dE as blocked float32 sums per chunk (torch's matmul) the
+    device sat at 10.1x the emulated error in the rows only the GEMM writes at B = 1024 (2.0e-06 against 2.0e-07; 1.0 .. 2.5x at the
+    other shapes) -- a 1024-term fmaf chain of mostly like-signed terms is that much less exact than a blocked sum, and it is what
+    the kernel states.  Emulated as the chain, the kernels sit on the emulation (tests/test_gpu_table_grad_rowwise.py).
+    ncol [B]: override of the softmax columns per row; no_teacher (batch row): that distilled row's teacher term left out of dlogit;
+    label_shift (b, d): the -1 of batch row b placed d columns off (the planted-fault tests).  Returns the outputs of emulate()."""
+    f32 = torch.float32
+    N, B, H, n_train, tl = inp["N"], inp["B"], inp["H"], inp["n_train"], inp["tl"]
+    E, rep, w, y = inp["E0"][1:N + 1], inp["rep"], inp["w"], inp["y"]
+    valid, _ = loss_tail_terms(inp, f32)
+    if ncol is not None:
+        valid = torch.arange(N)[None, :] < torch.as_tensor(ncol)[:, None]
+    ninf = torch.tensor(-float("inf"))
+    zero = torch.zeros((), dtype=f32)
+    s = _chain_mm(rep, E.t())
+    m, l = torch.full((B,), -float("inf")), torch.zeros(B)
+    for t0 in range(0, N, TI):
+        st = torch.where(valid[:, t0:t0 + TI], s[:, t0:t0 + TI], ninf)
+        m2 = st.max(-1).values
+        l2 = torch.exp(st - torch.where(torch.isinf(m2), zero, m2)[:, None]).sum(-1)
+        mn = torch.maximum(m, m2)
+        a = torch.where(torch.isinf(m), zero, l * torch.exp(m - mn))
+        b = torch.where(torch.isinf(m2), zero, l2 * torch.exp(m2 - mn))
+        m, l = mn, a + b
+    lse = m + torch.log(l)
+    hot = torch.nonzero(y > 0).reshape(-1)
+    dot = torch.zeros(B)
+    dot[hot] = s[hot, y[hot] - 1]
+    q = None
+    if tl is not None:
+        Np = inp["Np"]
+        tm = tl.max(-1).values
+        tlse = tm + torch.log(torch.exp(tl - tm[:, None]).sum(-1))
+        q = torch.exp(tl - tlse[:, None])
+        dot[n_train:] += (q * s[n_train:, :Np]).sum(-1)
+    rowloss = w * (lse - dot)
+    p = torch.exp(s - lse[:, None])
+    col = y[hot] - 1
+    if label_shift is not None:
+        col = torch.where(hot == label_shift[0], col + label_shift[1], col)
+    p[hot, col] -= 1.0
+    if q is not None:
+        if no_teacher is not None:
+            q = q.clone()
+            q[no_teacher - n_train] = 0.0
+        p[n_train:, :Np] -= q
+    p = torch.where(valid, p, zero)
+    c = w[:, None] * p
+    g = _chain_mm(c.t(), rep)
+    nsub = (N + TI - 1) // TI
+    R = logits_ranges(N, (B + 63) // 64 * 64)
+    per = (nsub + R - 1) // R
+    drep = torch.zeros(B, H)
+    for r in range(R):
+        i0, i1 = min(N, r * per * TI), min(N, (r * per + per) * TI)
+        drep += _chain_mm(c[:, i0:i1], E[i0:i1])
+    g = torch.from_numpy(_scatter_ordered(g.numpy(), inp))
+    return dict(lse=lse, rowloss=rowloss, loss=rowloss.sum(), drep=drep, g=g, c=c, rep_q=rep, parts=None, off=None)
+
+
+def tensor_max_error(a, b, floor=0.0):
+    """The measure of tests/test_gpu_parity.py (nerr): max |a - b| over the WHOLE tensor by max(max |b|, floor).  Its bounds on the
+    table gradient there: NERR_F32 with exact-f32 block GEMMs, NERR_X3 with the x3 block GEMMs, floor = 1e-4."""
+    a, b = np.asarray(torch.as_tensor(a), dtype=np.float64), np.asarray(torch.as_tensor(b), dtype=np.float64)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), floor, 1e-30))
+
+
+NERR_F32, NERR_X3, NERR_FLOOR = 5e-5, 6e-4, 1e-4
+
+
+def check_rows_zero(g_full, lo, hi, what="gradient"):
+    """Exact: rows lo..hi (inclusive) of a full [V,H] table tensor are BITWISE zero -- row 0, the rows beyond max_item, and the rows
+    a shrunken catalog has left behind (Engine.loss_and_grad clears _grad_hi's stale rows)."""
+    z = torch.as_tensor(g_full).detach().cpu().contiguous().view(torch.int32)[lo:hi + 1]
+    bad = (z != 0).any(-1)
+    if bool(bad.any()):
+        raise ParityError("%s: row %d of rows %d..%d is not zero" % (what, lo + int(torch.nonzero(bad)[0]), lo, hi))
+
+
+def grad_buffer_emulate(calls, V, stale_row=None):
+    """Engine.loss_and_grad's plumbing of the table gradient buffer over several calls on one engine (backward.py:252-255): calls =
+    [(N, g [N,H])]; a call with N below the highest N so far first clears rows N + 1 .. that N, then rows 1..N are overwritten.
+    stale_row: planted fault -- that row is left out of the clearing.  Returns the full [V,H] buffer after the last call."""
+    buf, hi = None, 0
+    for N, g in calls:
+        g = torch.as_tensor(g, dtype=torch.float32)
+        if buf is None:
+            buf = torch.zeros(V, g.shape[1])
+        if N < hi:
+            keep = buf[stale_row].clone() if stale_row is not None else None
+            buf[N + 1:hi + 1] = 0.0
+            if keep is not None:
+                buf[stale_row] = keep
+        hi = max(hi, N)
+        buf[1:N + 1] = g
+    return buf
+
+
+def step_rows(B, n_ex, kd_flash, pad=128):
+    """(rows [B + n_ex], total): the row of the per-row device buffers (lse, rowloss, weights) that holds each batch row, and the
+    buffers' length.  Plain numbering padded to `pad` rows (128 on the flash kernels, 64 on the exact-f32 ones), or -- a distilled
+    step on the flash kernels -- [train rows padded to 128 | exemplar rows padded to 128] (padded_layout of one rank)."""
+    if kd_flash:
+        lay = padded_layout(1, B, n_ex)
+        return lay["rows"], lay["Bg"]
+    return torch.arange(B + n_ex), (B + n_ex + pad - 1) // pad * pad
+
+
 # =============================================================================================== check
-QUANTITIES = ("lse", "rowloss", "loss", "drep", "g_dense", "g_sparse")
+QUANTITIES =("lse", "rowloss", "loss", "drep", "g_dense", "g_sparse")
 
 
 def quantity_errors(x, ref, dense):
@@ -532,8 +754,9 @@ def _pool(N):
     return p if len(p) else np.array([N])
 
 
-def _case(name, N=650, B=70, H=150, mode="vanilla", n_ex=0, Np=0, lam=0.0, plant=None, item_num=None):
-    return dict(name=name, N=N, B=B, H=H, mode=mode, n_ex=n_ex, Np=Np, lam=lam, plant=plant, item_num=item_num or max(N + 50, 700), T=8)
+def _case(name, N=650, B=70, H=150, mode="vanilla", n_ex=0, Np=0, lam=0.0, plant=None, item_num=None, share=None, then_N=None):
+    return dict(name=name, N=N, B=B, H=H, mode=mode, n_ex=n_ex, Np=Np, lam=lam, plant=plant, item_num=item_num or max(N + 50, 700), T=8,
+                share=share, then_N=then_N)
 
 
 # One family per mechanism, the others at their base value (H = 150, B = 70 train rows, N = 650).  Numbers from
@@ -548,6 +771,40 @@ CASES = (
     + [_case("H%d" % h, H=h) for h in (64, 158, 10)]
 )
 CASE_IDS = [c["name"] for c in CASES]
+
+# ---- the table gradient written out to Engine.grad (tests/test_gpu_table_grad_rowwise.py).  Forms: "f32" = the exact-f32 kernels of
+# logits.hip (64-row chunks, rows padded to 64, MAXB = 1024 rows), "x3u" = the x3 forward + the gradient-only table launch.
+# Planted labels of `labels_shared` (B = 260): ids no ordinary row uses (the pool holds multiples of 4).
+SHARED_LABELS = ((101, (0, 1, 2, 3)),        # one label in the four rows of ONE workgroup of k_tab_target_fix (one wave per row)
+                 (202, (5, 70, 200)))        # one label in rows of three different 64-row ballot blocks
+_BY_NAME = {c["name"]: c for c in CASES}
+_BOTH, _X3U = ("f32", "x3u"), ("x3u",)
+GRAD_CASES = [dict(c, forms=f) for c, f in (
+    [(_BY_NAME["N%d" % n], _BOTH) for n in (2, 63, 64, 65, 128, 129, 650)]
+    # exact-f32 rows: one row, a full chunk, one row into the second chunk, MAXB; x3 rows as in CASES (B1153: beyond MAXB, x3 only)
+    + [(_BY_NAME["B1"], _BOTH)] + [(_case("B%d" % b, B=b), _BOTH) for b in (64, 65, 1024)]
+    + [(_BY_NAME["B%d" % b], _X3U) for b in (32, 33, 128, 129, 1153)]
+    + [(_BY_NAME["lists_records"], _BOTH), (_BY_NAME["lists_hot"], _BOTH)]
+    + [(_case("labels_shared", B=260, share="labels"), _BOTH)]
+    + [(_BY_NAME["onehot"], _BOTH)]
+    # three exemplar labels equal train labels: the rows that share a label carry DIFFERENT weights
+    + [(_case("onehot_shared", B=53, n_ex=17, mode="onehot", lam=0.6, share="onehot"), _BOTH)]
+    + [(_BY_NAME["kd_Np%d_ex%d" % k], _BOTH) for k in ((648, 70), (645, 70), (64, 70), (650, 70), (648, 1))]
+    + [(_BY_NAME["kd_Np%d_ex%d" % k], _X3U) for k in ((645, 129), (650, 129))]
+    + [(_BY_NAME["H%d" % h], _BOTH) for h in (64, 158, 10)]
+    # 18 sub-tiles: ader_logits_ranges gives 16 ranges at Bp = 128 (from 961 items on), two sub-tiles each, seven of them empty
+    # (the catalogs up to 448 items give 8 ranges of which some hold no sub-tile)
+    + [(_case("N1100", N=1100), _BOTH)]
+    # two calls on ONE engine, N = 650 and then N = 300: the stale rows 301..650 must be cleared
+    + [(_case("shrink", then_N=300), _BOTH)]
+)]
+GRAD_CASE_BY_NAME = {c["name"]: c for c in GRAD_CASES}
+ADAM_FAMILIES = ("N650", "N65", "lists_hot")          # the dense Adam step behind the unfused gradient
+
+
+def second_call(case):
+    """The case of the second call of a two-call family (its own batch: make_batch(second_call(case), seed=1))."""
+    return dict(case, name=case["name"] + "/2", N=case["then_N"], then_N=None)
 
 
 def make_batch(case, seed=0):
@@ -592,8 +849,14 @@ def make_batch(case, seed=0):
         for idv, cnt in labels:
             pos[k:k + cnt] = idv
             k += cnt
+    if case.get("share") == "labels":
+        for idv, rows in SHARED_LABELS:
+            pos[list(rows)] = idv
     if case["mode"] == "onehot":
         out["ex_pos"] = pool[rs.randint(0, len(pool), size=n_ex)].astype(np.int32)
+        if case.get("share") == "onehot":       # exemplar rows 0..2 take the first three DISTINCT train labels
+            _, first = np.unique(pos, return_index=True)
+            out["ex_pos"][:3] = pos[np.sort(first)[:3]]
     elif case["mode"] == "kd":
         out["teacher"] = (rs.standard_normal((n_ex + 9, case["Np"])) * 2).astype(np.float32)
         out["trow"] = rs.permutation(n_ex + 9)[:n_ex].astype(np.int32)

@@ -81,12 +81,8 @@ def _run_step(case, batch, preload):
         out["readout"] = "k_lx3r" if (teacher.stride(0) % 4 == 0 and teacher.data_ptr() % 16 == 0 and case["Np"] >= 32
                                       and H == 150) else "k_lx3_fwd"
         assert out["readout"] == ("k_lx3_fwd" if case["Np"] % 4 else "k_lx3r")
-        Bt = (B + 127) // 128 * 128
-        rows = torch.cat([torch.arange(B), Bt + torch.arange(n_ex)])
-        assert out["lse"].numel() == Bt + (n_ex + 127) // 128 * 128
-    else:
-        rows = torch.arange(Ba)
-        assert out["lse"].numel() == (Ba + 127) // 128 * 128
+    rows, total = X.step_rows(B, n_ex, case["mode"] == "kd")
+    assert out["lse"].numel() == total
     pad = torch.ones(out["lse"].numel(), dtype=torch.bool)
     pad[rows] = False
     for name in ("lse", "rowloss"):
