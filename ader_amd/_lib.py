@@ -103,6 +103,7 @@ _SIGS = {
     "ader_topk_items": [P, P, I, I, I, I, P, P, I, I, P, P, P, P],
     "ader_teacher_ranges": [I, I],
     "ader_teacher_rows": [P, P, P, I, I, I, I, I, P, L, P, P, P, P],
+    "ader_teacher_rows_shard": [P, P, P, I, I, I, I, I, I, I, P, L, P, P, P],
     "ader_adam_step": [P, P, P, P, Z, F, F, F, F, P, Z, I, P],
     "ader_fill": [P, Z, F, P],
     "ader_reduce_slabs": [P, L, I, I, I, I, P, P, P],

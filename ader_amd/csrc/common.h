@@ -32,6 +32,12 @@ template <auto Kern> static int ader_dyn_lds(size_t bytes) {
     return 0;
 }
 
+// items of the shard [item_begin + 1, item_begin + item_count] that lie within the first N (catalog-sharded launchers)
+static inline int shard_items(int N, int item_begin, int item_count) {
+    const int n = N - item_begin < item_count ? N - item_begin : item_count;
+    return n < 0 ? 0 : n;
+}
+
 // status bits written by kernels into the engine's status word
 #define ADER_ST_BAD_ID 1
 #define ADER_ST_BAD_TROW 2      // a teacher row index >= the number of stored teacher representations (ader_teacher_rows)

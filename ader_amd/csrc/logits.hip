@@ -952,5 +952,27 @@ int ader_teacher_rows(const float* trep, const float* temb, const int* ex_trow, 
     HIP_LAUNCH_CHECK();
     return 0;
 }
+// The column window of ader_teacher_rows' rows that a rank of the catalog-sharded scheme reads (util.py:433, ADER.py:134-135 with the
+// table sharded): rows_win[e, c] = the float32 ader_teacher_rows writes at column item_begin + c of row e, c < n_loc = the shard's items
+// [item_begin + 1, item_begin + item_count] below Np (shard_items).  k_teacher_rows as it stands: its table operand starts at the
+// shard's first item, its catalog is the n_loc items, and its range partition runs over them -- a (row, item) result does not depend on
+// its tile neighbours, so the window holds the dense teacher's bits.  Nothing outside [0, n_loc) of a row is written; n_loc == 0 writes
+// trow_local (and the status word) only: every range of the launch is empty and the table operand is never dereferenced.
+int ader_teacher_rows_shard(const float* trep, const float* temb, const int* ex_trow, int n_ex, int Bk, int E, int H, int Np,
+                            int item_begin, int item_count, float* rows_win, long ldr, int* trow_local, int* status, void* stream) {
+    if (H > HP || H < 1 || Bk <= 0 || Bk % TB != 0 || n_ex < 0 || n_ex > Bk || E < 0 || Np < 1 || item_begin < 0 || item_count < 0 ||
+        item_begin % 4 != 0 || ldr % 4 != 0) return -2;
+    const int n_loc = shard_items(Np, item_begin, item_count);
+    if (ldr < n_loc) return -2;
+    TeachArgs a;
+    a.trep = trep; a.emb1 = temb + (size_t)H * (1 + (n_loc > 0 ? item_begin : 0)); a.ex_trow = ex_trow; a.n_ex = n_ex; a.Bk = Bk; a.E = E; a.H = H;
+    a.N = n_loc; a.ranges = ader_teacher_ranges(n_loc, Bk); a.rows = rows_win; a.ldr = ldr; a.trow_local = trow_local; a.status = status;
+    const size_t lds = (size_t)(2 * 64 * LDE) * sizeof(float) + TB * sizeof(int);
+    const int rc = ader_dyn_lds<k_teacher_rows>(lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_teacher_rows, dim3(a.ranges * (Bk / TB)), dim3(512), lds, (hipStream_t)stream, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
 
 }  // extern "C"

@@ -886,11 +886,6 @@ static int lx3_readout(const Lx3Args& x, void* stream) {
     hipLaunchKernelGGL(k_lx3_fwd<true>, dim3(x.ranges2 * ((x.Bp - x.kd_row0) / 128)), dim3(256), kLx3FwdLds, (hipStream_t)stream, x);
     return 0;
 }
-// items of the shard [item_begin + 1, item_begin + item_count] that lie within the first N
-static int shard_items(int N, int item_begin, int item_count) {
-    const int n = N - item_begin < item_count ? N - item_begin : item_count;
-    return n < 0 ? 0 : n;
-}
 
 extern "C" {
 

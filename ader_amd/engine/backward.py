@@ -142,10 +142,12 @@ class _Backward:
 
     def _check_teacher(self, teacher):
         """A teacher argument of a public entry point: the dense [*, Np] tensor or a TeacherRep -- which the catalog-sharded scheme
-        does not take (its readout reads teacher COLUMNS by item shard: the rows would have to be materialised shard by shard)."""
-        if isinstance(teacher, TeacherRep) and self.dp_world > 1 and self.dp_mode == "catalog":
-            raise RuntimeError("dp_mode='catalog' does not take a TeacherRep: the sharded teacher readout reads the dense [E, Np] "
-                               "logits by item shard -- pass Engine.teacher_logits' tensor, or use dp_mode='replicated'")
+        takes only with its rows' log-sum-exps (a rank regenerates its own COLUMNS of a row, ader_teacher_rows_shard: the lse over the
+        whole row cannot come from them).  Raised here, before any collective is issued."""
+        if isinstance(teacher, TeacherRep) and teacher.lse is None and self.dp_world > 1 and self.dp_mode == "catalog":
+            raise RuntimeError("dp_mode='catalog' takes a TeacherRep only with its rows' log-sum-exps: a rank regenerates its item "
+                               "shard's columns of a teacher row, not the row -- take the record with Engine.teacher_rep(..., lse=True), "
+                               "pass Engine.teacher_logits' tensor, or use dp_mode='replicated'")
 
     def _teacher_rows(self, trep, ex_trow, n_ex):
         """The teacher of this step from a TeacherRep: the rows of its n_ex exemplar rows are regenerated into workspace (the bits

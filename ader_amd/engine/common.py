@@ -137,10 +137,12 @@ class TeacherRep:
     """The teacher of a distilled period in its small form: instead of the logits [E, Np] of every stored exemplar
     (util.py:433), what they are a pure function of -- rep [E, H], the teacher's representation of each exemplar, and table [>= Np+1, H],
     a COPY of the item table as it stood when the teacher was taken (row 0 = the padding item; never a view of the live parameters, which
-    move with every step).  The rows a step needs are regenerated by ader_teacher_rows with the bits ader_logits_store gave them."""
-    __slots__ = ("rep", "table", "Np")
+    move with every step).  The rows a step needs are regenerated by ader_teacher_rows with the bits ader_logits_store gave them.
+    lse [E] (optional; Engine.teacher_rep(..., lse=True)): every row's log-sum-exp over its Np columns, the bits ader_row_lse gives the
+    dense row -- a constant of the period that the catalog-sharded step cannot regenerate, because a rank holds only its columns of a row."""
+    __slots__ = ("rep", "table", "Np", "lse")
 
-    def __init__(self, rep, table, Np):
+    def __init__(self, rep, table, Np, lse=None):
         Np = int(Np)
         for t, name in ((rep, "rep"), (table, "table")):
             _check(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous(),
@@ -148,16 +150,19 @@ class TeacherRep:
         _check(rep.shape[1] == table.shape[1] and rep.device == table.device and 1 <= Np <= table.shape[0] - 1,
                "TeacherRep: rep [E, H] and table [>= Np+1, H] on one device, Np >= 1 (got %s, %s, Np = %d)"
                % (tuple(rep.shape), tuple(table.shape), Np))
-        self.rep, self.table, self.Np = rep, table, Np
+        _check(lse is None or (isinstance(lse, torch.Tensor) and lse.dtype == torch.float32 and tuple(lse.shape) == (rep.shape[0],)
+                               and lse.is_contiguous() and lse.device == rep.device),
+               "TeacherRep: lse must be a contiguous float32 [E = %d] tensor on the device of rep" % rep.shape[0])
+        self.rep, self.table, self.Np, self.lse = rep, table, Np, lse
 
     def __len__(self):
         return int(self.rep.shape[0])
 
     def to(self, device):
-        return TeacherRep(self.rep.to(device), self.table.to(device), self.Np)
+        return TeacherRep(self.rep.to(device), self.table.to(device), self.Np, None if self.lse is None else self.lse.to(device))
 
     def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in (self.rep, self.table))
+        return sum(t.numel() * t.element_size() for t in (self.rep, self.table, self.lse) if t is not None)
 
     def key(self):
         """What a launch plan that holds the two pointers is keyed by (a raw pointer that is neither workspace nor a
@@ -179,6 +184,32 @@ class TeacherRep:
                  ptr(torch.empty(Bk, dtype=torch.int32, device=dev)), None, ptr(status), torch.cuda.current_stream().cuda_stream)
             _check(int(status.item()) == 0, "TeacherRep.rows: a row index >= %d" % E)
         return out[:n, :self.Np]
+
+
+def teacher_window_numel(n_rows, item_begin, S):
+    """Floats of the workspace teacher_window lays its two views over."""
+    return item_begin + n_rows * S
+
+
+def teacher_window(buf, n_rows, item_begin, S):
+    """A rank's column window of regenerated teacher rows, addressed the way the dense teacher is.  The two consumers of the
+    catalog-sharded step read their teacher operand as base[t * ldt + GLOBAL column], and only at these columns:
+      * ader_lx3_readout_shard (csrc/logits_bf16.hip) hands its kernels teacher + item_begin and n_loc columns -- k_lx3r (R3_TLOAD /
+        R3_TSLOW, clamped below Np) and k_lx3_fwd<true> (LBF_TLOAD, it + k < Np) read columns [item_begin, item_begin + n_loc);
+      * k_tab32x3<KD> under ader_tab_update_x3_kd_range (csrc/table_update_x3.hip, the tv[...] loads) reads teacher[trow * ldt + it] with
+        `it` a column of the rank's own tiles -- a second tile beyond the launch starts at or behind max_item >= Np -- and column 0 as a
+        dummy for it >= Np, whose value is never used.
+    Both read row 0 for a padding row (trow < 0).  So the rows need no storage left of the window: buf holds item_begin + n_rows * S
+    floats (teacher_window_numel), `block` [n_rows, S] = buf[item_begin:] is what ader_teacher_rows_shard fills (rows_win, ldr = S), and
+    `view` [n_rows, item_begin + S] with row stride S OVERLAPS itself so that view[t, item_begin + c] is block[t, c]: the teacher
+    operand, ldt = S.  view[t, 0] = buf[t * S] lies in an earlier row's block (or in the zeroed head of buf): in bounds, finite as long
+    as buf was zeroed when it was allocated.  S % 128 == 0 and a 16-byte aligned buf keep k_lx3r's 16-byte loads aligned.
+    Returns (view, block)."""
+    _check(buf.dim() == 1 and buf.is_contiguous() and buf.numel() >= teacher_window_numel(n_rows, item_begin, S)
+           and n_rows >= 1 and item_begin >= 0 and item_begin % 4 == 0 and S >= 128 and S % 128 == 0,
+           "teacher_window: a flat buffer of item_begin + rows * S elements, item_begin % 4 == 0, S a multiple of 128")
+    view = buf.as_strided((n_rows, item_begin + S), (S, 1))
+    return view, view[:, item_begin:]
 
 
 def issue_table_job(job, lists, table, item_num, H, shadow, rep_img, lr_t, b1, b2, eps, stream, tile_begin=0, tile_count=-1, bf16="sh"):

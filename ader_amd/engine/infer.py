@@ -69,14 +69,36 @@ class _Infer:
         self._refresh_stream()
         return self.logits(seq, max_item)
 
-    def teacher_rep(self, seq, max_item):
+    def teacher_rep(self, seq, max_item, lse=False, chunk_rows=None):
         """teacher_logits' small form: TeacherRep(the eval-mode representations [n, H], a copy of table rows 0..max_item, max_item) --
-        what the logits [n, max_item] are a pure function of; a distilled step regenerates the rows it needs (ader_teacher_rows)."""
+        what the logits [n, max_item] are a pure function of; a distilled step regenerates the rows it needs (ader_teacher_rows).
+        lse=True adds the record's lse [n]: the log-sum-exp of every row over its max_item columns, bit for bit ader_row_lse of
+        teacher_logits' row -- what the catalog-sharded step needs beside its column window (_train_step_catalog).  The rows pass
+        chunk_rows at a time (a multiple of 64; None: as many as keep the workspace under 0.8 GB, at most 1024) through one
+        workspace [chunk_rows, max_item padded to 4] and ader_teacher_rows' lse output; nothing of them is kept."""
         self._refresh_stream()
-        rep = self.encode(seq)
         N = int(max_item)
         _check(1 <= N <= self.item_num, "max_item must be in [1, item_num = %d] (got %d)" % (self.item_num, N))
-        return TeacherRep(rep, self.param("emb")[:N + 1].detach().clone(), N)
+        ldr = (N + 3) // 4 * 4
+        chunk = max(64, min(1024, 200_000_000 // ldr // 64 * 64)) if chunk_rows is None else int(chunk_rows)
+        _check(chunk >= 64 and chunk % 64 == 0, "teacher_rep: chunk_rows must be a positive multiple of 64 (got %r)" % (chunk_rows,))
+        rep = self.encode(seq)
+        trep = TeacherRep(rep, self.param("emb")[:N + 1].detach().clone(), N)
+        if not lse:
+            return trep
+        E, dev, st = rep.shape[0], self.device, self._stream()
+        out = torch.empty(E, dtype=torch.float32, device=dev)
+        chunk = min(chunk, (max(E, 1) + 63) // 64 * 64)
+        rows = torch.empty((chunk, ldr), dtype=torch.float32, device=dev)
+        trl, z = torch.empty(chunk, dtype=torch.int32, device=dev), torch.empty(chunk, dtype=torch.float32, device=dev)
+        ex = torch.arange(E, dtype=torch.int32, device=dev)
+        for s in range(0, E, chunk):
+            n = min(chunk, E - s)
+            Bk = (n + 63) // 64 * 64
+            call("ader_teacher_rows", ptr(trep.rep), ptr(trep.table), ptr(ex[s:]), n, Bk, E, self.H, N, ptr(rows), ldr, ptr(trl), ptr(z),
+                 None, st)
+            out[s:s + n] = z[:n]
+        return TeacherRep(trep.rep, trep.table, N, out)
 
     def rank_targets(self, seq, pos, max_item, dtype=None, cand_cap=None):
         """0-based rank of pos[b] among items 1..N for every row (Evaluator path, util.py:323-325) -> int32 numpy [n].

@@ -83,7 +83,10 @@ class ExemplarStore:
 
     def tensors(self):
         """Every tensor / array the store holds."""
-        return [self.rows] + ([self.teacher.rep, self.teacher.table] if _is_rep(self.teacher) else [self.teacher])
+        if not _is_rep(self.teacher):
+            return [self.rows, self.teacher]
+        t = self.teacher
+        return [self.rows, t.rep, t.table] + ([t.lse] if getattr(t, "lse", None) is not None else [])
 
     def __len__(self):
         return int(self.rows.shape[0])
@@ -100,8 +103,11 @@ class ExemplarStore:
         rows = torch.as_tensor(np.ascontiguousarray(np.asarray(self.rows), dtype=np.int32))
         if _is_rep(self.teacher):
             t = self.teacher
-            torch.save({"rows": rows, "rep": t.rep.detach().cpu().contiguous(), "table": t.table.detach().cpu().contiguous(),
-                        "Np": int(t.Np), "max_item": int(self.max_item)}, path)
+            d = {"rows": rows, "rep": t.rep.detach().cpu().contiguous(), "table": t.table.detach().cpu().contiguous(),
+                 "Np": int(t.Np), "max_item": int(self.max_item)}
+            if getattr(t, "lse", None) is not None:         # (the rows' log-sum-exps: a record taken for the catalog-sharded step)
+                d["lse"] = t.lse.detach().cpu().contiguous()
+            torch.save(d, path)
             return path
         lg = self.logits.detach().cpu().contiguous() if hasattr(self.logits, "detach") else torch.as_tensor(np.asarray(self.logits))
         torch.save({"rows": rows, "logits": lg, "max_item": int(self.max_item)}, path)
@@ -113,7 +119,7 @@ class ExemplarStore:
         d = torch.load(path, weights_only=True)        # tensors and plain numbers only: nothing is unpickled
         if "rep" in d:
             from .engine.common import TeacherRep
-            t = TeacherRep(d["rep"], d["table"], int(d["Np"]))
+            t = TeacherRep(d["rep"], d["table"], int(d["Np"]), d.get("lse"))
             return cls(d["rows"].numpy(), t if device is None else t.to(device), int(d["max_item"]))
         lg = d["logits"]
         if device is not None:          # on the device the rows keep the 16-byte aligned stride Engine.teacher_logits gives them
@@ -174,7 +180,13 @@ class ExemplarGenerator:
     def _make_store(self, model, sel_rows):
         """self.store <- the selected rows with their teacher in the form asked for; returns the logits-by-exemplar of the views."""
         seq = sel_rows[:, :self.maxlen]
-        teacher = (model.engine.teacher_rep if self.teacher_form == "rep" else model.engine.teacher_logits)(seq, self.max_item)
+        eng = model.engine
+        if self.teacher_form == "rep":
+            # an engine that will step catalog-sharded reads COLUMNS of the regenerated rows: it needs the rows' log-sum-exps stored
+            sharded = getattr(eng, "dp_world", 1) > 1 and getattr(eng, "dp_mode", None) == "catalog"
+            teacher = eng.teacher_rep(seq, self.max_item, lse=True) if sharded else eng.teacher_rep(seq, self.max_item)
+        else:
+            teacher = eng.teacher_logits(seq, self.max_item)
         self.store = ExemplarStore(sel_rows, teacher, self.max_item)
         return self.store.logits
 

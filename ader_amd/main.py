@@ -59,7 +59,9 @@ _BUILD_FLAGS = (
     ("pack_sessions", "auto", str, ("auto", "on", "off")),
     ("dp_mode", "auto", str, ("auto", "replicated", "catalog")),
     # what the exemplar store keeps of the previous period's model: "logits" = its logits [E, Np] (util.py:433), "rep" = its
-    # representations [E, H] and a copy of its item table; the rows a step needs are regenerated, bit for bit (engine.TeacherRep)
+    # representations [E, H] and a copy of its item table; the rows a step needs are regenerated, bit for bit (engine.TeacherRep).
+    # With a catalog-sharded table (dp_mode resolves to "catalog") the record also keeps the rows' log-sum-exps and every rank
+    # regenerates only the columns of its own items (ExemplarGenerator._make_store, Engine._train_step_catalog)
     ("teacher_form", "logits", str, ("logits", "rep")),
     ("fed_steps", True, bool, "single GPU with --device_feed and --fixed_batches: the batch is cut on the GPU by the step's first launch "
                               "and the step is one native call (Engine.train_step_fed); False: batches assembled by torch, as data-parallel runs do"),

@@ -18,6 +18,9 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
   ader::teacher_rows(trep, temb, ex_trow, Np)                  -> (rows, trow_local)   teacher logits of a step's exemplar rows from
                                                                          stored representations + a table snapshot: the bits of
                                                                          ader_logits_store (util.py:433, ADER.py:134-135)
+  ader::teacher_rows_shard(trep, temb, ex_trow, Np, item_begin, item_count) -> (rows, trow_local)   the same rows' columns of the items
+                                                                         [item_begin + 1, item_begin + item_count] below Np: what a rank
+                                                                         of the catalog-sharded table reads of them
   ader::herding_select(rep, seg, quota, max_steps)             -> (sel, cnt)   util.py:401-434
 
 Trainable surface (second half of this file; every forward has an autograd formula over its `_bwd` operator):
@@ -244,6 +247,38 @@ def teacher_rows(trep: torch.Tensor, temb: torch.Tensor, ex_trow: torch.Tensor, 
 def _(trep, temb, ex_trow, Np):
     Bk = (ex_trow.shape[0] + 63) // 64 * 64
     return trep.new_empty((Bk, (Np + 3) // 4 * 4))[:, :Np], ex_trow.new_empty(Bk)
+
+
+@torch.library.custom_op("ader::teacher_rows_shard", mutates_args=())
+def teacher_rows_shard(trep: torch.Tensor, temb: torch.Tensor, ex_trow: torch.Tensor, Np: int, item_begin: int,
+                       item_count: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """teacher_rows for a rank of the catalog-sharded table: only the columns of items [item_begin + 1, item_begin + item_count] below
+    Np -> (rows float32 [Bk, n_loc], a view of a buffer whose row stride is n_loc padded to 4; trow_local int32 [Bk]): rows[e, c] is, bit
+    for bit, teacher_rows' rows[e, item_begin + c].  n_loc = 0 (a shard that owns no item below Np) gives [Bk, 0].  item_begin % 4 == 0.
+    A teacher row >= E raises (one synchronisation to read the status)."""
+    _chk(trep, "trep", torch.float32, 2), _chk(temb, "temb", torch.float32, 2), _chk(ex_trow, "ex_trow", torch.int32, 1)
+    E, H = trep.shape
+    n = ex_trow.shape[0]
+    if (temb.shape[1] != H or H > HP or not (1 <= Np <= temb.shape[0] - 1) or n < 1 or item_begin < 0 or item_begin % 4 != 0
+            or item_count < 0):
+        raise RuntimeError("ader::teacher_rows_shard: bad shapes (trep %s, temb %s, Np = %d, n = %d, items [%d + 1, %d + %d])"
+                           % (tuple(trep.shape), tuple(temb.shape), Np, n, item_begin, item_begin, item_count))
+    n_loc = max(0, min(Np - item_begin, item_count))
+    Bk, ldr = (n + 63) // 64 * 64, (n_loc + 3) // 4 * 4
+    dev = trep.device
+    rows, trl = torch.empty(Bk, ldr, device=dev), torch.empty(Bk, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    call("ader_teacher_rows_shard", ptr(trep), ptr(temb), ptr(ex_trow), n, Bk, E, H, Np, item_begin, item_count, ptr(rows), ldr, ptr(trl),
+         ptr(status), _st())
+    if int(status.item()):
+        raise RuntimeError("ader::teacher_rows_shard: a teacher row >= E = %d in ex_trow" % E)
+    return rows[:, :n_loc], trl
+
+
+@teacher_rows_shard.register_fake
+def _(trep, temb, ex_trow, Np, item_begin, item_count):
+    Bk, n_loc = (ex_trow.shape[0] + 63) // 64 * 64, max(0, min(Np - item_begin, item_count))
+    return trep.new_empty((Bk, (n_loc + 3) // 4 * 4))[:, :n_loc], ex_trow.new_empty(Bk)
 
 
 @torch.library.custom_op("ader::herding_select", mutates_args=())

@@ -272,6 +272,16 @@ int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, in
 int ader_teacher_ranges(int Np, int Bk);
 int ader_teacher_rows(const float* trep, const float* temb, const int* ex_trow, int n_ex, int Bk, int E, int H, int Np, float* rows,
                       long ldr, int* trow_local, float* lse, int* status, void* stream);
+/* The same rows for a rank of the catalog-sharded scheme (util.py:433, ADER.py:134-135 with the item table sharded): only the columns of
+ * the rank's items.  With n_loc = the items of [item_begin + 1, item_begin + item_count] that are <= Np: rows_win[e * ldr + c], c in
+ * [0, n_loc), = bit for bit the float32 ader_teacher_rows writes at column item_begin + c of row e (padding rows 0.0f; a teacher row >= E
+ * is written as a padding row and flagged, as above); trow_local[e] = e or -1.  Nothing outside [0, n_loc) of a row is written, and
+ * n_loc == 0 writes trow_local only.  ex_trow is the all-gathered list of every rank's exemplar rows (-1 inside each rank's padded block),
+ * so n_ex and Bk are world x the per-rank counts.  rows_win on a 16-byte boundary takes the vector stores.  No lse: a row's log-sum-exp
+ * runs over all Np columns and is a constant of the period (TeacherRep.lse).  Enqueue only.
+ * -2 when item_begin < 0 or item_begin % 4 != 0, item_count < 0, ldr % 4 != 0, ldr < n_loc, H > 160, Bk % 64 != 0, n_ex > Bk or Np < 1. */
+int ader_teacher_rows_shard(const float* trep, const float* temb, const int* ex_trow, int n_ex, int Bk, int E, int H, int Np,
+                            int item_begin, int item_count, float* rows_win, long ldr, int* trow_local, int* status, void* stream);
 
 /* ---- bf16-MFMA variant of the one-hot softmax CE (fp32 master table, fp32 accumulate/softmax): ADER.py:88-93 ------ */
 /* Bp % 128 == 0, H even.  Scratch: rep_bf Bp*168 bf16; pm, pl: R*Bp floats; pO: R*Bp*160 floats, R = ader_lbf_ranges(N,Bp).
