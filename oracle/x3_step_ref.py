@@ -100,7 +100,7 @@ def loss_tail_terms(inp, dt=torch.float64):
 
 def reference(inp):
     """Closed forms in float64 and their term sums.  Returns a dict: lse, rowloss [B]; loss; drep [B,H]; g [N,H] (table rows 1..N);
-    c [B,N] the logit gradient; s_lse, s_rowloss [B], s_loss, s_drep [B], s_g [N] the term sums."""
+    c [B,N] the logit gradient; s_lse, s_rowloss [B], s_loss, s_drep [B], s_g [N] the term sums (t_g [N,H]: those of g per column)."""
     dt = torch.float64
     N = inp["N"]
     E, rep, w = inp["E0"][1:N + 1].to(dt), inp["rep"].to(dt), inp["w"].to(dt)
@@ -123,7 +123,7 @@ def reference(inp):
     s_rowloss = w.abs() * (lse.abs() + tterm.abs())
     return dict(lse=lse, rowloss=rowloss, loss=rowloss.sum(), drep=drep, g=g, c=c,
                 s_lse=lse.abs().clamp_min(1.0), s_rowloss=s_rowloss, s_loss=s_rowloss.sum(),
-                s_drep=(c.abs() @ E.abs()).max(-1).values, s_g=s_g.max(-1).values)
+                s_drep=(c.abs() @ E.abs()).max(-1).values, s_g=s_g.max(-1).values, t_g=s_g)
 
 
 def row_errors(x, ref, scale):
@@ -592,6 +592,17 @@ def _worst(name, excess):
     return "%s: element (row %d, col %d) exceeds its bound by %.3g" % (name, i // excess.shape[1], i % excess.shape[1], float(excess.max()))
 
 
+# CONTRACTED ADAM.  The bounds below count the roundings of the three lines written as separately rounded operations (k_tab32x3 is
+# compiled under fp contract(off)):  m' = m + rd(rd(g - m) omb1): 3 roundings, each at most 2^-24 of a value <= |m| + |g|;  v' likewise
+# with rd(g g) first: 4 roundings <= 2^-24 (v + g^2) each: 2^-21 = 8 x 2^-24 leaves room for both.  The bf16-grade kernels (k_tab16, the
+# resident k_tab_upd, ader_adam_step) are NOT under that pragma, so the compiler may contract
+#     m' = fma(g - m, omb1, m)                  2 roundings: the difference, the fma
+#     v' = fma(fma(g, g, -v), omb2, v)          2 roundings: fma(g, g, -v) = rd(g^2 - v), error <= 2^-24 |g^2 - v| <= 2^-24 (v + g^2)
+# An fma rounds ONCE where the separate form rounds twice, and every intermediate keeps its magnitude bound (|g - m| <= |m| + |g|,
+# |g^2 - v| <= v + g^2): each contracted line carries a SUBSET of the roundings counted above, so the same 2^-21 bounds hold for any
+# mixture of contracted and separate operations.  From zero state contraction changes nothing at all: fma(g, omb1, 0) = rd(g omb1) and
+# fma(rd(g g), omb2, 0) = rd(rd(g^2) omb2) are the separately rounded values.  theta' = theta - rd(m' lr_t) / (sqrt(v') + eps) has no
+# product feeding an addition (the division stands between them): nothing to contract, check_theta holds as stated.
 def check_theta(theta0, theta1, m1, v1, N, k):
     """Always: theta' against theta0 - u, u = lr_t m' / (sqrt(v') + eps) from the device's own m', v':
     |theta' - (theta0 - u)| <= 2^-23 |theta0| + 2e-6 |u|  (one float32 subtraction; 2e-6 = five times the kernel's statement of its
@@ -633,9 +644,14 @@ def check_adam_preloaded(theta0, m0, v0, theta1, m1, v1, g, N, k):
     check_theta(theta0, theta1, m1, v1, N, k)
 
 
+TABLES = ("theta", "m", "v", "shadow")
+
+
 def check_untouched(before, after, N):
-    """Rows 0 and > N of theta, m and v must be BITWISE what they were (before / after: triples of full [V,H] tables)."""
-    for name, b, a in zip(("theta", "m", "v"), before, after):
+    """Rows 0 and > N of theta, m and v must be BITWISE what they were (before / after: triples of full [V,H] tables -- or, behind a
+    bf16 update, 4-tuples whose last member is the bf16 shadow [rows, 168]: its row i belongs to table row i, and the rows it holds
+    beyond the table must not change either)."""
+    for name, b, a in zip(TABLES, before, after):
         b = torch.as_tensor(b).detach().cpu().contiguous().view(torch.int32)
         a = torch.as_tensor(a).detach().cpu().contiguous().view(torch.int32)
         for lo, hi in ((0, 1), (N + 1, b.shape[0])):
@@ -680,8 +696,9 @@ def range_update_emulate(theta0, m0, v0, g, N, k, shards, fault=None, frank=None
 
 
 def check_range_untouched(before, after, lo, hi, rank):
-    """A rank's launch must leave every table row outside lo..hi (1-based, inclusive; empty: all rows) BITWISE what it was."""
-    for name, b, a in zip(("theta", "m", "v"), before, after):
+    """A rank's launch must leave every table row outside lo..hi (1-based, inclusive; empty: all rows) BITWISE what it was (triples,
+    or 4-tuples with the bf16 shadow: check_untouched)."""
+    for name, b, a in zip(TABLES, before, after):
         b = torch.as_tensor(b).detach().cpu().contiguous().view(torch.int32)
         a = torch.as_tensor(a).detach().cpu().contiguous().view(torch.int32)
         diff = (b != a).any(-1)

@@ -59,6 +59,14 @@ def relu_masks_of(eng):
     return out
 
 
+def assert_shadow_is_bf16_of_theta(eng):
+    """The bf16 shadow of the table behind whatever kernel wrote it last: shadow[:, :H] == bf16(theta) BITWISE, padding columns zero."""
+    sh = eng.shadow.view(-1, 168)[:eng.V].cpu()
+    emb = eng.param("emb").cpu()
+    assert torch.equal(sh[:, :eng.H].contiguous().view(torch.int16), emb.bfloat16().view(torch.int16))
+    assert not bool((sh[:, eng.H:].contiguous().view(torch.int16) != 0).any())
+
+
 def nerr(a, b, floor=0.0):
     """max |a-b| normalised by max(|b|max, floor).  `floor` guards tensors whose true value is ~0 (e.g. the key bias
     gradient: softmax is shift-invariant, so d/d(bk) is exactly zero up to float32 noise)."""
@@ -576,6 +584,8 @@ def test_fused_table_adam_equals_unfused_step(cfg, ld):
             torch.cuda.synchronize()
             sh = eng.shadow.float().cpu().numpy().copy() if eng.shadow is not None else np.zeros(1)
             snaps.append((eng.theta.cpu().numpy().copy(), eng.adam_m.cpu().numpy().copy(), eng.adam_v.cpu().numpy().copy(), sh))
+        if eng.shadow is not None:                     # each engine on its own, whatever the summation order
+            assert_shadow_is_bf16_of_theta(eng)
         states.append(snaps)
     (a1, a2), (b1, b2) = states
     # after ONE step from identical state the two paths differ by summation order only
@@ -638,6 +648,7 @@ def test_both_bf16_update_forms_agree(cfg):
         torch.cuda.synchronize()
         out.append((eng.theta.cpu().numpy().copy(), eng.adam_m.cpu().numpy().copy(), eng.adam_v.cpu().numpy().copy(),
                     eng.shadow.float().cpu().numpy().copy()))
+        assert_shadow_is_bf16_of_theta(eng)
     a, b = out
     assert nerr(a[1], b[1]) < 2e-5 and nerr(a[2], b[2]) < 2e-5
     d = np.abs(a[0] - b[0])
@@ -829,6 +840,8 @@ def test_train_step_is_bitwise_reproducible(ld, variant):
             eng.train_step(seq, pos, N, 5e-4, rate=0.3)
         torch.cuda.synchronize()
         sh = eng.shadow.clone() if eng.shadow is not None else torch.zeros(1)
+        if eng.shadow is not None:
+            assert_shadow_is_bf16_of_theta(eng)
         finals.append((eng.theta.clone(), eng.adam_m.clone(), eng.adam_v.clone(), sh, float(eng.loss.item())))
     for x, y in zip(finals[0][:4], finals[1][:4]):
         assert torch.equal(x, y)
