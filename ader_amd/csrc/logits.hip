@@ -17,6 +17,7 @@
 // Row descriptors (RowInfo): label, ncol (N for one-hot rows, Np for distilled rows), weight
 // (1/B_train or lambda/B_ex, global counts under data parallelism), teacher row + teacher log-sum-exp.
 #include "common.h"
+#include "topk_key.h"
 #include "../../include/ader_hip.h"
 
 #define HP 160
@@ -449,7 +450,6 @@ __global__ __launch_bounds__(256) void k_pair_logit_rank(LogitArgs a, const floa
 // (The MFMA chain starts from +0 and rounds to nearest, so it never yields -0; topk_key still folds -0 onto +0, as == does.)
 // The best k of a set under a total order do not depend on the order the set was visited in: that is the whole determinism argument --
 // LDS atomics only hand out buffer slots, the kept SET is the same however they land, and every output is derived from sorted keys.
-typedef unsigned long long u64;
 #define TOPK_KMAX 64
 
 struct TopkArgs {
@@ -464,16 +464,7 @@ struct TopkArgs {
     float* scores;         // [B,k]
 };
 
-__device__ __forceinline__ u64 topk_key(float s, int item1) {
-    uint32_t u = __float_as_uint(s + 0.0f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((u64)u << 32) | (uint32_t)~(uint32_t)item1;
-}
-__device__ __forceinline__ float topk_score(u64 key) {
-    const uint32_t u = (uint32_t)(key >> 32);
-    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
-}
-__device__ __forceinline__ int topk_item(u64 key) { return (int)~(uint32_t)key; }
+// (topk_key / topk_score / topk_item: topk_key.h, shared with the x3 filter of logits_x3.hip)
 
 // Workgroup = (64-row chunk, contiguous range of 64-item tiles), block -> (range, chunk) as in k_logits_bwd_drep.  The chunk's rep rows
 // are staged once; the range's table tiles stream through E_l, the next tile's loads in flight (registers) under the current tile's MFMAs.

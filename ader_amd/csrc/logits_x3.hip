@@ -19,6 +19,7 @@
 // Output partials (pm, pl, pO per item range) and the merge (k_lbf_combine<true>) are those of k_lx3_fwd.  gfx950 only.
 #include "lbf_common.h"
 #include "x3_image.h"
+#include "topk_key.h"
 #include "../../include/ader_hip.h"
 
 #define F3_FB 32                   // items per streamed block
@@ -920,6 +921,292 @@ __global__ __launch_bounds__(256, 2) void k_lx3k(RankX3Args a) {
     if (hh == 0 && cnt) atomicAdd(a.rank + b, cnt);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Top-K recommendation on the bf16 matrix cores, byte-identical to ader_topk_items (k_topk_tile + k_topk_merge, logits.hip): the same
+// items in the same order (score descending, id ascending) and the same float32 score bits, by construction and not by tolerance.
+// k_lx3t computes every catalog logit at x3 grade (s3) and keeps, per row, a small SUPERSET of the exact top-k; k_topk3_finish merges
+// the ranges' sets, recomputes the kept (row, item) pairs on the exact chain and selects the best k by the exact key.
+//
+// Why it is exact.  s = exact-chain score, s3 = x3 score, d = delta_b = KAPPA |rep_b| Emax (norms rounded up: k_rank_delta's value, the
+// derivation above), so |s3 - s| < d / 2.  Let t3 be the k-th largest s3 over ANY subset U of the row's live items that holds >= k.
+//   1. The k items of U with s3 >= t3 each have s > t3 - d/2: the row's exact k-th best score is >= t3 - d/2.
+//   2. Any item of the exact top-k therefore has s3 > t3 - d.
+//   3. So C = {n : !(s3_n < t3 - d)} contains the exact top-k -- for the running t3 of any prefix of the catalog and for the final one
+//      (t3 only grows as U grows, and every C is cut with a t3 of a subset of the live items).
+//   4. Every member of C outside the exact top-k has a smaller exact key than every member inside it: the best k of C by the exact
+//      64-bit key (topk_key of the exact score and id, a total order) ARE the answer.
+// The test is written !(s3 < lo): a NaN edge keeps everything.  The edge lo = t3 - d is computed in float32; its rounding
+// (<= 2^-24 (|t3| + d) <= 2^-10.9 d, as for the rank filter's edges) is inside KAPPA's factor of two over the derived 2^-14.1.
+// Where the guarantee cannot be given the row is marked in status[b] and the caller takes ader_topk_items' answer for it: a kept set
+// larger than k + band keys (ties or near-ties across rank k: a constant row, a zero rep row), or a NaN s3 (non-finite operands: the
+// error bound says nothing about them).
+//
+// k_lx3t: k_lx3k's blocking, staging and S^T phase; after each block a lane holds 16 x3 scores of its row and runs k_topk_tile's
+// filter / append / compact on keys of (order-preserving s3 bits, complemented id), with one change: a compaction keeps EVERY key with
+// !(s3 < t3 - d), t3 = the score of the k-th best key, not "the best k".  Per row: a buffer of k + band + 32 keys, its count (LDS), its
+// lower edge lo and its overflow flag (registers of the lane pair that owns the row).  A wave owns its 32 rows' buffers outright -- both
+// lanes that append to a row and the 64 lanes that compact it belong to it -- so compaction is decided by a wave ballot, with no
+// workgroup barrier, and one wave's LDS operations are performed in order.
+// INVARIANT: every row enters a block with cnt <= keep = k + band; a 32-item block proposes at most 32 keys per row; every row with
+// cnt > keep is compacted to <= keep before the next block (more than keep inside the band: overflow, cut to the best keep): cnt <=
+// keep + 32 = the buffer's size, always -- also when every item beats the threshold (scores increasing with the id).
+// LDS: the three block images (67.5 KiB) + 128 rows x (keep + 32) keys x 8 B.  At k = 20, band = 16 that is 135.5 KiB: one workgroup
+// per CU whatever k (two would need the buffers in 12.5 KiB = 12 keys per row).  Taken as it is: a retry loop with a smaller slack costs
+// a workgroup barrier per block, and 64-row workgroups halve the flops per staged table byte; what it costs -- one wave per SIMD, no
+// second workgroup to hide the barriers and the compactions -- is measured (0.60 of k_topk_tile at N = 10^6, 1.5 - 2.4 x
+// it at the shipped catalogs, where a workgroup walks ~25 - 42 blocks and its rows' edges are loose for most of them).  160 KiB bounds
+// keep + 32 <= 88: TK3_KMAX = 40 with band <= 16; a larger k takes the f32 kernels.  Registers: k_lx3k's plan + ~12 of row state
+// (212 compiled, no scratch).
+#define TK3_KMAX 40
+#define TK3_BANDMAX 16
+#define TK3_LDE 162                 // logits.hip's LDE: the [64][LDE] operand layout of the exact chain
+
+struct TopkX3Args {
+    const float* rep; const float* emb1; int vrows; // fp32 rep [B,H]; fp32 table, row of item 1; rows available from it (item_num)
+    const bf16* rep_hi; const bf16* rep_lo;         // [Bp][LDR] (k_lx3_prep)
+    int B, Bp, H, N, ranges, k, keep;               // keep = k + band
+    const int* ncol;                                // [Bp] N for real rows, 0 for padding rows
+    const int* seen; int seen_ld;                   // [B, seen_ld] 1-based ids never to be returned (0 = none), or NULL
+    const float* delta;                             // [Bp] band width d (k_rank_delta)
+    u64* part3;                                     // [ranges][Bp][keep] kept x3 keys, zeros behind a row's count
+    int* status;                                    // [Bp] != 0: the row's result is not guaranteed (zeroed by the launcher)
+    int* diag;                                      // [0] kept pairs, [1] overflowed rows, [2] float bits of max |s3 - s| / d
+    int* items; float* scores;                      // [B,k]
+};
+
+__global__ __launch_bounds__(256, 1) void k_lx3t(TopkX3Args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [3 buffers][block image] | buf [128][keep + 32] | cnt [128]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r32 = lane & 31, hh = lane >> 5;
+    const int nchunk = a.Bp / G3_ROWS;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int range = xcd + 8 * (slot / nchunk);           // as k_lx3g: the row chunks of an item range sit on one XCD
+    const int bc = slot % nchunk;
+    if (range >= a.ranges) return;
+    const int H = a.H, N = a.N;
+    const int nblk_all = (N + F3_FB - 1) / F3_FB;
+    const int per = (nblk_all + a.ranges - 1) / a.ranges;
+    const int blk_begin = range * per, blk_end = min(nblk_all, blk_begin + per);
+    const int nb_blocks = max(0, blk_end - blk_begin);
+    const int b0 = bc * G3_ROWS + wave * 32;
+    const int k = a.k, keep = a.keep, ldb = keep + F3_FB;
+    u64* buf = (u64*)(smem_raw + 3 * X3B_IMG_B);
+    int* cnt = (int*)(buf + G3_ROWS * ldb);
+    for (int i = tid; i < 3 * X3B_IMG_B / 16; i += 256) ((uint4*)smem_raw)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (tid < G3_ROWS) cnt[tid] = 0;
+    bf16x8 rh[10], rl[10];
+#pragma unroll
+    for (int ks = 0; ks < 10; ++ks) {
+        rh[ks] = *(const bf16x8*)(a.rep_hi + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
+        rl[ks] = *(const bf16x8*)(a.rep_lo + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
+    }
+    // this lane's batch row (shared with lane ^ 32, which holds the block's other 16 items): live items [0, nc) without the seen ids
+    const int b = b0 + r32, wrow = wave * 32 + r32;
+    const int nc = min(a.ncol[b], N);
+    const float dl = a.delta[b];
+    u64* mybuf = buf + wrow * ldb;
+    int* mycnt = cnt + wrow;
+    float lo = -INFINITY;                                  // the row's lower edge t3 - d at its last compaction
+    int ovf = 0;
+    // seen ids: the lane pair folds the row's ids that fall into the block into a 32-bit mask; rows without an id in this item range
+    // (most, when the range is a small part of the catalog) never look again
+    const int* srow = (a.seen && b < a.B) ? a.seen + (size_t)b * a.seen_ld : nullptr;
+    int any_seen = 0;
+    if (srow)
+        for (int t = hh; t < a.seen_ld; t += 2)
+            any_seen |= (unsigned)(srow[t] - 1 - blk_begin * F3_FB) < (unsigned)(nb_blocks * F3_FB);        // id 0 wraps: never inside
+    any_seen |= __shfl_xor(any_seen, 32, 64);
+    // staging locals of F3_LOAD / F3_STORE: as k_lx3g
+    const int nfull = H >> 3, rem = H & 7;
+    const int it_ = 8 * wave + (lane & 7), kc0 = lane >> 3;
+    const int voff = 4 * (it_ * H + 8 * kc0);
+    const int voffp = voff + 4 * (rem - 4);
+    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
+    const int dst0 = X3B_KC * kc0 + 16 * it_;
+    f32x4_t sa[F3_RND], sb[F3_RND];
+    G3_A_OFF()
+    if (nb_blocks > 0) F3_LOAD(blk_begin);
+    __syncthreads();                                       // zero fill done
+    if (nb_blocks > 0) F3_STORE(0);
+    if (nb_blocks > 1) { F3_LOAD(blk_begin + 1); F3_STORE(1); }
+    int bcur = 0;                                          // i % 3
+    for (int i = 0; i < nb_blocks; ++i) {
+        __syncthreads();                                   // blocks i and i + 1 are in LDS; every wave is done with block i - 1
+        const bool more = i + 2 < nb_blocks;
+        if (more) F3_LOAD(blk_begin + i + 2);
+        const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
+        const int i0 = (blk_begin + i) * F3_FB;
+        f32x16 S;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) S[j] = 0.0f;
+        bf16x8 fa[2][2];
+        G3_LOADA(fa[0], Bh, 0);
+        G3_LOADA(fa[1], Bh, 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ks = 0; ks < 10; ++ks) {
+            bf16x8* A_ = fa[ks & 1];                             // {hi, lo}
+            S = mfma_bf16(A_[1], rh[ks], S);
+            S = mfma_bf16(A_[0], rl[ks], S);
+            S = mfma_bf16(A_[0], rh[ks], S);
+            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bh, ks + 2);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (more) F3_STORE(g3_buf_new(bcur));
+        unsigned sm = 0u;                                  // bit i: item i0 + i is in the row's seen list
+        if (any_seen)
+            for (int t = hh; t < a.seen_ld; t += 2) {
+                const unsigned d = (unsigned)(srow[t] - 1 - i0);
+                if (d < (unsigned)F3_FB) sm |= 1u << d;
+            }
+        sm |= __shfl_xor(sm, 32, 64);
+        // filter + append: a key goes in unless its x3 score is provably outside the band below the row's running k-th best
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int il = acc_row(j, hh);
+            const float s = S[j];
+            if (i0 + il < nc && !((sm >> il) & 1u) && !(s < lo)) {
+                if (s != s) ovf = 1;                       // a NaN x3 score: the bound does not cover it
+                else {
+                    const int p = atomicAdd(mycnt, 1);     // p < keep + 32 (the invariant above)
+                    mybuf[p] = topk_key(s, i0 + il + 1);
+                }
+            }
+        }
+        // compact: the wave's rows that hold more than keep keys, one after the other, all 64 lanes on a row
+        const u64 need = __ballot(*mycnt > keep);
+        unsigned rows = (unsigned)need | (unsigned)(need >> 32);
+        while (rows) {
+            const int rr = __ffs(rows) - 1;
+            rows &= rows - 1;
+            u64* bp = buf + (wave * 32 + rr) * ldb;
+            const int n = cnt[wave * 32 + rr];             // keep < n <= keep + 32 <= 88: at most two keys per lane
+            const u64 e0 = lane < n ? bp[lane] : 0, e1 = lane + 64 < n ? bp[lane + 64] : 0;
+            // keys of a row are distinct: rank = number of larger keys.  The keys are broadcast from the lanes that hold them (the index
+            // is wave-uniform: v_readlane), not read back from LDS one by one: with one wave per SIMD nothing hides that latency
+            const unsigned e0l = (unsigned)e0, e0h = (unsigned)(e0 >> 32), e1l = (unsigned)e1, e1h = (unsigned)(e1 >> 32);
+            int r0 = 0, r1 = 0;
+            for (int q = 0; q < min(n, 64); ++q) {
+                const u64 x = ((u64)(unsigned)__builtin_amdgcn_readlane((int)e0h, q) << 32) | (unsigned)__builtin_amdgcn_readlane((int)e0l, q);
+                r0 += x > e0; r1 += x > e1;
+            }
+            for (int q = 64; q < n; ++q) {
+                const u64 x = ((u64)(unsigned)__builtin_amdgcn_readlane((int)e1h, q - 64) << 32) | (unsigned)__builtin_amdgcn_readlane((int)e1l, q - 64);
+                r0 += x > e0; r1 += x > e1;
+            }
+            // t3 = the score of the key of rank k - 1 (n > keep >= k: there is one), from the lane that holds it
+            const u64 h0 = __ballot(lane < n && r0 == k - 1), h1 = __ballot(lane + 64 < n && r1 == k - 1);
+            const u64 tk = h0 ? __shfl(e0, __ffsll(h0) - 1, 64) : __shfl(e1, __ffsll(h1) - 1, 64);
+            const float nlo = topk_score(tk) - __shfl(dl, rr, 64);
+            // no key is a NaN, so the kept keys are the head of the sorted order: a kept key's rank is its new place
+            const bool k0 = lane < n && !(topk_score(e0) < nlo), k1 = lane + 64 < n && !(topk_score(e1) < nlo);
+            const int m = __popcll(__ballot(k0)) + __popcll(__ballot(k1));
+            // in place: every key was read into a register before the first store, and one wave's LDS operations are performed in order
+            if (k0 && r0 < keep) bp[r0] = e0;
+            if (k1 && r1 < keep) bp[r1] = e1;
+            if (lane == 0) cnt[wave * 32 + rr] = min(m, keep);
+            if (r32 == rr) { lo = nlo; ovf |= m > keep; }  // more than keep keys inside the band: the row's result is discarded
+        }
+        bcur = g3_buf_next(bcur);
+    }
+    ovf |= __shfl_xor(ovf, 32, 64);
+    if (hh == 0 && ovf) atomicOr(a.status + b, 1);
+    u64* o = a.part3 + ((size_t)range * a.Bp + b0) * keep;  // the wave's 32 rows (an empty range writes zeros: no candidate)
+    for (int i = lane; i < 32 * keep; i += 64) {
+        const int row = i / keep, j = i - row * keep;
+        o[i] = j < cnt[wave * 32 + row] ? buf[(wave * 32 + row) * ldb + j] : 0;
+    }
+}
+
+// One workgroup per real row: (1) the keys of the ranges' lists with !(s3 < t3 - d), t3 = the k-th best s3 over all of them, by
+// k_topk_merge's filter / append / compact over batches of 256 keys with k_lx3t's keep rule (buffer keep + 256; more than keep
+// inside the band: the row is marked overflowed); (2) the kept pairs through the exact chain, as k_pair_logit_rank does: 16 pairs per
+// wave in the [rows][LDE] layout, mma_tile<1>'s k-order, the diagonal -- the float32 ader_logits_store writes for that pair, whatever
+// its tile neighbours (here: the row's own rep in every column); (3) the best k by topk_key(exact score, id), unpacked as k_topk_merge does.  Every output is a function of
+// sorted keys; LDS and global atomics only hand out slots and add up the diagnostics.
+__global__ __launch_bounds__(256) void k_topk3_finish(TopkX3Args a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* E_l = smem;                                     // [keep rounded up to 16][LDE] table rows of the kept pairs
+    float* R_l = E_l + ((a.keep + 15) & ~15) * TK3_LDE;    // [LDE] the row's rep: every pair's second operand (column stride 0)
+    __shared__ u64 mb[TK3_KMAX + TK3_BANDMAX + 256];
+    __shared__ u64 ek[64];
+    __shared__ float mlo;
+    __shared__ int mcnt, movf;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int k = a.k, keep = a.keep, total = a.ranges * keep;
+    const float d = a.delta[b];
+    if (tid == 0) { mlo = -INFINITY; mcnt = 0; movf = a.status[b] != 0; }
+    __syncthreads();
+    for (int base = 0; base <= total; base += 256) {       // the pass at base >= total appends nothing: the final, sorting compaction
+        const int i = base + tid;
+        const bool last = base + 256 > total;
+        u64 key = 0;
+        if (i < total) { const int rg = i / keep; key = a.part3[((size_t)rg * a.Bp + b) * keep + (i - rg * keep)]; }
+        int over = 0;
+        if (key != 0 && !(topk_score(key) < mlo)) { const int p = atomicAdd(&mcnt, 1); mb[p] = key; over = (p >= keep); }
+        if (__syncthreads_or(over | last)) {
+            const int n = mcnt;                            // n <= keep + 256 <= 312: at most two keys per thread
+            const u64 e0 = tid < n ? mb[tid] : 0, e1 = tid + 256 < n ? mb[tid + 256] : 0;
+            int r0 = 0, r1 = 0;
+#pragma unroll 8
+            for (int j = 0; j < n; ++j) { const u64 x = mb[j]; r0 += x > e0; r1 += x > e1; }      // (unrolled: eight reads in flight)
+            __syncthreads();
+            if (tid < n && r0 == k - 1) mlo = topk_score(e0) - d;          // (fewer than k keys so far: the edge stays where it is)
+            if (tid + 256 < n && r1 == k - 1) mlo = topk_score(e1) - d;
+            __syncthreads();
+            const float lo = mlo;
+            const bool k0 = tid < n && !(topk_score(e0) < lo), k1 = tid + 256 < n && !(topk_score(e1) < lo);
+            const int m = __syncthreads_count(k0) + __syncthreads_count(k1);
+            if (k0 && r0 < keep) mb[r0] = e0;
+            if (k1 && r1 < keep) mb[r1] = e1;
+            if (tid == 0) { mcnt = min(m, keep); if (m > keep) movf = 1; }
+            __syncthreads();
+        }
+        if (last) break;
+    }
+    const int n = mcnt;                                    // <= keep <= 56: one pass of 64 pairs
+    if (movf) {                                            // (workgroup-uniform) the caller replaces this row
+        if (tid == 0) { a.status[b] = 1; atomicAdd(a.diag + 1, 1); }
+        for (int j = tid; j < k; j += 256) { a.items[(size_t)b * k + j] = 0; a.scores[(size_t)b * k + j] = -INFINITY; }
+        return;
+    }
+    const int H = a.H, ksteps = (H + 3) >> 2;
+    for (int i = tid; i < ((n + 15) & ~15) * TK3_LDE; i += 256) {
+        const int r = i / TK3_LDE, c = i - r * TK3_LDE;
+        E_l[i] = (r < n && c < H) ? a.emb1[(size_t)(topk_item(mb[r]) - 1) * H + c] : 0.0f;
+    }
+    for (int c = tid; c < TK3_LDE; c += 256) R_l[c] = c < H ? a.rep[(size_t)b * H + c] : 0.0f;
+    __syncthreads();
+    f32x4 acc[1];
+    acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (wave * 16 < n)                                     // (wave-uniform) the same fma chain in k order whatever the neighbours
+        mma_tile<1>(E_l + wave * 16 * TK3_LDE, TK3_LDE, 1, R_l, 1, 0, ksteps, acc, lane);
+    const int col = lane & 15, q = lane >> 4;
+    const int p = wave * 16 + col;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (q * 4 + r == col) {
+            u64 e = 0;
+            if (p < n) {
+                const float s = acc[0][r], s3 = topk_score(mb[p]);
+                e = topk_key(s, topk_item(mb[p]));
+                const float err = d > 0.0f ? fabsf(s3 - s) / d : 0.0f;
+                if (err > 0.0f) atomicMax(a.diag + 2, __float_as_int(err));
+            }
+            ek[p] = e;
+        }
+    __syncthreads();
+    if (tid == 0) atomicAdd(a.diag, n);
+    if (tid < n) {
+        const u64 e = ek[tid];
+        int r = 0;                                         // exact keys of a row are distinct: rank = number of larger keys
+        for (int j = 0; j < n; ++j) r += ek[j] > e;
+        if (r < k) { a.items[(size_t)b * k + r] = topk_item(e); a.scores[(size_t)b * k + r] = topk_score(e); }
+    }
+    for (int j = n + tid; j < k; j += 256) { a.items[(size_t)b * k + j] = 0; a.scores[(size_t)b * k + j] = -INFINITY; }
+}
+
 // in logits.hip: the exact-f32 target logits (k_target_logit) and the recheck of the listed pairs (k_pair_logit_rank)
 int rank_target_logit_launch(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
                              float* tlogit, void* stream);
@@ -964,6 +1251,53 @@ int ader_rank_targets_x3(const float* rep, const float* emb, int item_num, int B
     hipLaunchKernelGGL(k_lx3k, dim3(a.ranges * (Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, st, a);
     HIP_LAUNCH_CHECK();
     return rank_pairs_launch(rep, emb, B, Bp, H, N, target, ncol, tlogit, delta, cand, cap, diag, rank, stream);
+}
+
+// ader_topk_items on the bf16 matrix cores (k_lx3t + k_topk3_finish above).  ader_topk_x3_ranges: item ranges per 128-row chunk -- about
+// one workgroup per CU over the Bp/128 chunks (every range emits k + band keys per row, so no more of them than fill the machine), a
+// multiple of 8 (the block -> (range, chunk) mapping), so it may exceed the number of 32-item blocks: such ranges are empty.
+int ader_topk_x3_kmax(void) { return TK3_KMAX; }
+int ader_topk_x3_ranges(int N, int Bp) {
+    const int nblk = (N + F3_FB - 1) / F3_FB;
+    const int nchunk = Bp / G3_ROWS > 0 ? Bp / G3_ROWS : 1;
+    int target = 256 / nchunk / 8 * 8;
+    if (target < 8) target = 8;
+    int r = (nblk + 7) / 8 * 8;
+    if (r > target) r = target;
+    if (r < 8) r = 8;
+    return r;
+}
+// items / scores [B,k]: ader_topk_items' output, byte for byte, for every row with status[b] == 0 afterwards; a row with status[b] != 0
+// (its kept set outgrew k + band keys, or an x3 score was a NaN) holds item 0 / -inf and the caller takes ader_topk_items' answer for it.
+// emax: ader_rank_emax's output (once per call, after the table is final).  Scratch: rep_hi, rep_lo Bp*168 bf16; delta Bp floats; part3
+// ader_topk_x3_ranges(N,Bp) * Bp * (k + band) keys.  status [Bp] and diag [3] are zeroed here.  Enqueue only.
+int ader_topk_items_x3(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* ncol, const int* seen,
+                       int seen_ld, int k, int band, void* rep_hi, void* rep_lo, float* delta, const float* emax,
+                       unsigned long long* part3, int* status, int* diag, int* items, float* scores, void* stream) {
+    if (k < 1 || k > TK3_KMAX || band < 0 || band > TK3_BANDMAX || Bp % G3_ROWS != 0 || B > Bp || !lx3f_supports(H) || N < 1 ||
+        N > item_num || ((uintptr_t)emb & 7) || (seen && seen_ld < 1))
+        return -2;
+    if ((long)item_num * H * 4 >= (1l << 31)) return -2;          // the block offsets of the buffer loads are 32-bit
+    if (B <= 0) return 0;
+    TopkX3Args a = {};
+    a.rep = rep; a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo;
+    a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ranges = ader_topk_x3_ranges(N, Bp); a.k = k; a.keep = k + band;
+    a.ncol = ncol; a.seen = seen; a.seen_ld = seen_ld; a.delta = delta; a.part3 = part3; a.status = status; a.diag = diag;
+    a.items = items; a.scores = scores;
+    const size_t lds = 3 * X3B_IMG_B + (size_t)G3_ROWS * (a.keep + F3_FB) * sizeof(u64) + G3_ROWS * sizeof(int);
+    const size_t lds_fin = (size_t)((((a.keep + 15) & ~15) + 1) * TK3_LDE) * sizeof(float);
+    if (int e = ader_dyn_lds<k_lx3t>(lds)) return e;
+    if (int e = ader_dyn_lds<k_topk3_finish>(lds_fin)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(status, 0, sizeof(int) * (size_t)Bp, st);
+    if (e == hipSuccess) e = hipMemsetAsync(diag, 0, 3 * sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+    if (int rc = ader_lx3_prep(rep, rep_hi, rep_lo, B, Bp, H, stream)) return rc;
+    hipLaunchKernelGGL(k_rank_delta, dim3(Bp / 4), dim3(256), 0, st, rep, B, Bp, H, emax, delta);
+    hipLaunchKernelGGL(k_lx3t, dim3(a.ranges * (Bp / G3_ROWS)), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(k_topk3_finish, dim3(B), dim3(256), lds_fin, st, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // extern "C"

@@ -10,10 +10,19 @@ from .common import TeacherRep, _check
 RANK_X3_KAPPA = 2.0 ** -13
 RANK_X3_CAND_PER_ROW = 64      # default candidate-list entries per padded row of a chunk (Engine.rank_targets cand_cap)
 RANK_DTYPES = ("f32", "x3")
+TOPK_DTYPES = ("f32", "x3")
+# Keys beyond k that a row of the x3 top-K filter may keep inside its band (Engine.recommend band): tests/test_topk_x3_host.py holds the
+# band populations of Gaussian operands at or below half of it; at most 16 (the LDS of k_lx3t, csrc/logits_x3.hip)
+TOPK_X3_BAND = 16
 
 
 def _check_rank_dtype(v):
     _check(v in RANK_DTYPES, "rank_dtype must be 'f32' or 'x3' (got %r)" % (v,))
+    return v
+
+
+def _check_topk_dtype(v):
+    _check(v in TOPK_DTYPES, "topk_dtype must be 'f32' or 'x3' (got %r)" % (v,))
     return v
 
 
@@ -23,6 +32,7 @@ def rank_x3_supports(H):
 
 
 class _Infer:
+    last_topk_stats = None     # Engine.recommend(dtype="x3"): kept_pairs, rows, overflowed_rows, fallback_chunks, max_err_over_delta of the last call
     last_rank_stats = None     # Engine.rank_targets(dtype="x3"): candidates, pairs, overflowed_chunks, max_err_over_delta of the last call
 
     # ---------------------------------------------------------------------------------------- inference paths
@@ -180,18 +190,27 @@ class _Infer:
             "max_err_over_delta": float(diag[:, 1].copy().view(np.float32).max()) if len(chunks) else 0.0}
         return ranks
 
-    def recommend(self, seq, k, max_item=None, exclude_seen=False):
+    def recommend(self, seq, k, max_item=None, exclude_seen=False, dtype=None, band=None):
         """The k best items of 1..max_item for every row, fused with the catalog logits (ader_topk_items): (items int32 [n,k], 1-based;
         scores float32 [n,k]) as numpy.  Order: (score descending, item id ascending) -- the tie rule of rank_targets -- on the very
         float32 logits() returns, so items == stable_argsort(-logits)[:, :k] + 1 and rank_targets(seq_b, items[b, j]) == j.
         exclude_seen removes the non-zero ids of the row's own seq from its candidates (off by default: a repeated item is a legitimate
         target, and the reference's evaluation does not exclude).  Fewer than k candidates: the tail is item 0, score -inf.
-        max_item=None: the whole catalog.  Chunks of MAX_ROWS rows, one device -> host copy."""
+        max_item=None: the whole catalog.  Chunks of MAX_ROWS rows, one device -> host copy.
+        dtype: "f32" (k_topk_tile on the exact-f32 MFMA chain) or "x3" (bf16 matrix cores as a filter that keeps a superset of every
+        row's top-k + exact recheck of the kept pairs: the same bytes, ties included); None: the engine's topk_dtype.  "x3" takes the
+        f32 kernels for a hidden size outside k_lx3t's, k > ader_topk_x3_kmax() or a table of 2^31 bytes or more.  band: keys beyond
+        k a row's kept set may hold on the "x3" path before the row is handed to the f32 kernels (None: TOPK_X3_BAND)."""
+        dtype = _check_topk_dtype(self.topk_dtype if dtype is None else dtype)
         kmax = call("ader_topk_kmax")
         k = int(k)
         N = self.item_num if max_item is None else int(max_item)
+        band = TOPK_X3_BAND if band is None else int(band)
         _check(1 <= k <= kmax, "recommend: k must be in 1..%d (got %d)" % (kmax, k))
         _check(1 <= N <= self.item_num, "recommend: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        _check(0 <= band <= TOPK_X3_BAND, "recommend: band must be in 0..%d (got %d)" % (TOPK_X3_BAND, band))
+        if dtype == "x3" and rank_x3_supports(self.H) and k <= call("ader_topk_x3_kmax") and self.item_num * self.H * 4 < 2 ** 31:
+            return self._recommend_x3(seq, k, N, exclude_seen, band)
         self._refresh_stream()
         self.sync_table()
         seq = self._seq_in(seq)
@@ -200,14 +219,63 @@ class _Infer:
         scores = res[1].view(torch.float32)
         for s in range(0, n, self.MAX_ROWS):
             e = min(n, s + self.MAX_ROWS)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
             rep = self.forward(seq[s:e], training=False)
-            part = self.buf("tk_part", (call("ader_topk_ranges", N, Bp) * Bp * k,), torch.int64)
-            call("ader_topk_items", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
-                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, ptr(part), ptr(res[0, s:e]), ptr(scores[s:e]), self._stream())
+            self._topk_f32(rep, seq[s:e] if exclude_seen else None, N, k, res[0, s:e], scores[s:e])
         host = res.cpu().numpy()
         return host[0], host[1].view(np.float32)
+
+    def _topk_f32(self, rep, seen, N, k, items, scores):
+        """ader_topk_items of one chunk: rep [B,H], seen [B,T] or None -> items / scores [B,k] (device, written in place)."""
+        B = rep.shape[0]
+        Bp = (B + 63) // 64 * 64
+        part = self.buf("tk_part", (call("ader_topk_ranges", N, Bp) * Bp * k,), torch.int64)
+        call("ader_topk_items", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
+             ptr(seen), seen.shape[1] if seen is not None else 0, k, ptr(part), ptr(items), ptr(scores), self._stream())
+
+    def _recommend_x3(self, seq, k, N, exclude_seen, band):
+        """recommend on the bf16 matrix cores (ader_topk_items_x3): per 128-row-padded chunk k_lx3t keeps every item whose x3 logit is not
+        provably below the row's k-th best, k_topk3_finish rechecks the kept pairs on the exact chain and selects.  One device -> host
+        copy of items, scores, status and diag; a chunk with a row whose kept set outgrew k + band keys goes through ader_topk_items on
+        the representations kept from this call's forward, and those rows are replaced."""
+        self._refresh_stream()
+        self.sync_table()
+        seq = self._seq_in(seq)
+        n, st, dev = seq.shape[0], self._stream(), self.device
+        chunks = [(s, min(n, s + self.MAX_ROWS)) for s in range(0, n, self.MAX_ROWS)]
+        res = torch.zeros(2 * n * k + n + 3 * len(chunks), dtype=torch.int32, device=dev)      # items | score bits | status | diag
+        items, scores = res[:n * k].view(n, k), res[n * k:2 * n * k].view(n, k).view(torch.float32)
+        status, diag = res[2 * n * k:2 * n * k + n], res[2 * n * k + n:]
+        rep_all = torch.empty((n, self.H), dtype=torch.float32, device=dev)
+        emax = self.buf("tkx_emax", (1,))
+        if chunks:
+            call("ader_rank_emax", self._pp["emb"], self.item_num, self.H, N, ptr(emax), st)       # once per call, not per chunk
+        for c, (s, e) in enumerate(chunks):
+            B = e - s
+            Bp = (B + 127) // 128 * 128
+            rep_all[s:e] = self.forward(seq[s:e], training=False)
+            rep_hi, rep_lo = self.buf("tkx_hi", (Bp * 168,), torch.bfloat16), self.buf("tkx_lo", (Bp * 168,), torch.bfloat16)
+            delta, stat = self.buf("tkx_delta", (Bp,)), self.buf("tkx_status", (Bp,), torch.int32)
+            part3 = self.buf("tkx_part", (call("ader_topk_x3_ranges", N, Bp) * Bp * (k + band),), torch.int64)
+            call("ader_topk_items_x3", ptr(rep_all[s:e]), self._pp["emb"], self.item_num, B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
+                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, band, ptr(rep_hi), ptr(rep_lo), ptr(delta), ptr(emax),
+                 ptr(part3), ptr(stat), ptr(diag[3 * c:]), ptr(items[s:e]), ptr(scores[s:e]), st)
+            status[s:e] = stat[:B]
+        host = res.cpu().numpy()
+        h_items, h_scores = host[:n * k].reshape(n, k).copy(), host[n * k:2 * n * k].reshape(n, k).view(np.float32).copy()
+        h_status, h_diag = host[2 * n * k:2 * n * k + n], host[2 * n * k + n:].reshape(-1, 3)
+        over = [c for c, (s, e) in enumerate(chunks) if h_status[s:e].any()]
+        for c in over:
+            s, e = chunks[c]
+            fb = torch.empty((2, e - s, k), dtype=torch.int32, device=dev)
+            self._topk_f32(rep_all[s:e], seq[s:e] if exclude_seen else None, N, k, fb[0], fb[1].view(torch.float32))
+            fb = fb.cpu().numpy()
+            rows = np.nonzero(h_status[s:e])[0]
+            h_items[s + rows], h_scores[s + rows] = fb[0][rows], fb[1].view(np.float32)[rows]
+        self.last_topk_stats = {
+            "kept_pairs": int(h_diag[:, 0].sum()), "rows": int(n), "overflowed_rows": int(np.count_nonzero(h_status)),
+            "fallback_chunks": len(over),
+            "max_err_over_delta": float(h_diag[:, 2].copy().view(np.float32).max()) if len(chunks) else 0.0}
+        return h_items, h_scores
 
     def row_losses(self, seq, pos, max_item):
         """Per-row cross entropy -log softmax(logits)[label] in eval mode (the quantity the reference's `loss` exemplar selector

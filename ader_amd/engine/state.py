@@ -10,7 +10,7 @@ import torch
 from .. import _lib
 from .._lib import call, ptr
 from .common import _NULL, LDR, StepState, _check, param_layout, side_stream
-from .infer import _check_rank_dtype
+from .infer import _check_rank_dtype, _check_topk_dtype
 
 
 class _State:
@@ -18,10 +18,13 @@ class _State:
     MAX_ROWS_FAST = 4096   # ... of a train step whose logits run on the flash kernels (logits_dtype bf16 / x3): 128-row chunks
 
     def __init__(self, item_num, maxlen=50, hidden_units=150, num_blocks=2, num_heads=1, seed=0, device="cuda:0",
-                 logits_dtype="x3", gemm="x3", dp_rank=0, dp_world=1, rank_dtype="f32"):
+                 logits_dtype="x3", gemm="x3", dp_rank=0, dp_world=1, rank_dtype="f32", topk_dtype="f32"):
         # arithmetic of rank_targets (infer.py): "f32" = the exact-f32 MFMA kernel, "x3" = bf16 matrix cores as a filter + exact recheck
         # of the undecided pairs -- the same ranks.  (Checked first: an option error does not need a GPU to be reported.)
         self.rank_dtype = _check_rank_dtype(rank_dtype)
+        # arithmetic of recommend (infer.py): "f32" = k_topk_tile on the exact-f32 MFMA chain, "x3" = bf16 matrix cores as a filter that
+        # keeps a superset of every row's top-k + exact recheck of the kept pairs -- the same bytes
+        self.topk_dtype = _check_topk_dtype(topk_dtype)
         if not torch.cuda.is_available():
             raise _lib.AderHipError("ader_amd.Engine needs an MI355X (no CPU fallback)")
         _lib.load()

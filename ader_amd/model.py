@@ -31,7 +31,8 @@ class Ader:
         ld = logits_dtype or getattr(args, "logits_dtype", "x3")
         self.engine = Engine(item_num, maxlen=args.maxlen, hidden_units=args.hidden_units, num_blocks=args.num_blocks,
                              num_heads=args.num_heads, seed=args.random_seed, device=device, logits_dtype=ld,
-                             dp_rank=dp_rank, dp_world=dp_world, rank_dtype=getattr(args, "rank_dtype", "f32"))
+                             dp_rank=dp_rank, dp_world=dp_world, rank_dtype=getattr(args, "rank_dtype", "f32"),
+                             topk_dtype=getattr(args, "topk_dtype", "f32"))
         # session kernels on the real positions only (packed tiles): "auto" goes by the density of the batches (engine.py)
         self.engine.pack_sessions = {"auto": "auto", "on": True, "off": False}[getattr(args, "pack_sessions", "auto")]
         for n in ("is_training", "input_seq", "pos", "exemplar_logits", "exemplar_pos", "max_item", "lr", "dropout_rate",
@@ -74,9 +75,9 @@ class Ader:
     def rank_targets(self, seq, pos, max_item):
         return self.engine.rank_targets(seq, pos, max_item)
 
-    def recommend(self, seq, k, max_item=None, exclude_seen=False):
-        """The k best items per session, (items int32 [n,k], scores float32 [n,k]): Engine.recommend."""
-        return self.engine.recommend(seq, k, max_item, exclude_seen)
+    def recommend(self, seq, k, max_item=None, exclude_seen=False, dtype=None):
+        """The k best items per session, (items int32 [n,k], scores float32 [n,k]): Engine.recommend (dtype None: --topk_dtype)."""
+        return self.engine.recommend(seq, k, max_item, exclude_seen, dtype=dtype)
 
     def predict(self, sess, seq, item_idx):
         """Rank of every candidate item (ADER.py:140-150).  Kept for API parity; the Evaluator uses rank_targets."""

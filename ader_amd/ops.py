@@ -15,6 +15,8 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
                                                                          + exact-f32 recheck of the undecided pairs)
   ader::topk_items(rep, emb, seen, N, k)                       -> (items, scores)   the k best items per row, fused with the logits:
                                                                          order and bits of argsort(-logits) (ADER.py:92, 103)
+  ader::topk_items_x3(rep, emb, seen, N, k)                    -> (items, scores)   the same bytes; products on the bf16 matrix cores (x3
+                                                                         filter keeping a superset of the top-k + exact-f32 recheck)
   ader::teacher_rows(trep, temb, ex_trow, Np)                  -> (rows, trow_local)   teacher logits of a step's exemplar rows from
                                                                          stored representations + a table snapshot: the bits of
                                                                          ader_logits_store (util.py:433, ADER.py:134-135)
@@ -218,6 +220,48 @@ def topk_items(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor
 
 
 @topk_items.register_fake
+def _(rep, emb, seen, N, k):
+    return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
+
+
+@torch.library.custom_op("ader::topk_items_x3", mutates_args=())
+def topk_items_x3(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor], N: int, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """topk_items' contract and result, byte for byte, through ader_topk_items_x3 (k <= ader_topk_x3_kmax(), H as rank_of_target_x3).
+    Reads the row status back (one synchronisation): rows whose kept set outgrew k + TOPK_X3_BAND keys take topk_items' answer."""
+    from .engine.infer import TOPK_X3_BAND, rank_x3_supports
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
+    B, H = rep.shape
+    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
+        raise RuntimeError("ader::topk_items_x3: bad shapes")
+    if not rank_x3_supports(H):
+        raise RuntimeError("ader::topk_items_x3: H must be even, 8 <= H <= 160, H mod 8 in {0, 4, 6} (got %d)" % H)
+    if not (1 <= k <= call("ader_topk_x3_kmax")):
+        raise RuntimeError("ader::topk_items_x3: k must be in 1..%d (got %d)" % (call("ader_topk_x3_kmax"), k))
+    if seen is not None:
+        _chk(seen, "seen", torch.int32, 2)
+        if seen.shape[0] != B or seen.shape[1] < 1:
+            raise RuntimeError("ader::topk_items_x3: seen must be [B, S] with S >= 1")
+    Bp = (B + 127) // 128 * 128
+    dev = rep.device
+    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
+    ncol[:B] = N
+    delta, emax = torch.empty(Bp, device=dev), torch.empty(1, device=dev)
+    rep_hi, rep_lo = (torch.empty(Bp * LDR, dtype=torch.bfloat16, device=dev) for _ in range(2))
+    part3 = torch.empty(call("ader_topk_x3_ranges", N, Bp) * Bp * (k + TOPK_X3_BAND), dtype=torch.int64, device=dev)
+    status, diag = torch.empty(Bp, dtype=torch.int32, device=dev), torch.empty(3, dtype=torch.int32, device=dev)
+    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
+    call("ader_rank_emax", ptr(emb), emb.shape[0] - 1, H, N, ptr(emax), _st())
+    call("ader_topk_items_x3", ptr(rep), ptr(emb), emb.shape[0] - 1, B, Bp, H, N, ptr(ncol), ptr(seen),
+         seen.shape[1] if seen is not None else 0, k, TOPK_X3_BAND, ptr(rep_hi), ptr(rep_lo), ptr(delta), ptr(emax), ptr(part3),
+         ptr(status), ptr(diag), ptr(items), ptr(scores), _st())
+    over = status[:B] != 0
+    if bool(over.any().item()):
+        fi, fs = topk_items(rep, emb, seen, N, k)
+        items[over], scores[over] = fi[over], fs[over]
+    return items, scores
+
+
+@topk_items_x3.register_fake
 def _(rep, emb, seen, N, k):
     return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
 

@@ -259,6 +259,21 @@ int ader_topk_kmax(void);
 int ader_topk_ranges(int N, int Bp);
 int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
                     int k, unsigned long long* part, int* items, float* scores, void* stream);
+/* ader_topk_items with the [B,N] products on the bf16 matrix cores: k_lx3t keeps, per row and item range, every item whose x3 logit is
+ * not provably below the row's k-th best by delta[b] = 2^-13 |rep_b| emax[0] (a superset of the exact top-k, at most k + band keys), and
+ * k_topk3_finish merges the ranges, re-evaluates the kept pairs through the exact-f32 MFMA chain and selects: for every row with
+ * status[b] == 0 afterwards items / scores are ader_topk_items' bytes (order, score bits, ties, item 0 / -inf padding).  status[b] != 0:
+ * the row's kept set outgrew k + band keys (ties or near-ties across rank k) or an x3 logit was a NaN; its output is item 0 / -inf and
+ * the caller takes ader_topk_items' answer for it.  emax: ader_rank_emax's output.  diag[0] = kept pairs, diag[1] = rows with
+ * status != 0, diag[2] = float bits of max |s_x3 - s_f32| / delta over the re-evaluated pairs.  Scratch: rep_hi, rep_lo Bp*168 bf16; delta
+ * Bp floats; part3 ader_topk_x3_ranges(N,Bp)*Bp*(k+band) 64-bit keys.  status [Bp] and diag [3] are zeroed here.  Enqueue only.
+ * -2 when Bp % 128 != 0, B > Bp, H not (even, 8 <= H <= 160, H mod 8 in {0, 4, 6}), k < 1, k > ader_topk_x3_kmax() (= 40: the LDS of
+ * one CU), band < 0, band > 16, N < 1, N > item_num, or a table of 2^31 bytes or more. */
+int ader_topk_x3_kmax(void);
+int ader_topk_x3_ranges(int N, int Bp);
+int ader_topk_items_x3(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* ncol, const int* seen,
+                       int seen_ld, int k, int band, void* rep_hi, void* rep_lo, float* delta, const float* emax,
+                       unsigned long long* part3, int* status, int* diag, int* items, float* scores, void* stream);
 
 /* Teacher logits of a step's exemplar rows, regenerated from stored teacher representations (util.py:433 computes them, ADER.py:134-135
  * consumes them as softmax(exemplar_logits)): trep [E,H] = the teacher's representations, temb = the item table as it stood when the

@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """Top-K recommendation, fused (Engine.recommend) against the composition a caller had to write before it existed.
 
-    python tools/bench_topk.py [--check] [--reps 3] [--warmup 1] [--rows 1024] [--k 20] [--out profiles/topk.txt]
+    python tools/bench_topk.py [--check] [--reps 3] [--warmup 1] [--rows 1024] [--k 20] [--datasets YOOCHOOSE,DIGINETICA]
+                               [--train_steps 200] [--out profiles/topk.txt]
 
 (A) Engine.recommend(seq, k, N): ader_topk_items -- k_topk_tile (logit tiles + per-row selection in LDS) and k_topk_merge;
 (B) Engine.logits(seq, N) followed by torch.topk(.., k): dense [n, N] logits in HBM, then torch's selection.  (B) is the yardstick.
+(C) Engine.recommend(seq, k, N, dtype="x3"): ader_topk_items_x3 -- k_lx3t (x3 logits on the bf16 matrix cores + a per-row superset of
+    the top-k in LDS) and k_topk3_finish (merge, exact recheck of the kept pairs, selection).  Its yardstick is (A) of the same run.
 Shapes: --rows sessions at the catalog sizes of the two datasets (N = 25,750 and 43,105) and at N = 10^6, each on an Engine of that
 catalog size at its initial weights with synthetic sessions (random lengths, uniform ids), as tools/bench_eval.py builds its synthetic
-shape.  One process; after a warm-up (A) and (B) alternate inside every repetition; device events around the whole call (session
+shape; --datasets adds the first --rows rows of the last test period of the shipped datasets on an Engine after --train_steps steps
+on the first period (tools/bench_eval.py's model: the x3 band scales with the largest table-row norm, and an initial Gaussian table
+flatters it).  One process; after a warm-up (A), (B) and (C) alternate inside every repetition; device events around the whole call (session
 forward, launches, the copy back), medians.  The kernels of (A) are timed by torch.profiler over one more call; k_topk_tile is set
 against its two bounds: 2 n N H over the f32 MFMA peak (157.3 TFLOP/s, v_mfma_f32_16x16x4_f32) and N H 4 bytes per 64-row chunk over
-the HBM peak (8 TB/s) -- the larger one binds.  --check asserts that the items of (A) and (B) agree on every row whose k-th and (k+1)-th
+the HBM peak (8 TB/s) -- the larger one binds; k_lx3t against 3 x 2 n N H over the bf16 MFMA peak (2.5 PFLOP/s) and against k_topk_tile
+of the same run.  --check asserts that (C) equals (A) bytewise, that the items of (A) and (B) agree on every row whose k-th and (k+1)-th
 scores of (B) differ (torch.topk does not promise an order among ties) and that the scores agree bitwise there."""
 import argparse
 import os
@@ -23,8 +29,9 @@ import torch  # noqa: E402
 
 from ader_amd._lib import call  # noqa: E402
 from ader_amd.engine import Engine  # noqa: E402
+from ader_amd.engine.infer import TOPK_X3_BAND  # noqa: E402
 
-PEAK_F32_MFMA, PEAK_HBM = 157.3e12, 8.0e12
+PEAK_F32_MFMA, PEAK_BF16_MFMA, PEAK_HBM = 157.3e12, 2.5e15, 8.0e12
 T, H = 50, 150
 _out = []
 
@@ -70,33 +77,74 @@ def kernel_times(fn):
     return out
 
 
-def measure(N, args):
-    n, k = args.rows, args.k
+def synthetic(N, args):
+    n = args.rows
     eng = Engine(N, maxlen=T, hidden_units=H, num_blocks=2, num_heads=1, seed=0)
     rs = np.random.RandomState(0)
     seq = np.zeros((n, T), dtype=np.int32)
     for b in range(n):
         ln = int(rs.randint(1, T + 1))
         seq[b, T - ln:] = rs.randint(1, N + 1, size=ln)
-    seq_d = torch.from_numpy(seq).to(eng.device)
-    tA, tB, a, b = [], [], None, None
+    return measure("N = %d" % N, eng, seq, N, args)
+
+
+def dataset(name, args):
+    """The first --rows rows the Evaluator ranks in the last test period, on tools/bench_eval.py's briefly trained model."""
+    import random
+
+    from bench_eval import evaluator_rows
+    from ader_amd.data import DataLoader, Sampler
+    from ader_amd.main import ITEM_NUM
+    dl = DataLoader(name)
+    periods = dl.num_periods() - 1
+    eng = Engine(ITEM_NUM[name], maxlen=T, hidden_units=H, num_blocks=2, num_heads=1, seed=0)
+    random.seed(0)
+    np.random.seed(0)
+    for period in range(1, periods + 1):
+        train_sess, _ = dl.train_loader(period - 1)
+        test_sess, _ = dl.evaluate_loader(period)
+        N = dl.max_item()
+        if period == 1 and args.train_steps:
+            smp = Sampler(train_sess, T, 256)
+            for _ in range(min(args.train_steps, smp.batch_num())):
+                seq, pos = smp.next_batch()
+                if len(pos) == 256:
+                    eng.train_step(seq, pos, N, 5e-4, rate=0.3)
+            torch.cuda.synchronize()
+    seq, _ = evaluator_rows(test_sess, N, 1024)
+    return measure("%s, test period %d, N = %d, %d training steps" % (name, periods, N, args.train_steps), eng, seq[:args.rows], N, args)
+
+
+def measure(name, eng, seq, N, args):
+    n, k = seq.shape[0], args.k
+    seq_d = torch.from_numpy(np.ascontiguousarray(seq)).to(eng.device)
+    tA, tB, tC, a, b, c = [], [], [], None, None, None
     for it in range(args.warmup + args.reps):
         ta, a = ev_time(lambda: eng.recommend(seq_d, k, N))
         tb, b = ev_time(lambda: composed(eng, seq_d, N, k))
+        tc, c = ev_time(lambda: eng.recommend(seq_d, k, N, dtype="x3"))
         if it >= args.warmup:
             tA.append(ta)
             tB.append(tb)
+            tC.append(tc)
+    st3 = dict(eng.last_topk_stats or {})
     tf = statistics.median(ev_time(lambda: eng.encode(seq_d))[0] for _ in range(args.reps))
     med = statistics.median
     rows = min(n, eng.MAX_ROWS)
     Bp = (rows + 63) // 64 * 64
     ranges = call("ader_topk_ranges", N, Bp)
-    say("== N = %d: %d rows, k = %d, H = %d; %d repetitions after %d warm-up, medians [min .. max]" % (N, n, k, H, args.reps, args.warmup))
+    Bp3 = (rows + 127) // 128 * 128
+    ranges3 = call("ader_topk_x3_ranges", N, Bp3)
+    say("== %s: %d rows, k = %d, H = %d; %d repetitions after %d warm-up, medians [min .. max]" % (name, n, k, H, args.reps, args.warmup))
     say("  (A) Engine.recommend       %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (%d ranges x %d rows x k keys of 8 B)" %
         (med(tA) * 1e3, min(tA) * 1e3, max(tA) * 1e3, n / med(tA), ranges * Bp * k * 8, ranges, Bp))
     say("  (B) logits + torch.topk    %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (the [n, N] float32 logits)" %
         (med(tB) * 1e3, min(tB) * 1e3, max(tB) * 1e3, n / med(tB), n * ((N + 3) // 4 * 4) * 4))
-    say("  (A) / (B) whole call %.3f  (< 1: the fused path is faster); session forward (encode) alone %.2f ms" % (med(tA) / med(tB), tf * 1e3))
+    say("  (C) recommend dtype=x3     %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (%d ranges x %d rows x (k + band) keys of 8 B)" %
+        (med(tC) * 1e3, min(tC) * 1e3, max(tC) * 1e3, n / med(tC), ranges3 * Bp3 * (k + TOPK_X3_BAND) * 8, ranges3, Bp3))
+    say("  (A) / (B) whole call %.3f  (< 1: the fused path is faster); (C) / (A) whole call %.3f  (< 1: x3 is faster); session forward "
+        "(encode) alone %.2f ms" % (med(tA) / med(tB), med(tC) / med(tA), tf * 1e3))
+    say("  (C) last_topk_stats %r: %.2f kept pairs per row" % (st3, st3.get("kept_pairs", 0) / max(n, 1)))
     kt = kernel_times(lambda: eng.recommend(seq_d, k, N))
     tile = sum(t for name, t in kt.items() if "k_topk_tile" in name)
     merge = sum(t for name, t in kt.items() if "k_topk_merge" in name)
@@ -110,14 +158,27 @@ def measure(N, args):
     else:
         say("  torch.profiler reported no k_topk_tile rows (kernels seen: %d): kernel time NOT measured; bounds: MFMA %.3f ms, HBM %.3f ms "
             "-> %s binds" % (len(kt), b_mfma * 1e3, b_hbm * 1e3, which))
+    kt3 = kernel_times(lambda: eng.recommend(seq_d, k, N, dtype="x3"))
+    filt = sum(t for nm, t in kt3.items() if "k_lx3t" in nm)
+    fin = sum(t for nm, t in kt3.items() if "k_topk3_finish" in nm)
+    b3 = 3.0 * 2.0 * n * N * H / PEAK_BF16_MFMA
+    if filt:
+        say("  k_lx3t %.3f ms, k_topk3_finish %.3f ms (torch.profiler, one call); bound: 3 x 2nNH over the bf16 MFMA peak %.3f ms; k_lx3t = "
+            "%.1f x its bound%s" % (filt * 1e3, fin * 1e3, b3 * 1e3, filt / b3, ", %.2f x k_topk_tile" % (filt / tile) if tile else ""))
+    else:
+        say("  torch.profiler reported no k_lx3t rows (kernels seen: %d): kernel time NOT measured; bound %.3f ms" % (len(kt3), b3 * 1e3))
     ok = True
     if args.check:
+        same_c = (np.array_equal(a[0], c[0]) and
+                  np.array_equal(np.ascontiguousarray(a[1]).view(np.int32), np.ascontiguousarray(c[1]).view(np.int32)))
+        say("  check: (C) equals (A) bytewise (items and score bits): %s" % same_c)
+        ok = bool(same_c)
         ib, vb = b
         decided = vb[:, k - 1] != vb[:, k] if vb.shape[1] > k else np.ones(n, dtype=bool)
         kk = min(k, vb.shape[1])
         same_items = np.array_equal(a[0][decided, :kk], ib[decided, :kk])
         same_bits = np.array_equal(np.ascontiguousarray(a[1][decided, :kk]).view(np.int32), np.ascontiguousarray(vb[decided, :kk]).view(np.int32))
-        ok = bool(same_items and same_bits)
+        ok &= bool(same_items and same_bits)
         say("  check: %d of %d rows have distinct k-th and (k+1)-th scores; on those, items equal: %s, scores bitwise equal: %s" %
             (int(decided.sum()), n, same_items, same_bits))
     del eng
@@ -133,19 +194,24 @@ def main():
     ap.add_argument("--rows", type=int, default=1024)
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--catalogs", default="25750,43105,1000000")
+    ap.add_argument("--datasets", default="", help="e.g. YOOCHOOSE,DIGINETICA: also the last test period of these, on a briefly trained model")
+    ap.add_argument("--train_steps", type=int, default=200)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "topk.txt"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_topk.py measures on the GPU: no device found")
     _out.append(open(args.out, "w"))
-    say("# tools/bench_topk.py%s: (A) Engine.recommend (k_topk_tile + k_topk_merge) against (B) Engine.logits + torch.topk, same process, "
-        "alternating; %s" % (" --check" if args.check else "", torch.cuda.get_device_name(0)))
+    say("# tools/bench_topk.py%s: (A) Engine.recommend (k_topk_tile + k_topk_merge) against (B) Engine.logits + torch.topk and (C) "
+        "Engine.recommend(dtype=\"x3\") (k_lx3t + k_topk3_finish), same process, alternating; %s" %
+        (" --check" if args.check else "", torch.cuda.get_device_name(0)))
     ok = True
     for N in [int(x) for x in args.catalogs.split(",") if x]:
-        ok &= measure(N, args)
-    say("# items equal wherever the yardstick's order is decided: %s" % (ok if args.check else "not checked"))
+        ok &= synthetic(N, args)
+    for name in [d for d in args.datasets.split(",") if d]:
+        ok &= dataset(name, args)
+    say("# (C) equal to (A) bytewise, (A) equal to (B) wherever the yardstick's order is decided: %s" % (ok if args.check else "not checked"))
     if args.check and not ok:
-        raise SystemExit("top-K mismatch between Engine.recommend and logits + torch.topk")
+        raise SystemExit("top-K mismatch between the three legs")
 
 
 if __name__ == "__main__":
