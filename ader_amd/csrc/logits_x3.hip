@@ -7,13 +7,19 @@
 // nothing [rows, N]-sized is ever written.  The table block is split into hi/lo on its way into LDS as the bank-conflict-free image
 // of x3_image.h (16-byte k-chunks [kc][item][8 channels]), and both operand reads -- ds_read_b128 rows for S^T, ds_read_b64_tr_b16
 // k-major for the readout -- are pipelined by hand ahead of their MFMAs.
-//   k_lx3g  32 batch rows per wave on v_mfma_f32_32x32x16_bf16 (128 per workgroup, two workgroups per CU); any supported H, the
-//           table block staged by k-chunks.  Launched for H != 150
-//   k_lx3p  the same with the softmax / staging vector work issued inside the MFMA phases, the table block staged in memory
-//           order (H = 150 only: the default forward)
-//   k_lx3r  the teacher readout of distilled steps (ADER.py:132-137) on the same images
-//   k_lx3k  the S^T phase of k_lx3g alone, as the FILTER of the evaluation ranking (ADER.py:99-103, util.py:323-325): counts the items
-//           whose x3 logit is provably above the row's target logit and lists the undecidable (row, item) pairs for the exact recheck
+//
+// Five kernels stream the table through that image.  They share ONE walk, stated once below: a workgroup = (item range, 128-row chunk)
+// on one XCD, 32 batch rows per wave on v_mfma_f32_32x32x16_bf16, the range's 32-item blocks through three LDS buffers, and per block
+// the S^T phase (G3_SPHASE) and / or the readout (G3_READOUT).  What each adds:
+//   k_lx3g  the flash forward: F3 staging (by k-chunks, any supported H), S^T, online softmax, readout.  Launched for H != 150
+//   k_lx3p  the same arithmetic with the softmax / staging vector work issued inside the MFMA phases, P3 staging (memory order,
+//           H = 150 only): the default forward
+//   k_lx3r  the teacher readout of distilled steps (ADER.py:132-137): P3 staging two blocks ahead, P from the teacher logits instead
+//           of an S^T phase, readout
+//   k_lx3k  the FILTER of the evaluation ranking (ADER.py:99-103, util.py:323-325): F3 staging, S^T, then counts the items whose x3
+//           logit is provably above the row's target logit and lists the undecidable (row, item) pairs for the exact recheck
+//   k_lx3t  the FILTER of the top-K recommendation: F3 staging, S^T, then keeps per row a small superset of the exact top-k
+//           (filter / append / compact on x3 keys) for k_topk3_finish
 // (k_lx3f, 16 rows per wave on 16x16x32 tiles, and k_lx3h, k_lx3g's blocking on 16x16x32 tiles, were measured 25 % and 4 % slower in
 // round 3 -- NOTEBOOK.md -- and removed in round 4.)
 // Output partials (pm, pl, pO per item range) and the merge (k_lbf_combine<true>) are those of k_lx3_fwd.  gfx950 only.
@@ -29,8 +35,41 @@
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
-// ---- what the three kernels share: the operand reads of a block image (x3_image.h, 32x32x16 maps) and the rotation of its three
-// LDS buffers.  (The reads are macros, expanded in the kernel, and not functions: as functions they compile to other streams.)
+// ===========================================================================================================================
+// The shared walk.  Every piece is a macro over the kernel's locals, expanded in the kernel, and not a function: as functions the
+// operand reads compile to other streams.  Names a piece expects in scope are the ones the pieces before it define.
+
+// ---- workgroup prologue.  G3_WG_MAP: tid / lane / wave / r32 / hh, block -> (item range `range`, row chunk `bc` of nchunk_).  The
+// row chunks of an item range sit on one XCD: the table block is fetched from HBM once and served to the others by that XCD's L2
+#define G3_WG_MAP(ranges_, nchunk_)                                                                       \
+    const int tid = threadIdx.x, lane = tid & 63;                                                         \
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                                            \
+    const int r32 = lane & 31, hh = lane >> 5;                                                            \
+    const int nchunk = (nchunk_);                                                                         \
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;                                               \
+    const int range = xcd + 8 * (slot / nchunk);                                                          \
+    const int bc = slot % nchunk;                                                                         \
+    if (range >= (ranges_)) return;
+// G3_WG_BLOCKS: the range's span [blk_begin, blk_end) of the ncat_ items' 32-item blocks, cut at the ncol_ columns these rows see,
+// nb_blocks of them; b0 = the wave's first row; and the LDS zero fill: pads of every image (k-chunks >= ceil(H/8), bytes between the
+// quads) stay zero, the block stores never touch them.  (b0 stands behind nb_blocks and not in G3_WG_MAP: in front of the span's
+// divisions hipcc schedules the scalar prologue of all five kernels differently -- profiles/logits_x3_refactor_isa.txt)
+#define G3_WG_BLOCKS(ranges_, ncat_, ncol_)                                                               \
+    const int nblk_all = ((ncat_) + F3_FB - 1) / F3_FB;                                                   \
+    const int per = (nblk_all + (ranges_) - 1) / (ranges_);                                               \
+    const int blk_begin = range * per, blk_end = min(((ncol_) + F3_FB - 1) / F3_FB, blk_begin + per);     \
+    const int nb_blocks = max(0, blk_end - blk_begin);                                                    \
+    const int b0 = bc * G3_ROWS + wave * 32;                                                              \
+    for (int i = tid; i < 3 * X3B_IMG_B / 16; i += 256) ((uint4*)smem_raw)[i] = make_uint4(0u, 0u, 0u, 0u);
+// rep fragments: lane (batch row r32, k-half hh) holds rep[b0 + r32][16 ks + 8 hh + 0..7]
+#define G3_REP_FRAGS()                                                                                    \
+    bf16x8 rh[10], rl[10];                                                                                \
+    _Pragma("unroll") for (int ks = 0; ks < 10; ++ks) {                                                   \
+        rh[ks] = *(const bf16x8*)(a.rep_hi + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);                \
+        rl[ks] = *(const bf16x8*)(a.rep_lo + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);                \
+    }
+
+// ---- the operand reads of a block image (x3_image.h, 32x32x16 maps) and the rotation of its three LDS buffers.
 // Per-lane byte offsets into a block image, with lane, r32 = lane & 31 and hh = lane >> 5 in scope: t_off = transposed read of (item
 // 4 hh + q4, channels 16 g1 + 4 p4.. of a 32-channel block = k-chunks 2 g1 + (p4 >> 1) of its four); a_off = row read of (item r32,
 // k-half hh)
@@ -54,8 +93,114 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int g3_buf_next(int b) { return b == 2 ? 0 : b + 1; }       // (i + 1) % 3 from i % 3
 __device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; }        // (i + 2) % 3
 
-// ---- staging of k_lx3g / k_lx3k: a table block on its way into an LDS block image.  Macros, expanded in the kernel, over its locals:
-// H, nfull, rem, kc0, voff, voffp, trs, dst0, the staging registers sa / sb and smem_raw (see k_lx3g for what they are)
+// ---- the plain S^T phase: S_ = logits of the block image at img_ against the rep fragments rh / rl.  Ten k-steps of three MFMAs
+// (lo.hi + hi.lo + hi.hi), the operand sets two k-steps ahead of their use
+#define G3_SPHASE(S_, img_)                                                                               \
+    {                                                                                                     \
+        _Pragma("unroll") for (int j = 0; j < 16; ++j) S_[j] = 0.0f;                                      \
+        bf16x8 fa[2][2];                                                                                  \
+        G3_LOADA(fa[0], img_, 0);                                                                         \
+        G3_LOADA(fa[1], img_, 1);                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                \
+        _Pragma("unroll") for (int ks = 0; ks < 10; ++ks) {                                               \
+            bf16x8* A_ = fa[ks & 1];                             /* {hi, lo} */                           \
+            S_ = mfma_bf16(A_[1], rh[ks], S_);                                                            \
+            S_ = mfma_bf16(A_[0], rl[ks], S_);                                                            \
+            S_ = mfma_bf16(A_[0], rh[ks], S_);                                                            \
+            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], img_, ks + 2);                                          \
+            __builtin_amdgcn_sched_barrier(0);                                                            \
+        }                                                                                                 \
+    }
+
+// ---- the online softmax's head of block i0 (logits S of the chunk's N columns; running m_run, l_run, O): tail mask, running
+// maximum, (rare) rescale of l and O.  Leaves nm = -m_run and the block's sum ls = 0 for the exp that follows.
+// The two half-waves of a lane pair (l, l + 32) hold different items of the SAME batch row; m_run is kept equal in both, so the
+// cross-half exchange is only needed on the (rare) rescale path
+#define G3_SOFTMAX_HEAD()                                                                                 \
+        if (i0 + F3_FB > N) {                              /* tail block: items >= N are outside the softmax */ \
+            _Pragma("unroll") for (int j = 0; j < 16; ++j) if (i0 + acc_row(j, hh) >= N) S[j] = -INFINITY; \
+        }                                                                                                 \
+        float tmax = S[0];                                                                                \
+        _Pragma("unroll") for (int j = 1; j < 16; ++j) tmax = fmaxf(tmax, S[j]);                          \
+        float t2 = tmax * LOG2E;                                                                          \
+        if (__any(t2 > m_run + RESCALE_THR)) {                                                            \
+            t2 = fmaxf(t2, __shfl_xor(t2, 32, 64));                                                       \
+            const float m_new = (t2 > m_run + RESCALE_THR) ? t2 : m_run;                                  \
+            const float alpha = (m_new == -INFINITY) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);      \
+            l_run *= alpha;                                                                               \
+            m_run = m_new;                                                                                \
+            _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                              \
+                const float ar = __shfl(alpha, acc_row(j, hh), 64);     /* O rows are batch rows */       \
+                _Pragma("unroll") for (int nb = 0; nb < 5; ++nb) O[nb][j] *= ar;                          \
+            }                                                                                             \
+        }                                                                                                 \
+        const float nm = -m_run;                                                                          \
+        float ls = 0.0f;
+
+// ---- the plain readout O += P^T . E of the block image at Bh.  G3_PSPLIT: the probabilities in S as the A operands pa0 / pa1 (hi)
+// and pl0 / pl1 (lo).  G3_READOUT_LOADS: the first transposed reads (ft: half sets {items 4hh.., 8 + 4hh.., 16 + 4hh.., 24 + 4hh..} of
+// ONE plane; hi, lo, hi, lo ...), which do not depend on P.  G3_READOUT: ten half steps, 30 MFMAs, the reads three half steps ahead
+#define G3_O_ZERO()                                                                                       \
+    f32x16 O[5];                                                                                          \
+    _Pragma("unroll") for (int nb = 0; nb < 5; ++nb)                                                      \
+        _Pragma("unroll") for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
+#define G3_PSPLIT()                                                                                       \
+        const bf16x8 pa0 = pack8(S, 0), pa1 = pack8(S, 1);                                                \
+        bf16x8 pl0, pl1;                                                                                  \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j) { pl0[j] = (bf16)(S[j] - (float)pa0[j]); pl1[j] = (bf16)(S[8 + j] - (float)pa1[j]); }
+#define G3_READOUT_LOADS()                                                                                \
+        bf16x4 ft[3][4];                                                                                  \
+        G3_LOADT(ft[0], 0, 0);                                                                            \
+        G3_LOADT(ft[1], 0, 1);                                                                            \
+        G3_LOADT(ft[2], 1, 0);
+#define G3_READOUT()                                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                                \
+        _Pragma("unroll") for (int hs = 0; hs < 10; ++hs) {      /* half step: (channel block nb = hs >> 1, plane hs & 1) */ \
+            bf16x4* T_ = ft[hs % 3];                                                                      \
+            bf16x8 v0, v1;                                                                                \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) { v0[j] = T_[0][j]; v0[4 + j] = T_[1][j]; v1[j] = T_[2][j]; v1[4 + j] = T_[3][j]; } \
+            if ((hs & 1) == 0) {                                 /* hi plane of the table: P lo and P hi */ \
+                O[hs >> 1] = mfma_bf16(pl0, v0, O[hs >> 1]);                                              \
+                O[hs >> 1] = mfma_bf16(pl1, v1, O[hs >> 1]);                                              \
+                O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);                                              \
+                O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);                                              \
+            } else {                                             /* lo plane: P hi */                     \
+                O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);                                              \
+                O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);                                              \
+            }                                                                                             \
+            if (hs + 3 < 10) G3_LOADT(ft[hs % 3], (hs + 3) >> 1, (hs + 3) & 1);                           \
+            __builtin_amdgcn_sched_barrier(0);                                                            \
+        }
+
+// ---- epilogues: the wave's 32 rows of O to o_ [rows][HP]; a forward's (m, l) partials of its range
+#define G3_STORE_O(o_)                                                                                    \
+    {                                                                                                     \
+        float* o = (o_);                                                                                  \
+        _Pragma("unroll") for (int nb = 0; nb < 5; ++nb)                                                  \
+            _Pragma("unroll") for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r32] = O[nb][j]; \
+    }
+#define G3_STORE_ML()                                                                                     \
+    {                                                                                                     \
+        const float l_tot = l_run + __shfl_xor(l_run, 32, 64);                                            \
+        if (hh == 0) {                                                                                    \
+            a.pm[(size_t)range * a.Bp + b0 + r32] = m_run;                                                \
+            a.pl[(size_t)range * a.Bp + b0 + r32] = l_tot;                                                \
+        }                                                                                                 \
+    }
+
+// ---- F3 staging (k_lx3g / k_lx3k / k_lx3t): a table block = 32 rows of H floats on its way into an LDS block image, by k-chunks.
+// Round r (0..2) of wave w covers items 8 w.. and k-chunks 8 r..: lane l -> item + (l & 7), k-chunk + (l >> 3): the 8 lanes of an
+// LDS write group store 8 consecutive 16-byte slots (conflict-free), and a wave's two 16-byte loads per slot touch 2 cache lines
+// per table row.
+#define F3_LOCALS()                                                                                       \
+    const int nfull = H >> 3, rem = H & 7;                 /* full k-chunks; channels of the partial one (0, 4 or 6: see launcher) */ \
+    /* round r of this lane: item it_ (a wave stages the same 8 items in every round), k-chunk 8 r + kc0 */ \
+    const int it_ = 8 * wave + (lane & 7), kc0 = lane >> 3;                                               \
+    const int voff = 4 * (it_ * H + 8 * kc0);              /* byte offset inside the block (round r: + 256 r) */ \
+    const int voffp = voff + 4 * (rem - 4);                /* second vector of the partial k-chunk: ends with the row */ \
+    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000); \
+    const int dst0 = X3B_KC * kc0 + 16 * it_;              /* byte offset inside a plane (round r: + 8 k-chunks) */ \
+    f32x4_t sa[F3_RND], sb[F3_RND];
 #define F3_KC(r_) (8 * (r_) + kc0)
 #define F3_PART(r_) (rem && F3_KC(r_) == nfull)
 #define F3_VALID(r_) (F3_KC(r_) < nfull || F3_PART(r_))
@@ -91,6 +236,56 @@ __device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; } 
             }                                                                                             \
         }                                                                                                 \
     }
+// The walk over the range's blocks with F3 staging.  Between F3_WALK_BEGIN() and F3_WALK_END() stands the kernel's per-block body,
+// with i (block of the range), i0 (its first item), Bh (its image) and S (its logits: the S^T phase is done) in scope.  Block i + 2
+// is requested at the head of iteration i and stored behind the S^T phase
+#define F3_WALK_BEGIN()                                                                                   \
+    if (nb_blocks > 0) F3_LOAD(blk_begin);                                                                \
+    __syncthreads();                                       /* zero fill done */                           \
+    if (nb_blocks > 0) F3_STORE(0);                                                                       \
+    if (nb_blocks > 1) { F3_LOAD(blk_begin + 1); F3_STORE(1); }                                           \
+    int bcur = 0;                                          /* i % 3 */                                    \
+    for (int i = 0; i < nb_blocks; ++i) {                                                                 \
+        __syncthreads();                                   /* blocks i and i + 1 are in LDS; every wave is done with block i - 1 */ \
+        const bool more = i + 2 < nb_blocks;                                                              \
+        if (more) F3_LOAD(blk_begin + i + 2);                                                             \
+        const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);                                      \
+        const int i0 = (blk_begin + i) * F3_FB;                                                           \
+        f32x16 S;                                                                                         \
+        G3_SPHASE(S, Bh)                                                                                  \
+        if (more) F3_STORE(g3_buf_new(bcur));
+#define F3_WALK_END()                                                                                     \
+        bcur = g3_buf_next(bcur);                                                                         \
+    }
+
+// ---- P3 staging (k_lx3p / k_lx3r, H = 150): a block = 32 table rows of 150 floats, as 16-byte pieces read in memory order.  Lane l ->
+// item 8 wave + (l >> 3), piece (l & 7) + 8 r of the row's 37.5 (round r = 0..4): a wave-instruction reads 8 x 128 contiguous bytes --
+// ~12 cache lines, every byte used -- where the F3 k-chunk mapping reads 8 x 8 half-used 32-byte pieces (~20 lines, each touched by
+// two instructions); 5 loads instead of 6.  A piece = 4 channels = half a k-chunk slot: one ds_write_b64 per plane (two-way bank
+// conflicts, hidden under the VGPR-to-LDS transfer of the store).  The loads go through a buffer descriptor of the table as in
+// F3_LOAD; rows beyond the table's last one come back as zeros from the hardware range check.  sc_ = the staging set, f32x4_t [5].
+// The kernel's locals: qb, itb (the lane's piece and item), trs, voffb, dstb.  (They are written out in both kernels: each keeps its
+// instruction stream only with its own order of qb and itb, so one shared statement of them serves one kernel and not the other.)
+#define P3_LOAD(sc_, blk_)                                                                              \
+    {                                                                                                     \
+        const int so_ = (blk_) * (F3_FB * 4) * H;              /* byte offset of the block (< 2^31: checked by the launcher) */ \
+        _Pragma("unroll") for (int r = 0; r < 5; ++r)                                                     \
+            sc_[r] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(trs, voffb + 128 * r, so_, 0)); \
+    }
+#define P3_STORE(sc_, buf_)                                                                               \
+    {                                                                                                     \
+        unsigned char* dst_ = smem_raw + (buf_) * X3B_IMG_B;                                              \
+        _Pragma("unroll") for (int r = 0; r < 5; ++r) {                                                   \
+            const int p_ = qb + 8 * r;                          /* piece 37 = channels 148, 149 and two floats of the next row */ \
+            float x_[4];                                        /* pieces 38, 39 = channels 152..159: zeros (no branch) */ \
+            x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc_[r][0]; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc_[r][1]; \
+            x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc_[r][2]; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc_[r][3]; \
+            bf16x4 h_, l_;                                                                                \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) { h_[j] = (bf16)x_[j]; l_[j] = (bf16)(x_[j] - (float)h_[j]); } \
+            *(bf16x4*)(dst_ + dstb + 4 * X3B_KC * r) = h_;                                                \
+            *(bf16x4*)(dst_ + X3B_PLANE_B + dstb + 4 * X3B_KC * r) = l_;                                  \
+        }                                                                                                 \
+    }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // k_lx3g: 32 batch rows per wave on v_mfma_f32_32x32x16_bf16 (128 per workgroup, two workgroups per CU): every LDS operand fragment
@@ -98,147 +293,29 @@ __device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; } 
 // Register plan (<= 256): rep fragments 80, O 80, S / P 16, one block in flight 24, operand sets 16 / 32.
 __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [3 buffers][block image]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r32 = lane & 31, hh = lane >> 5;
-    const int nchunk = a.Bp / G3_ROWS;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk);           // the row chunks of an item range sit on one XCD: the table block is
-    const int bc = slot % nchunk;                          // fetched from HBM once and served to the others by that XCD's L2
-    if (range >= a.ranges) return;
+    G3_WG_MAP(a.ranges, a.Bp / G3_ROWS)
     const int H = a.H;
     const int N = (bc * G3_ROWS >= a.kd_row0) ? a.Np : a.N;            // columns of this chunk's softmax (distilled rows: first Np)
-    const int nblk_all = (a.N + F3_FB - 1) / F3_FB;
-    const int per = (nblk_all + a.ranges - 1) / a.ranges;
-    const int blk_begin = range * per, blk_end = min((N + F3_FB - 1) / F3_FB, blk_begin + per);
-    const int nb_blocks = max(0, blk_end - blk_begin);
-    const int b0 = bc * G3_ROWS + wave * 32;
-    // pads of both images (k-chunks >= ceil(H/8), bytes between the quads) stay zero: the block stores never touch them
-    for (int i = tid; i < 3 * X3B_IMG_B / 16; i += 256) ((uint4*)smem_raw)[i] = make_uint4(0u, 0u, 0u, 0u);
-    // rep fragments: lane (batch row r32, k-half hh) holds rep[b0 + r32][16 ks + 8 hh + 0..7]
-    bf16x8 rh[10], rl[10];
-#pragma unroll
-    for (int ks = 0; ks < 10; ++ks) {
-        rh[ks] = *(const bf16x8*)(a.rep_hi + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
-        rl[ks] = *(const bf16x8*)(a.rep_lo + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
-    }
-    f32x16 O[5];
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
+    G3_WG_BLOCKS(a.ranges, a.N, N)
+    G3_REP_FRAGS()
+    G3_O_ZERO()
     float m_run = -INFINITY, l_run = 0.0f;
-    // ---- staging: a block = 32 table rows of H floats.  Round r (0..2) of wave w covers items 8 w.. and k-chunks 8 r..:
-    // lane l -> item + (l & 7), k-chunk + (l >> 3): the 8 lanes of an LDS write group store 8 consecutive 16-byte
-    // slots (conflict-free), and a wave's two 16-byte loads per slot touch 2 cache lines per table row.
-    const int nfull = H >> 3, rem = H & 7;                 // full k-chunks; channels of the partial one (0, 4 or 6: see launcher)
-    // round r of this lane: item it_ (= 8 wave + (lane & 7): a wave stages the same 8 items in every round), k-chunk 8 r + kc0
-    const int it_ = 8 * wave + (lane & 7), kc0 = lane >> 3;
-    const int voff = 4 * (it_ * H + 8 * kc0);              // byte offset inside the block (round r: + 256 r)
-    const int voffp = voff + 4 * (rem - 4);                // second vector of the partial k-chunk: ends with the row
-    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
-    const int dst0 = X3B_KC * kc0 + 16 * it_;               // byte offset inside a plane (round r: + 8 k-chunks)
-    f32x4_t sa[F3_RND], sb[F3_RND];
+    F3_LOCALS()
     G3_T_OFF()
     G3_A_OFF()
-    if (nb_blocks > 0) F3_LOAD(blk_begin);
-    __syncthreads();                                       // zero fill done
-    if (nb_blocks > 0) F3_STORE(0);
-    if (nb_blocks > 1) { F3_LOAD(blk_begin + 1); F3_STORE(1); }
-    int bcur = 0;                                          // i % 3
-    for (int i = 0; i < nb_blocks; ++i) {
-        __syncthreads();                                   // blocks i and i + 1 are in LDS; every wave is done with block i - 1
-        const bool more = i + 2 < nb_blocks;
-        if (more) F3_LOAD(blk_begin + i + 2);
-        const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
-        const int i0 = (blk_begin + i) * F3_FB;
-        f32x16 S;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) S[j] = 0.0f;
-        bf16x8 fa[2][2];
-        G3_LOADA(fa[0], Bh, 0);
-        G3_LOADA(fa[1], Bh, 1);
+    F3_WALK_BEGIN()
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 10; ++ks) {
-            bf16x8* A_ = fa[ks & 1];                             // {hi, lo}
-            S = mfma_bf16(A_[1], rh[ks], S);
-            S = mfma_bf16(A_[0], rl[ks], S);
-            S = mfma_bf16(A_[0], rh[ks], S);
-            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bh, ks + 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (more) F3_STORE(g3_buf_new(bcur));
+        G3_READOUT_LOADS()                                 // they do not depend on S: in flight under the softmax section
         __builtin_amdgcn_sched_barrier(0);
-        // the first transposed reads of the readout do not depend on S: in flight under the softmax section
-        bf16x4 ft[3][4];        // half sets: {items 4hh.., 8 + 4hh.., 16 + 4hh.., 24 + 4hh..} of ONE plane; hi, lo, hi, lo ...
-        G3_LOADT(ft[0], 0, 0);
-        G3_LOADT(ft[1], 0, 1);
-        G3_LOADT(ft[2], 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (i0 + F3_FB > N) {                              // tail block: items >= N are outside the softmax
-#pragma unroll
-            for (int j = 0; j < 16; ++j) if (i0 + acc_row(j, hh) >= N) S[j] = -INFINITY;
-        }
-        float tmax = S[0];
-#pragma unroll
-        for (int j = 1; j < 16; ++j) tmax = fmaxf(tmax, S[j]);
-        // the two half-waves of a lane pair (l, l + 32) hold different items of the SAME batch row; m_run is kept equal in both, so
-        // the cross-half exchange is only needed on the (rare) rescale path
-        float t2 = tmax * LOG2E;
-        if (__any(t2 > m_run + RESCALE_THR)) {
-            t2 = fmaxf(t2, __shfl_xor(t2, 32, 64));
-            const float m_new = (t2 > m_run + RESCALE_THR) ? t2 : m_run;
-            const float alpha = (m_new == -INFINITY) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run *= alpha;
-            m_run = m_new;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const float ar = __shfl(alpha, acc_row(j, hh), 64);     // O rows are batch rows
-#pragma unroll
-                for (int nb = 0; nb < 5; ++nb) O[nb][j] *= ar;
-            }
-        }
-        const float nm = -m_run;
-        float ls = 0.0f;
+        G3_SOFTMAX_HEAD()
 #pragma unroll
         for (int j = 0; j < 16; ++j) { S[j] = __builtin_amdgcn_exp2f(fmaf(S[j], LOG2E, nm)); ls += S[j]; }
         l_run += ls;
-        const bf16x8 pa0 = pack8(S, 0), pa1 = pack8(S, 1);
-        bf16x8 pl0, pl1;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { pl0[j] = (bf16)(S[j] - (float)pa0[j]); pl1[j] = (bf16)(S[8 + j] - (float)pa1[j]); }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int hs = 0; hs < 10; ++hs) {                        // half step: (channel block nb = hs >> 1, plane hs & 1)
-            bf16x4* T_ = ft[hs % 3];
-            bf16x8 v0, v1;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { v0[j] = T_[0][j]; v0[4 + j] = T_[1][j]; v1[j] = T_[2][j]; v1[4 + j] = T_[3][j]; }
-            if ((hs & 1) == 0) {                                 // hi plane of the table: P lo and P hi
-                O[hs >> 1] = mfma_bf16(pl0, v0, O[hs >> 1]);
-                O[hs >> 1] = mfma_bf16(pl1, v1, O[hs >> 1]);
-                O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);
-                O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);
-            } else {                                             // lo plane: P hi
-                O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);
-                O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);
-            }
-            if (hs + 3 < 10) G3_LOADT(ft[hs % 3], (hs + 3) >> 1, (hs + 3) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        bcur = g3_buf_next(bcur);
-    }
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (hh == 0) {
-        a.pm[(size_t)range * a.Bp + b0 + r32] = m_run;
-        a.pl[(size_t)range * a.Bp + b0 + r32] = l_tot;
-    }
-    float* o = a.pO + ((size_t)range * a.Bp + b0) * HP;
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r32] = O[nb][j];
+        G3_PSPLIT()
+        G3_READOUT()
+    F3_WALK_END()
+    G3_STORE_ML()
+    G3_STORE_O(a.pO + ((size_t)range * a.Bp + b0) * HP)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -254,73 +331,24 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
     static_assert(HT == 150, "k_lx3p: piece staging (H = 150) only");
     constexpr int H = HT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [3 buffers][block image]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r32 = lane & 31, hh = lane >> 5;
-    const int nchunk = a.Bp / G3_ROWS;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk);           // the row chunks of an item range sit on one XCD: the table block is
-    const int bc = slot % nchunk;                          // fetched from HBM once and served to the others by that XCD's L2
-    if (range >= a.ranges) return;
+    G3_WG_MAP(a.ranges, a.Bp / G3_ROWS)
     const int N = (bc * G3_ROWS >= a.kd_row0) ? a.Np : a.N;            // columns of this chunk's softmax (distilled rows: first Np)
-    const int nblk_all = (a.N + F3_FB - 1) / F3_FB;
-    const int per = (nblk_all + a.ranges - 1) / a.ranges;
-    const int blk_begin = range * per, blk_end = min((N + F3_FB - 1) / F3_FB, blk_begin + per);
-    const int nb_blocks = max(0, blk_end - blk_begin);
-    const int b0 = bc * G3_ROWS + wave * 32;
-    // pads of both images (k-chunks >= ceil(H/8), bytes between the quads) stay zero: the block stores never touch them
-    for (int i = tid; i < 3 * X3B_IMG_B / 16; i += 256) ((uint4*)smem_raw)[i] = make_uint4(0u, 0u, 0u, 0u);
-    // rep fragments: lane (batch row r32, k-half hh) holds rep[b0 + r32][16 ks + 8 hh + 0..7]
-    bf16x8 rh[10], rl[10];
-#pragma unroll
-    for (int ks = 0; ks < 10; ++ks) {
-        rh[ks] = *(const bf16x8*)(a.rep_hi + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
-        rl[ks] = *(const bf16x8*)(a.rep_lo + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
-    }
-    f32x16 O[5];
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
+    G3_WG_BLOCKS(a.ranges, a.N, N)
+    G3_REP_FRAGS()
+    G3_O_ZERO()
     float m_run = -INFINITY, l_run = 0.0f;
-    // ---- staging: a block = 32 table rows of 150 floats, as 16-byte pieces read in memory order.  Lane l -> item 8 wave + (l >> 3),
-    // piece (l & 7) + 8 r of the row's 37.5 (round r = 0..4): a wave-instruction reads 8 x 128 contiguous bytes -- ~12 cache lines,
-    // every byte used -- where k_lx3g's k-chunk mapping reads 8 x 8 half-used 32-byte pieces (~20 lines, each touched by two
-    // instructions); 5 loads instead of 6.  A piece = 4 channels = half a k-chunk slot: one ds_write_b64 per plane (two-way bank
-    // conflicts, hidden under the VGPR-to-LDS transfer of the store).  The loads go through a buffer descriptor of the table as in
-    // k_lx3g; rows beyond the table's last one come back as zeros from the hardware range check.
-    const int qb = lane & 7, ib = lane >> 3;
+    const int qb = lane & 7, ib = lane >> 3;               // P3 staging locals
     const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
     const int itb = 8 * wave + ib;
     const int voffb = itb * (4 * H) + 16 * qb;               // round r: + 128 r
     const int dstb = X3B_KC * (qb >> 1) + 16 * itb + 8 * (qb & 1);      // round r: + 4 k-chunks
     f32x4_t sc[5];
-#define P3_LOADBLK(blk_)                                                                                  \
-    {                                                                                                     \
-        const int so_ = (blk_) * (F3_FB * 4) * H;              /* byte offset of the block (< 2^31: checked by the launcher) */ \
-        _Pragma("unroll") for (int r = 0; r < 5; ++r)                                                     \
-            sc[r] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(trs, voffb + 128 * r, so_, 0)); \
-    }
-#define P3_STOREBLK(buf_)                                                                                 \
-    {                                                                                                     \
-        unsigned char* dst_ = smem_raw + (buf_) * X3B_IMG_B;                                              \
-        _Pragma("unroll") for (int r = 0; r < 5; ++r) {                                                   \
-            const int p_ = qb + 8 * r;                          /* piece 37 = channels 148, 149 and two floats of the next row */ \
-            float x_[4];                                        /* pieces 38, 39 = channels 152..159: zeros (no branch) */ \
-            x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[r][0]; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[r][1];                  \
-            x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[r][2]; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[r][3];                  \
-            bf16x4 h_, l_;                                                                                \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) { h_[j] = (bf16)x_[j]; l_[j] = (bf16)(x_[j] - (float)h_[j]); } \
-            *(bf16x4*)(dst_ + dstb + 4 * X3B_KC * r) = h_;                                                \
-            *(bf16x4*)(dst_ + X3B_PLANE_B + dstb + 4 * X3B_KC * r) = l_;                                  \
-        }                                                                                                 \
-    }
     G3_T_OFF()
     G3_A_OFF()
-    if (nb_blocks > 0) P3_LOADBLK(blk_begin);
+    if (nb_blocks > 0) P3_LOAD(sc, blk_begin);
     __syncthreads();                                       // zero fill done
-    if (nb_blocks > 0) P3_STOREBLK(0);
-    if (nb_blocks > 1) { P3_LOADBLK(blk_begin + 1); P3_STOREBLK(1); }
+    if (nb_blocks > 0) P3_STORE(sc, 0);
+    if (nb_blocks > 1) { P3_LOAD(sc, blk_begin + 1); P3_STORE(sc, 1); }
     int bcur = 0;                                          // i % 3
     // softmax of ONE pair of logits of the current block (elements 2 q_, 2 q_ + 1 of S): p = exp2(s log2e - m), running sum in
     // element order (the order of k_lx3g: bit-equal results), hi / lo split into packed pairs
@@ -331,90 +359,29 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
       bf16x2 h_; h_[0] = (bf16)p0_; h_[1] = (bf16)p1_;                                                    \
       bf16x2 l_; l_[0] = (bf16)(p0_ - (float)h_[0]); l_[1] = (bf16)(p1_ - (float)h_[1]);                  \
       ph2[q_] = __builtin_bit_cast(uint32_t, h_); pl2[q_] = __builtin_bit_cast(uint32_t, l_); }
-    f32x16 S;
-    // ---- block 0's logits: a plain S phase (no softmax to hide yet)
-    __syncthreads();                                       // blocks 0 and 1 are in LDS
-    if (nb_blocks > 0) {
-        const char* Bs = (const char*)smem_raw;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) S[j] = 0.0f;
-        bf16x8 fa[2][2];
-        G3_LOADA(fa[0], Bs, 0);
-        G3_LOADA(fa[1], Bs, 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 10; ++ks) {
-            bf16x8* A_ = fa[ks & 1];
-            S = mfma_bf16(A_[1], rh[ks], S);
-            S = mfma_bf16(A_[0], rl[ks], S);
-            S = mfma_bf16(A_[0], rh[ks], S);
-            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bs, ks + 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    // the part of an iteration in front of the S phase / softmax: tail mask, running maximum, (rare) rescale of l and O
-#define P3_HEAD()                                                                                         \
-        const int i0 = (blk_begin + i) * F3_FB;                                                           \
-        if (i0 + F3_FB > N) {                              /* tail block: items >= N are outside the softmax */ \
-            _Pragma("unroll") for (int j = 0; j < 16; ++j) if (i0 + acc_row(j, hh) >= N) S[j] = -INFINITY; \
-        }                                                                                                 \
-        float tmax = S[0];                                                                                \
-        _Pragma("unroll") for (int j = 1; j < 16; ++j) tmax = fmaxf(tmax, S[j]);                          \
-        float t2 = tmax * LOG2E;                                                                          \
-        if (__any(t2 > m_run + RESCALE_THR)) {                                                            \
-            t2 = fmaxf(t2, __shfl_xor(t2, 32, 64));                                                       \
-            const float m_new = (t2 > m_run + RESCALE_THR) ? t2 : m_run;                                  \
-            const float alpha = (m_new == -INFINITY) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);      \
-            l_run *= alpha;                                                                               \
-            m_run = m_new;                                                                                \
-            _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                              \
-                const float ar = __shfl(alpha, acc_row(j, hh), 64);     /* O rows are batch rows */       \
-                _Pragma("unroll") for (int nb = 0; nb < 5; ++nb) O[nb][j] *= ar;                          \
-            }                                                                                             \
-        }                                                                                                 \
-        const float nm = -m_run;                                                                          \
-        float ls = 0.0f;                                                                                  \
-        uint32_t ph2[8], pl2[8];                           /* P hi / lo as packed bf16 pairs */
-    // ... and behind it: the readout O += P^T . E of the current block
-#define P3_TAIL()                                                                                         \
-        l_run += ls;                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        bf16x4 ft[3][4];                                                                                  \
-        G3_LOADT(ft[0], 0, 0);                                                                            \
-        G3_LOADT(ft[1], 0, 1);                                                                            \
-        G3_LOADT(ft[2], 1, 0);                                                                            \
+    // the readout's A operands from the packed pairs ph2 / pl2
+#define P3_PACK()                                                                                         \
         bf16x8 pa0, pa1, pl0, pl1;                                                                        \
         {   typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));                                  \
             pa0 = __builtin_bit_cast(bf16x8, (u32x4_){ph2[0], ph2[1], ph2[2], ph2[3]});                   \
             pa1 = __builtin_bit_cast(bf16x8, (u32x4_){ph2[4], ph2[5], ph2[6], ph2[7]});                   \
             pl0 = __builtin_bit_cast(bf16x8, (u32x4_){pl2[0], pl2[1], pl2[2], pl2[3]});                   \
             pl1 = __builtin_bit_cast(bf16x8, (u32x4_){pl2[4], pl2[5], pl2[6], pl2[7]});                   \
-        }                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        _Pragma("unroll") for (int hs = 0; hs < 10; ++hs) {      /* half step: (channel block nb = hs >> 1, plane hs & 1) */ \
-            bf16x4* T_ = ft[hs % 3];                                                                      \
-            bf16x8 v0, v1;                                                                                \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) { v0[j] = T_[0][j]; v0[4 + j] = T_[1][j]; v1[j] = T_[2][j]; v1[4 + j] = T_[3][j]; } \
-            if ((hs & 1) == 0) {                                 /* hi plane of the table: P lo and P hi */ \
-                O[hs >> 1] = mfma_bf16(pl0, v0, O[hs >> 1]);                                              \
-                O[hs >> 1] = mfma_bf16(pl1, v1, O[hs >> 1]);                                              \
-                O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);                                              \
-                O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);                                              \
-            } else {                                             /* lo plane: P hi */                     \
-                O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);                                              \
-                O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);                                              \
-            }                                                                                             \
-            if (hs + 3 < 10) G3_LOADT(ft[hs % 3], (hs + 3) >> 1, (hs + 3) & 1);                           \
-            __builtin_amdgcn_sched_barrier(0);                                                            \
         }
+    f32x16 S;
+    // ---- block 0's logits: a plain S phase (no softmax to hide yet)
+    __syncthreads();                                       // blocks 0 and 1 are in LDS
+    if (nb_blocks > 0) G3_SPHASE(S, (const char*)smem_raw)
     int i = 0;
     for (; i + 2 < nb_blocks; ++i) {                       // (every iteration stages a block: NO branch between the S phase and the readout --
         __syncthreads();                                   //  across one the compiler sinks the whole softmax to its first use)
-        P3_LOADBLK(blk_begin + i + 2);
+        P3_LOAD(sc, blk_begin + i + 2);
         const int bnext = g3_buf_next(bcur), bnew = g3_buf_new(bcur);
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
         const char* Bs = (const char*)(smem_raw + bnext * X3B_IMG_B);
-        P3_HEAD()
+        const int i0 = (blk_begin + i) * F3_FB;
+        G3_SOFTMAX_HEAD()
+        uint32_t ph2[8], pl2[8];                           // P hi / lo as packed bf16 pairs
         // ---- the NEXT block's S phase, with this block's softmax in the shadows of its MFMAs: a matrix instruction holds the SIMD's
         // vector issue for 8 of its 32 clocks, so a few vector instructions placed BETWEEN the three MFMAs of a k-step cost nothing
         // while the matrix pipe is busy.  Per k-step: the exp of one pair of logits, and the sum / hi-lo split of the PREVIOUS pair
@@ -462,17 +429,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
         l_run += ls;
         // ---- the readout O += P^T . E of block i, with the conversion of block i + 2 (fp32 -> hi / lo image: ~17 vector instructions
         // and two 8-byte LDS stores per 16-byte piece) in the shadows of its MFMAs: round r of the staging goes with half steps 2 r, 2 r + 1
-        bf16x4 ft[3][4];
-        G3_LOADT(ft[0], 0, 0);
-        G3_LOADT(ft[1], 0, 1);
-        G3_LOADT(ft[2], 1, 0);
-        bf16x8 pa0, pa1, pl0, pl1;
-        {   typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-            pa0 = __builtin_bit_cast(bf16x8, (u32x4_){ph2[0], ph2[1], ph2[2], ph2[3]});
-            pa1 = __builtin_bit_cast(bf16x8, (u32x4_){ph2[4], ph2[5], ph2[6], ph2[7]});
-            pl0 = __builtin_bit_cast(bf16x8, (u32x4_){pl2[0], pl2[1], pl2[2], pl2[3]});
-            pl1 = __builtin_bit_cast(bf16x8, (u32x4_){pl2[4], pl2[5], pl2[6], pl2[7]});
-        }
+        G3_READOUT_LOADS()
+        P3_PACK()
         unsigned char* dstn = smem_raw + bnew * X3B_IMG_B + dstb;
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -533,46 +491,27 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
         const int bnext = g3_buf_next(bcur);
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
         const char* Bs = (const char*)(smem_raw + bnext * X3B_IMG_B);
-        P3_HEAD()
+        const int i0 = (blk_begin + i) * F3_FB;
+        G3_SOFTMAX_HEAD()
+        uint32_t ph2[8], pl2[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) P3_PAIR(q);
         f32x16 Sn;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) Sn[j] = 0.0f;
-        if (i + 1 < nb_blocks) {
-            bf16x8 fa[2][2];
-            G3_LOADA(fa[0], Bs, 0);
-            G3_LOADA(fa[1], Bs, 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ks = 0; ks < 10; ++ks) {
-                bf16x8* A_ = fa[ks & 1];
-                Sn = mfma_bf16(A_[1], rh[ks], Sn);
-                Sn = mfma_bf16(A_[0], rl[ks], Sn);
-                Sn = mfma_bf16(A_[0], rh[ks], Sn);
-                if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bs, ks + 2);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        P3_TAIL()
+        for (int j = 0; j < 16; ++j) Sn[j] = 0.0f;         // (copied into S below also when there is no next block)
+        if (i + 1 < nb_blocks) G3_SPHASE(Sn, Bs)
+        l_run += ls;
+        __builtin_amdgcn_sched_barrier(0);
+        G3_READOUT_LOADS()
+        P3_PACK()
+        G3_READOUT()
         S = Sn;
         bcur = bnext;
     }
-#undef P3_HEAD
-#undef P3_TAIL
+#undef P3_PACK
 #undef P3_PAIR
-#undef P3_STOREBLK
-#undef P3_LOADBLK
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (hh == 0) {
-        a.pm[(size_t)range * a.Bp + b0 + r32] = m_run;
-        a.pl[(size_t)range * a.Bp + b0 + r32] = l_tot;
-    }
-    float* o = a.pO + ((size_t)range * a.Bp + b0) * HP;
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r32] = O[nb][j];
+    G3_STORE_ML()
+    G3_STORE_O(a.pO + ((size_t)range * a.Bp + b0) * HP)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -588,56 +527,18 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
 __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [3 buffers][block image]
     constexpr int H = 150;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r32 = lane & 31, hh = lane >> 5;
-    const int Bk = a.Bp - a.kd_row0;
-    const int nchunk = Bk / G3_ROWS;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk);
-    const int bc = slot % nchunk;
-    if (range >= a.ranges2) return;
-    const int Np = a.Np;
-    const int nblk_all = (Np + F3_FB - 1) / F3_FB;
-    const int per = (nblk_all + a.ranges2 - 1) / a.ranges2;
-    const int blk_begin = range * per, blk_end = min(nblk_all, blk_begin + per);
-    const int nb_blocks = max(0, blk_end - blk_begin);
-    const int bk0 = bc * G3_ROWS + wave * 32;              // first exemplar row of the wave (row of the padded batch: + kd_row0)
-    for (int i = tid; i < 3 * X3B_IMG_B / 16; i += 256) ((uint4*)smem_raw)[i] = make_uint4(0u, 0u, 0u, 0u);
-    f32x16 O[5];
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
-    // table staging: k_lx3g's memory-order mapping (lane -> item 8 wave + (l >> 3), 16-byte piece (l & 7) + 8 r of the row)
-    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
+    const int Bk = a.Bp - a.kd_row0, Np = a.Np;
+    G3_WG_MAP(a.ranges2, Bk / G3_ROWS)                     // b0 = first exemplar row of the wave (row of the padded batch: + kd_row0)
+    G3_WG_BLOCKS(a.ranges2, Np, Np)
+    G3_O_ZERO()
+    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);     // P3 staging locals
     const int itb = 8 * wave + (lane >> 3), qb = lane & 7;
     const int voffb = itb * (4 * H) + 16 * qb;
     const int dstb = X3B_KC * (qb >> 1) + 16 * itb + 8 * (qb & 1);
-    f32x4_t sc[2][5];
-#define R3_LOAD(set_, blk_)                                                                               \
-    {                                                                                                     \
-        const int so_ = (blk_) * (F3_FB * 4) * H;                                                         \
-        _Pragma("unroll") for (int r = 0; r < 5; ++r)                                                     \
-            sc[set_][r] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(trs, voffb + 128 * r, so_, 0)); \
-    }
-#define R3_STORE(set_, buf_)                                                                              \
-    {                                                                                                     \
-        unsigned char* dst_ = smem_raw + (buf_) * X3B_IMG_B;                                              \
-        _Pragma("unroll") for (int r = 0; r < 5; ++r) {                                                   \
-            const int p_ = qb + 8 * r;                                                                    \
-            float x_[4];                                                                                  \
-            x_[0] = (r == 4 && p_ >= 38) ? 0.f : sc[set_][r][0]; x_[1] = (r == 4 && p_ >= 38) ? 0.f : sc[set_][r][1]; \
-            x_[2] = (r == 4 && p_ >= 37) ? 0.f : sc[set_][r][2]; x_[3] = (r == 4 && p_ >= 37) ? 0.f : sc[set_][r][3]; \
-            bf16x4 h_, l_;                                                                                \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) { h_[j] = (bf16)x_[j]; l_[j] = (bf16)(x_[j] - (float)h_[j]); } \
-            *(bf16x4*)(dst_ + dstb + 4 * X3B_KC * r) = h_;                                                \
-            *(bf16x4*)(dst_ + X3B_PLANE_B + dstb + 4 * X3B_KC * r) = l_;                                  \
-        }                                                                                                 \
-    }
+    f32x4_t sc[2][5];                                      // two staging sets
     // teacher logits of this lane's accumulator positions: row r32, items 8 q + 4 hh + 0..3 of the block (register 4 q + k)
-    const int tr = a.trow[a.kd_row0 + bk0 + r32];
-    const float tl2 = a.tlse2[a.kd_row0 + bk0 + r32];
+    const int tr = a.trow[a.kd_row0 + b0 + r32];
+    const float tl2 = a.tlse2[a.kd_row0 + b0 + r32];
     const float* trp = a.teacher + (size_t)(tr < 0 ? 0 : tr) * a.ldt + 4 * hh;
     float tt[2][16];
     // Everything inside the block loop is unconditional -- a load under a branch becomes a phi of two register sets (hipcc then spilled
@@ -663,28 +564,25 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
     G3_T_OFF()
     const int nb_full = max(0, min(blk_end, nfull_all) - blk_begin);       // full blocks of this range (the rest: the partial one)
     // prologue: blocks 0, 1 -> LDS buffers 0, 1; blocks 2, 3 -> staging sets 0, 1; teacher blocks 0, 1 -> sets 0, 1
-    R3_LOAD(0, blk_begin);
-    R3_LOAD(1, blk_begin + 1);
+    P3_LOAD(sc[0], blk_begin);
+    P3_LOAD(sc[1], blk_begin + 1);
     R3_TLOAD(0, blk_begin);
     R3_TLOAD(1, blk_begin + 1);
     __syncthreads();                                       // zero fill done
-    R3_STORE(0, 0);
-    R3_STORE(1, 1);
-    R3_LOAD(0, blk_begin + 2);
-    R3_LOAD(1, blk_begin + 3);
+    P3_STORE(sc[0], 0);
+    P3_STORE(sc[1], 1);
+    P3_LOAD(sc[0], blk_begin + 2);
+    P3_LOAD(sc[1], blk_begin + 3);
     int bcur = 0;                                          // i % 3
     // one iteration (block i, register sets e_ = i & 1): block i + 2 (requested two iterations ago) goes into the buffer block i - 1
     // was read from, block i + 4 is requested; P from the teacher set, which is then refilled with block i + 2
 #define R3_ITER(e_)                                                                                       \
     {                                                                                                     \
         lds_only_barrier();                                /* blocks i, i + 1 in LDS; every wave is done with block i - 1 */ \
-        R3_STORE(e_, g3_buf_new(bcur));                                                                            \
-        R3_LOAD(e_, blk_begin + i + 4);                                                                   \
+        P3_STORE(sc[e_], g3_buf_new(bcur));                                                               \
+        P3_LOAD(sc[e_], blk_begin + i + 4);                                                               \
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);                                      \
-        bf16x4 ft[3][4];                                                                                  \
-        G3_LOADT(ft[0], 0, 0);                                                                            \
-        G3_LOADT(ft[1], 0, 1);                                                                            \
-        G3_LOADT(ft[2], 1, 0);                                                                            \
+        G3_READOUT_LOADS()                                                                                \
         f32x16 S;                                                                                         \
         const int lim_ = (tr >= 0) ? Np - (blk_begin + i) * F3_FB - 4 * hh : 0;     /* items of this lane's positions inside [0, Np) */ \
         _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                                  \
@@ -692,26 +590,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
             S[j] = ((j & 3) + 8 * (j >> 2) < lim_) ? x_ : 0.0f;                                           \
         }                                                                                                 \
         R3_TLOAD(e_, blk_begin + i + 2);                                                                  \
-        const bf16x8 pa0 = pack8(S, 0), pa1 = pack8(S, 1);                                                \
-        bf16x8 pl0, pl1;                                                                                  \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) { pl0[j] = (bf16)(S[j] - (float)pa0[j]); pl1[j] = (bf16)(S[8 + j] - (float)pa1[j]); } \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        _Pragma("unroll") for (int hs = 0; hs < 10; ++hs) {                                               \
-            bf16x4* T_ = ft[hs % 3];                                                                      \
-            bf16x8 v0, v1;                                                                                \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) { v0[j] = T_[0][j]; v0[4 + j] = T_[1][j]; v1[j] = T_[2][j]; v1[4 + j] = T_[3][j]; } \
-            if ((hs & 1) == 0) {                                                                          \
-                O[hs >> 1] = mfma_bf16(pl0, v0, O[hs >> 1]);                                              \
-                O[hs >> 1] = mfma_bf16(pl1, v1, O[hs >> 1]);                                              \
-                O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);                                              \
-                O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);                                              \
-            } else {                                                                                      \
-                O[hs >> 1] = mfma_bf16(pa0, v0, O[hs >> 1]);                                              \
-                O[hs >> 1] = mfma_bf16(pa1, v1, O[hs >> 1]);                                              \
-            }                                                                                             \
-            if (hs + 3 < 10) G3_LOADT(ft[hs % 3], (hs + 3) >> 1, (hs + 3) & 1);                           \
-            __builtin_amdgcn_sched_barrier(0);                                                            \
-        }                                                                                                 \
+        G3_PSPLIT()                                                                                       \
+        G3_READOUT()                                                                                      \
         bcur = g3_buf_next(bcur);                                                                         \
         ++i;                                                                                              \
     }
@@ -727,14 +607,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
 #undef R3_TSLOW
 #undef R3_ITER
 #undef R3_TLOAD
-#undef R3_STORE
-#undef R3_LOAD
-    float* o2 = a.pO2 + ((size_t)range * Bk + bk0) * HP;
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o2[(size_t)acc_row(j, hh) * HP + 32 * nb + r32] = O[nb][j];
+    G3_STORE_O(a.pO2 + ((size_t)range * Bk + b0) * HP)
 }
+
+// ---- launchers.  The grid of the shared walk: one workgroup per (item range, 128-row chunk)
+static dim3 x3_grid(int ranges, int rows) { return dim3(ranges * (rows / G3_ROWS)); }
+// the block offsets of the buffer loads are 32-bit
+static bool x3_table_fits(int vrows, int H) { return (long)vrows * H * 4 < (1l << 31); }
 
 // teacher readout launch: x.ranges2 item ranges x (Bp - kd_row0) / 128 chunks.  false: the shape is not k_lx3r's (caller falls back)
 bool lx3r_supports(const Lx3Args& x) {
@@ -742,25 +621,30 @@ bool lx3r_supports(const Lx3Args& x) {
 }
 int lx3r_launch(const Lx3Args& x, void* stream) {
     if (int e = ader_dyn_lds<k_lx3r>(3 * X3B_IMG_B)) return e;
-    hipLaunchKernelGGL(k_lx3r, dim3(x.ranges2 * ((x.Bp - x.kd_row0) / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
+    hipLaunchKernelGGL(k_lx3r, x3_grid(x.ranges2, x.Bp - x.kd_row0), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
     return 0;
 }
 
 bool lx3f_supports(int H) { return (H & 1) == 0 && H >= 8 && H <= HP && ((H & 7) == 0 || (H & 7) == 4 || (H & 7) == 6); }
+// what the filters k_lx3k / k_lx3t ask of a call's shapes: whole 128-row chunks, an H with an F3 staging, N items of an 8-byte
+// aligned table that the 32-bit block offsets reach
+static bool x3_filter_shapes_ok(const float* emb, int item_num, int B, int Bp, int H, int N) {
+    return Bp % G3_ROWS == 0 && B <= Bp && lx3f_supports(H) && N >= 1 && N <= item_num && !((uintptr_t)emb & 7) && x3_table_fits(item_num, H);
+}
 
 // x.ranges must be ader_lbf_ranges(x.N, x.Bp); Bp % 128 == 0
 int lx3g_launch(const Lx3Args& x, void* stream) {
     if (int e = ader_dyn_lds<k_lx3g>(3 * X3B_IMG_B)) return e;
-    if ((long)x.vrows * x.H * 4 >= (1l << 31)) return -2;          // the block offsets of the buffer loads are 32-bit
-    hipLaunchKernelGGL(k_lx3g, dim3(x.ranges * (x.Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
+    if (!x3_table_fits(x.vrows, x.H)) return -2;
+    hipLaunchKernelGGL(k_lx3g, x3_grid(x.ranges, x.Bp), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
     return 0;
 }
 
 int lx3p_launch(const Lx3Args& x, void* stream) {
     if (int e = ader_dyn_lds<k_lx3p<150>>(3 * X3B_IMG_B)) return e;
-    if ((long)x.vrows * x.H * 4 >= (1l << 31)) return -2;
+    if (!x3_table_fits(x.vrows, x.H)) return -2;
     if (x.H != 150) return lx3g_launch(x, stream);                 // (the pipelined form exists for the reference's hidden size only)
-    hipLaunchKernelGGL(k_lx3p<150>, dim3(x.ranges * (x.Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
+    hipLaunchKernelGGL(k_lx3p<150>, x3_grid(x.ranges, x.Bp), dim3(256), 3 * X3B_IMG_B, (hipStream_t)stream, x);
     return 0;
 }
 
@@ -830,27 +714,10 @@ __global__ __launch_bounds__(256) void k_rank_delta(const float* __restrict__ re
 // LDS) admit two workgroups per CU whatever the registers: the bound is k_lx3g's (256, 2), and a tighter one would only buy spills.
 __global__ __launch_bounds__(256, 2) void k_lx3k(RankX3Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [3 buffers][block image]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r32 = lane & 31, hh = lane >> 5;
-    const int nchunk = a.Bp / G3_ROWS;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk);           // as k_lx3g: the row chunks of an item range sit on one XCD
-    const int bc = slot % nchunk;
-    if (range >= a.ranges) return;
+    G3_WG_MAP(a.ranges, a.Bp / G3_ROWS)
     const int H = a.H, N = a.N;
-    const int nblk_all = (N + F3_FB - 1) / F3_FB;
-    const int per = (nblk_all + a.ranges - 1) / a.ranges;
-    const int blk_begin = range * per, blk_end = min(nblk_all, blk_begin + per);
-    const int nb_blocks = max(0, blk_end - blk_begin);
-    const int b0 = bc * G3_ROWS + wave * 32;
-    for (int i = tid; i < 3 * X3B_IMG_B / 16; i += 256) ((uint4*)smem_raw)[i] = make_uint4(0u, 0u, 0u, 0u);
-    bf16x8 rh[10], rl[10];
-#pragma unroll
-    for (int ks = 0; ks < 10; ++ks) {
-        rh[ks] = *(const bf16x8*)(a.rep_hi + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
-        rl[ks] = *(const bf16x8*)(a.rep_lo + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
-    }
+    G3_WG_BLOCKS(a.ranges, N, N)
+    G3_REP_FRAGS()
     // this lane's batch row: live items [0, nc) without the target; the band around its exact target logit
     const int b = b0 + r32;
     const int nc = min(a.ncol[b], N), tgt = a.target[b] - 1;
@@ -858,43 +725,9 @@ __global__ __launch_bounds__(256, 2) void k_lx3k(RankX3Args a) {
     const float s_hi = tl + dl, s_lo = tl - dl;
     int cnt = 0;
     bool full = false;
-    // staging locals of F3_LOAD / F3_STORE: as k_lx3g
-    const int nfull = H >> 3, rem = H & 7;
-    const int it_ = 8 * wave + (lane & 7), kc0 = lane >> 3;
-    const int voff = 4 * (it_ * H + 8 * kc0);
-    const int voffp = voff + 4 * (rem - 4);
-    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
-    const int dst0 = X3B_KC * kc0 + 16 * it_;
-    f32x4_t sa[F3_RND], sb[F3_RND];
+    F3_LOCALS()
     G3_A_OFF()
-    if (nb_blocks > 0) F3_LOAD(blk_begin);
-    __syncthreads();                                       // zero fill done
-    if (nb_blocks > 0) F3_STORE(0);
-    if (nb_blocks > 1) { F3_LOAD(blk_begin + 1); F3_STORE(1); }
-    int bcur = 0;                                          // i % 3
-    for (int i = 0; i < nb_blocks; ++i) {
-        __syncthreads();                                   // blocks i and i + 1 are in LDS; every wave is done with block i - 1
-        const bool more = i + 2 < nb_blocks;
-        if (more) F3_LOAD(blk_begin + i + 2);
-        const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
-        const int i0 = (blk_begin + i) * F3_FB;
-        f32x16 S;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) S[j] = 0.0f;
-        bf16x8 fa[2][2];
-        G3_LOADA(fa[0], Bh, 0);
-        G3_LOADA(fa[1], Bh, 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 10; ++ks) {
-            bf16x8* A_ = fa[ks & 1];                             // {hi, lo}
-            S = mfma_bf16(A_[1], rh[ks], S);
-            S = mfma_bf16(A_[0], rl[ks], S);
-            S = mfma_bf16(A_[0], rh[ks], S);
-            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bh, ks + 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (more) F3_STORE(g3_buf_new(bcur));
+    F3_WALK_BEGIN()
         unsigned band = 0u;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -915,8 +748,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3k(RankX3Args a) {
                     } else full = true;
                 }
         }
-        bcur = g3_buf_next(bcur);
-    }
+    F3_WALK_END()
     cnt += __shfl_xor(cnt, 32, 64);                        // the two half-waves hold different items of the same batch row
     if (hh == 0 && cnt) atomicAdd(a.rank + b, cnt);
 }
@@ -976,31 +808,14 @@ struct TopkX3Args {
 
 __global__ __launch_bounds__(256, 1) void k_lx3t(TopkX3Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // [3 buffers][block image] | buf [128][keep + 32] | cnt [128]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r32 = lane & 31, hh = lane >> 5;
-    const int nchunk = a.Bp / G3_ROWS;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk);           // as k_lx3g: the row chunks of an item range sit on one XCD
-    const int bc = slot % nchunk;
-    if (range >= a.ranges) return;
+    G3_WG_MAP(a.ranges, a.Bp / G3_ROWS)
     const int H = a.H, N = a.N;
-    const int nblk_all = (N + F3_FB - 1) / F3_FB;
-    const int per = (nblk_all + a.ranges - 1) / a.ranges;
-    const int blk_begin = range * per, blk_end = min(nblk_all, blk_begin + per);
-    const int nb_blocks = max(0, blk_end - blk_begin);
-    const int b0 = bc * G3_ROWS + wave * 32;
+    G3_WG_BLOCKS(a.ranges, N, N)
     const int k = a.k, keep = a.keep, ldb = keep + F3_FB;
     u64* buf = (u64*)(smem_raw + 3 * X3B_IMG_B);
     int* cnt = (int*)(buf + G3_ROWS * ldb);
-    for (int i = tid; i < 3 * X3B_IMG_B / 16; i += 256) ((uint4*)smem_raw)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (tid < G3_ROWS) cnt[tid] = 0;
-    bf16x8 rh[10], rl[10];
-#pragma unroll
-    for (int ks = 0; ks < 10; ++ks) {
-        rh[ks] = *(const bf16x8*)(a.rep_hi + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
-        rl[ks] = *(const bf16x8*)(a.rep_lo + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
-    }
+    G3_REP_FRAGS()
     // this lane's batch row (shared with lane ^ 32, which holds the block's other 16 items): live items [0, nc) without the seen ids
     const int b = b0 + r32, wrow = wave * 32 + r32;
     const int nc = min(a.ncol[b], N);
@@ -1017,43 +832,9 @@ __global__ __launch_bounds__(256, 1) void k_lx3t(TopkX3Args a) {
         for (int t = hh; t < a.seen_ld; t += 2)
             any_seen |= (unsigned)(srow[t] - 1 - blk_begin * F3_FB) < (unsigned)(nb_blocks * F3_FB);        // id 0 wraps: never inside
     any_seen |= __shfl_xor(any_seen, 32, 64);
-    // staging locals of F3_LOAD / F3_STORE: as k_lx3g
-    const int nfull = H >> 3, rem = H & 7;
-    const int it_ = 8 * wave + (lane & 7), kc0 = lane >> 3;
-    const int voff = 4 * (it_ * H + 8 * kc0);
-    const int voffp = voff + 4 * (rem - 4);
-    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
-    const int dst0 = X3B_KC * kc0 + 16 * it_;
-    f32x4_t sa[F3_RND], sb[F3_RND];
+    F3_LOCALS()
     G3_A_OFF()
-    if (nb_blocks > 0) F3_LOAD(blk_begin);
-    __syncthreads();                                       // zero fill done
-    if (nb_blocks > 0) F3_STORE(0);
-    if (nb_blocks > 1) { F3_LOAD(blk_begin + 1); F3_STORE(1); }
-    int bcur = 0;                                          // i % 3
-    for (int i = 0; i < nb_blocks; ++i) {
-        __syncthreads();                                   // blocks i and i + 1 are in LDS; every wave is done with block i - 1
-        const bool more = i + 2 < nb_blocks;
-        if (more) F3_LOAD(blk_begin + i + 2);
-        const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
-        const int i0 = (blk_begin + i) * F3_FB;
-        f32x16 S;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) S[j] = 0.0f;
-        bf16x8 fa[2][2];
-        G3_LOADA(fa[0], Bh, 0);
-        G3_LOADA(fa[1], Bh, 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 10; ++ks) {
-            bf16x8* A_ = fa[ks & 1];                             // {hi, lo}
-            S = mfma_bf16(A_[1], rh[ks], S);
-            S = mfma_bf16(A_[0], rl[ks], S);
-            S = mfma_bf16(A_[0], rh[ks], S);
-            if (ks + 2 < 10) G3_LOADA(fa[ks & 1], Bh, ks + 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (more) F3_STORE(g3_buf_new(bcur));
+    F3_WALK_BEGIN()
         unsigned sm = 0u;                                  // bit i: item i0 + i is in the row's seen list
         if (any_seen)
             for (int t = hh; t < a.seen_ld; t += 2) {
@@ -1108,8 +889,7 @@ __global__ __launch_bounds__(256, 1) void k_lx3t(TopkX3Args a) {
             if (lane == 0) cnt[wave * 32 + rr] = min(m, keep);
             if (r32 == rr) { lo = nlo; ovf |= m > keep; }  // more than keep keys inside the band: the row's result is discarded
         }
-        bcur = g3_buf_next(bcur);
-    }
+    F3_WALK_END()
     ovf |= __shfl_xor(ovf, 32, 64);
     if (hh == 0 && ovf) atomicOr(a.status + b, 1);
     u64* o = a.part3 + ((size_t)range * a.Bp + b0) * keep;  // the wave's 32 rows (an empty range writes zeros: no candidate)
@@ -1234,8 +1014,7 @@ int ader_rank_targets_x3(const float* rep, const float* emb, int item_num, int B
                          const int* ncol, void* rep_hi, void* rep_lo, float* tlogit, float* delta, const float* emax, int* cand, int cap,
                          int* diag, int* rank, void* stream) {
     if (B <= 0) return 0;
-    if (Bp % G3_ROWS != 0 || B > Bp || !lx3f_supports(H) || N < 1 || N > item_num || ((uintptr_t)emb & 7) || cap < 0) return -2;
-    if ((long)item_num * H * 4 >= (1l << 31)) return -2;          // the block offsets of the buffer loads are 32-bit
+    if (!x3_filter_shapes_ok(emb, item_num, B, Bp, H, N) || cap < 0) return -2;
     if (int e = ader_dyn_lds<k_lx3k>(3 * X3B_IMG_B)) return e;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(rank, 0, sizeof(int) * (size_t)Bp, st);
@@ -1248,7 +1027,7 @@ int ader_rank_targets_x3(const float* rep, const float* emb, int item_num, int B
     a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo;
     a.Bp = Bp; a.H = H; a.N = N; a.ranges = ader_lbf_ranges(N, Bp);
     a.target = target; a.ncol = ncol; a.tlogit = tlogit; a.delta = delta; a.cand = cand; a.cap = cap; a.diag = diag; a.rank = rank;
-    hipLaunchKernelGGL(k_lx3k, dim3(a.ranges * (Bp / G3_ROWS)), dim3(256), 3 * X3B_IMG_B, st, a);
+    hipLaunchKernelGGL(k_lx3k, x3_grid(a.ranges, Bp), dim3(256), 3 * X3B_IMG_B, st, a);
     HIP_LAUNCH_CHECK();
     return rank_pairs_launch(rep, emb, B, Bp, H, N, target, ncol, tlogit, delta, cand, cap, diag, rank, stream);
 }
@@ -1274,10 +1053,8 @@ int ader_topk_x3_ranges(int N, int Bp) {
 int ader_topk_items_x3(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* ncol, const int* seen,
                        int seen_ld, int k, int band, void* rep_hi, void* rep_lo, float* delta, const float* emax,
                        unsigned long long* part3, int* status, int* diag, int* items, float* scores, void* stream) {
-    if (k < 1 || k > TK3_KMAX || band < 0 || band > TK3_BANDMAX || Bp % G3_ROWS != 0 || B > Bp || !lx3f_supports(H) || N < 1 ||
-        N > item_num || ((uintptr_t)emb & 7) || (seen && seen_ld < 1))
+    if (k < 1 || k > TK3_KMAX || band < 0 || band > TK3_BANDMAX || !x3_filter_shapes_ok(emb, item_num, B, Bp, H, N) || (seen && seen_ld < 1))
         return -2;
-    if ((long)item_num * H * 4 >= (1l << 31)) return -2;          // the block offsets of the buffer loads are 32-bit
     if (B <= 0) return 0;
     TopkX3Args a = {};
     a.rep = rep; a.emb1 = emb + H; a.vrows = item_num; a.rep_hi = (const bf16*)rep_hi; a.rep_lo = (const bf16*)rep_lo;
@@ -1294,7 +1071,7 @@ int ader_topk_items_x3(const float* rep, const float* emb, int item_num, int B, 
     if (e != hipSuccess) return (int)e;
     if (int rc = ader_lx3_prep(rep, rep_hi, rep_lo, B, Bp, H, stream)) return rc;
     hipLaunchKernelGGL(k_rank_delta, dim3(Bp / 4), dim3(256), 0, st, rep, B, Bp, H, emax, delta);
-    hipLaunchKernelGGL(k_lx3t, dim3(a.ranges * (Bp / G3_ROWS)), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(k_lx3t, x3_grid(a.ranges, Bp), dim3(256), lds, st, a);
     hipLaunchKernelGGL(k_topk3_finish, dim3(B), dim3(256), lds_fin, st, a);
     HIP_LAUNCH_CHECK();
     return 0;
