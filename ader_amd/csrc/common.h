@@ -41,6 +41,7 @@ static inline int shard_items(int N, int item_begin, int item_count) {
 // status bits written by kernels into the engine's status word
 #define ADER_ST_BAD_ID 1
 #define ADER_ST_BAD_TROW 2      // a teacher row index >= the number of stored teacher representations (ader_teacher_rows)
+#define ADER_ST_BAD_CAND 4      // a candidate list that is not strictly ascending, or holds an id < 1 (ader_topk_items_cand)
 
 // ---------------------------------------------------------------- counter-based dropout mask
 // keep(idx) = (lowbias32(idx ^ key) >> 8) >= thr ; key = f(seed, step, site) computed on the host.

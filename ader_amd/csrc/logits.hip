@@ -10,7 +10,8 @@
 //   k_logits_tile<RANK>  per-row count of items ranked before the target           (Evaluator, util.py:323-325)
 //   k_logits_tile<STORE> dense logits (teacher logits of selected exemplars, util.py:433; model.logits fetch)
 //   k_topk_tile/_merge   per-row best k items by (logit descending, id ascending), the STORE bits       (Engine.recommend)
-//   k_teacher_rows       the STORE bits of a step's exemplar rows from stored teacher representations  (TeacherRep, util.py:433)
+//   k_topk_cand/_merge   the same over the items of a candidate id list, its table rows gathered: work follows the list  (Engine.recommend_among)
+//   k_teacher_rows      the STORE bits of a step's exemplar rows from stored teacher representations  (TeacherRep, util.py:433)
 //   k_logits_bwd_drep    dRep[b,:] = sum_n dlogit[b,n] E[n,:]   (b-chunk x item-range workgroups, slabs)
 //   k_logits_bwd_de      dE[n,:]   = sum_b dlogit[b,n] rep[b,:] (item-tile workgroups; rows written once, no atomics)
 // with dlogit[b,n] = w_b * (softmax_b[n] - target_b[n]) for n < ncol_b, else 0.
@@ -707,6 +708,185 @@ __global__ __launch_bounds__(512) void k_teacher_rows(TeachArgs a) {
     }
 }
 
+// ============================================================================================= exact top-K items of a candidate list
+// ader_topk_items_cand: ader_topk_items' contract over the items of one strictly ascending id list cand[M] shared by every row, with
+// work proportional to M.  k_topk_tile's shape, operand layout, mma_tile<2> call, filter / append / compact and row buffers; tile s is
+// positions [64s, 64s + 64) of the list and its 64 table rows are GATHERED into E_l, in stage_tile's element order (consecutive
+// threads cover consecutive floats of one table row).  A (row, item) result of the chain does not depend on which items share its tile
+// (k_teacher_rows relies on the same), so a score is k_logits_tile<MODE_STORE>'s float32, and the key carries the true item id: the
+// order, ties included, is ader_topk_items'.  Pipeline per tile s: its rows are written to E_l from registers, the rows of tile s + 1
+// are loaded into registers under the MFMAs, and the ids of tile s + 2 are fetched by wave 0 (the row addresses depend on the ids, so
+// the ids run one tile ahead of the rows).  The ids of a tile and the mask of its live positions sit in LDS, two slots: the loads of
+// tile s + 1 read one slot while the keys and the seen mask of tile s are built from the other.
+// Position p is live iff p < M, cand[p] >= 1, cand[p] > cand[p-1] and cand[p] <= N; for a row it also needs cand[p] <= ncol[row] and a
+// clear seen bit.  A dead position gets a zero operand row and is never proposed: no id outside [1, N] forms an address.  cand[p] < 1
+// or cand[p] <= cand[p-1] flags ADER_ST_BAD_CAND: every list that is not strictly ascending is reported, and its result is unspecified
+// (two equal keys in a row would break the rank-by-count compaction) but every access stays in bounds -- cnt <= k + 64 holds for any
+// list, since a 64-position tile proposes at most 64 keys per row.
+// Seen ids: the tile's ids are ascending (positions past M hold INT_MAX), so the 8 threads of a row look each seen id up by binary
+// search and set the bit of the position it sits at.
+struct TopkCandArgs {
+    TopkArgs t;            // N: the last item of the table that may be read; ranges, part: over the M positions
+    const int* cand;       // [M] strictly ascending 1-based item ids
+    int M;
+    int* status;           // status word or NULL
+};
+
+__global__ __launch_bounds__(512) void k_topk_cand(TopkCandArgs ca) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const TopkArgs& a = ca.t;
+    float* E_l = smem;                                       // [TI][LDE]
+    float* R_l = E_l + TI * LDE;                             // [TB][LDE]
+    u64* buf = (u64*)(R_l + TB * LDE);                       // [TB][k + 64]
+    const int k = a.k, ldb = k + TI;
+    u64* thr = buf + TB * ldb;                               // [TB]
+    u64* msk = thr + TB;                                     // [TB] bit i: the id at position i of the tile is in the row's seen list
+    u64* lm = msk + TB;                                      // [2] bit i: position i of the slot's tile is live
+    int* cnt = (int*)(lm + 2);                               // [TB]
+    int* idl = cnt + TB;                                     // [2][TI] the slot's ids
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int mw = wave & 3, nw = wave >> 2;
+    const int H = a.H, ksteps = (H + 3) >> 2;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int nchunk = a.Bp / TB;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int range = xcd + 8 * (slot / nchunk), bc = slot % nchunk;
+    if (range >= a.ranges) return;
+    const int nsub_total = (ca.M + TI - 1) / TI;
+    const int s_begin = (int)((long)range * nsub_total / a.ranges), s_end = (int)((long)(range + 1) * nsub_total / a.ranges);
+    int nid = 0;                                             // wave 0: the id at position `lane` of the tile fetched last, and that tile's
+    u64 nlm = 0;                                             // live mask
+    auto fetch_ids = [&](int s) {                            // wave 0 only
+        const int p = s * TI + lane;
+        int id = 0x7fffffff;
+        bool bad = false;
+        if (p < ca.M) {
+            id = ca.cand[p];
+            const int prev = p > 0 ? ca.cand[p - 1] : 0;
+            bad = id < 1 || id <= prev;
+        }
+        const u64 anybad = __ballot(bad);
+        if (anybad && lane == 0 && ca.status) atomicOr(ca.status, ADER_ST_BAD_CAND);
+        nid = id;
+        nlm = __ballot(p < ca.M && !bad && id <= a.N);
+    };
+    if (wave == 0 && s_begin < s_end) {
+        fetch_ids(s_begin);
+        idl[(s_begin & 1) * TI + lane] = nid;
+        if (lane == 0) lm[s_begin & 1] = nlm;
+    }
+    for (int i = tid; i < 64 * LDE; i += 512) {              // stage_tile's layout, written out (see k_topk_tile)
+        const int r = i / LDE, c = i - r * LDE;
+        R_l[i] = (bc * TB + r < a.B && c < H) ? a.rep[(size_t)(bc * TB + r) * H + c] : 0.0f;
+    }
+    if (tid < TB) { thr[tid] = 0; msk[tid] = 0; cnt[tid] = 0; }
+    int nc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) nc[j] = a.ncol[bc * TB + nw * 32 + j * 16 + r16];
+    float pre[TOPK_STAGE_REGS];                              // the next tile, in stage_tile's element order
+    auto load_tile = [&](int sl) {                           // the rows of the tile whose ids are in slot sl
+        const int* ids = idl + sl * TI;
+        const u64 live = lm[sl];
+#pragma unroll
+        for (int n = 0; n < TOPK_STAGE_REGS; ++n) {
+            const int i = tid + n * 512, r = (i / LDE) & (TI - 1), c = i - (i / LDE) * LDE;
+            const bool ok = i < 64 * LDE && c < H && ((live >> r) & 1ull);
+            pre[n] = ok ? a.emb1[(size_t)(ids[r] - 1) * H + c] : 0.0f;      // live: 1 <= ids[r] <= N
+        }
+    };
+    __syncthreads();                                         // the first tile's ids are in LDS
+    if (s_begin < s_end) load_tile(s_begin & 1);
+    if (wave == 0 && s_begin + 1 < s_end) fetch_ids(s_begin + 1);
+    for (int s = s_begin; s < s_end; ++s) {
+        const int cur = s & 1;
+        const int* ids = idl + cur * TI;
+        __syncthreads();                                     // the previous tile's MFMA reads, filter and compaction are done
+#pragma unroll
+        for (int n = 0; n < TOPK_STAGE_REGS; ++n)
+            if (tid + n * 512 < 64 * LDE) E_l[tid + n * 512] = pre[n];
+        if (wave == 0 && s + 1 < s_end) {                    // the other slot's last readers (tile s - 1) are behind the barrier above
+            idl[(cur ^ 1) * TI + lane] = nid;
+            if (lane == 0) lm[cur ^ 1] = nlm;
+        }
+        if (a.seen) {                                        // thread (row = tid / 8, part = tid % 8): the 8 lanes of a row are neighbours
+            const int row = tid >> 3, b = bc * TB + row;
+            const int lo = ids[0], hi = ids[TI - 1];
+            u64 m = 0;
+            if (b < a.B)
+                for (int t = tid & 7; t < a.seen_ld; t += 8) {
+                    const int sid = a.seen[(size_t)b * a.seen_ld + t];
+                    if (sid < lo || sid > hi) continue;
+                    int x = 0;                               // the first position whose id is >= sid: x + h - 1 <= 62, x <= 63
+#pragma unroll
+                    for (int h = TI / 2; h; h >>= 1)
+                        if (ids[x + h - 1] < sid) x += h;
+                    if (ids[x] == sid) m |= 1ull << x;
+                }
+            m |= __shfl_xor(m, 1, 64); m |= __shfl_xor(m, 2, 64); m |= __shfl_xor(m, 4, 64);
+            if ((tid & 7) == 0) msk[row] = m;
+        }
+        __syncthreads();
+        if (s + 1 < s_end) load_tile(cur ^ 1);
+        if (wave == 0 && s + 2 < s_end) fetch_ids(s + 2);
+        f32x4 acc[2];
+        acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        {   // mma_tile<2>(E_l + mw * 16 * LDE, LDE, 1, R_l + nw * 32 * LDE, 1, LDE, ksteps, acc, lane), written out: the same operands
+            // into the same instruction in the same k order, hence the same bits.  One more caller of mma_tile<2> changes the code the
+            // compiler emits for k_logits_bwd_de / _drep (tools/isa_digest.py), as one more caller of stage_tile does
+            const float* ap = E_l + (mw * 16 + r16) * LDE + q;
+            const float* bp = R_l + (nw * 32 + r16) * LDE + q;
+            for (int ks = 0; ks < ksteps; ++ks) {
+                const float av = ap[0];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bp[j * 16 * LDE], acc[j], 0, 0, 0);
+                ap += 4;
+                bp += 4;
+            }
+        }
+        const int il0 = mw * 16 + q * 4;                     // this lane's 4 consecutive positions of the tile
+        const u64 dead = ~lm[cur];
+        int id4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) id4[r] = ids[il0 + r];
+        int over = 0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int bl = nw * 32 + j * 16 + r16;           // batch row within the chunk
+            const u64 t = thr[bl];
+            const unsigned sm = (unsigned)((msk[bl] | dead) >> il0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const u64 key = topk_key(acc[j][r], id4[r]);
+                if (!((sm >> r) & 1u) && id4[r] <= nc[j] && key > t) {
+                    const int p = atomicAdd(cnt + bl, 1);    // p < k + 64 (the invariant of k_topk_tile)
+                    buf[bl * ldb + p] = key;
+                    over |= (p >= k);
+                }
+            }
+        }
+        if (__syncthreads_or(over)) {                        // some row holds more than k keys: wave w compacts rows 8w .. 8w+7
+            for (int rr = 0; rr < TB / 8; ++rr) {
+                const int row = wave * (TB / 8) + rr, n = cnt[row];
+                if (n <= k) continue;                        // (wave-uniform)
+                u64* bp = buf + row * ldb;
+                const u64 e0 = lane < n ? bp[lane] : 0, e1 = lane + 64 < n ? bp[lane + 64] : 0;      // n <= k + 64 <= 128
+                int r0 = 0, r1 = 0;                          // keys of a row are distinct: rank = number of larger keys
+                for (int i = 0; i < n; ++i) { const u64 x = bp[i]; r0 += x > e0; r1 += x > e1; }
+                // in place: a rank depends on every read of the loop, and one wave's LDS operations are performed in order
+                if (lane < n && r0 < k) { bp[r0] = e0; if (r0 == k - 1) thr[row] = e0; }
+                if (lane + 64 < n && r1 < k) { bp[r1] = e1; if (r1 == k - 1) thr[row] = e1; }
+                if (lane == 0) cnt[row] = k;
+            }
+        }
+    }
+    __syncthreads();
+    u64* o = a.part + ((size_t)range * a.Bp + bc * TB) * k;
+    for (int i = tid; i < TB * k; i += 512) {
+        const int row = i / k, j = i - row * k;
+        o[i] = j < cnt[row] ? buf[row * ldb + j] : 0;        // (an empty range writes zeros: no candidate)
+    }
+}
+
 // ============================================================================================= C ABI
 static const size_t kTileLds = (size_t)(2 * 64 * LDE + 4 * TB * 3 + MAXB * 3) * sizeof(float);
 static const size_t kBwdLds = (size_t)(2 * 64 * LDE + 64 * LDD) * sizeof(float);
@@ -905,6 +1085,31 @@ int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, in
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_topk_tile, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, a);
+    hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, st, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+// ader_topk_items over the items of cand[0:M] only (kernel above): a strictly ascending list of 1-based ids, shared by every row; ids
+// above N are ignored, as seen ids above N are.  N: no table row beyond item N is read.  M = 0: every row is padding (cand may be NULL).
+// part: ader_topk_ranges(M,Bp) * Bp * k keys of scratch.  status (NULL: none): ADER_ST_BAD_CAND is OR-ed in when the list is not
+// strictly ascending or holds an id < 1; the result is then unspecified, and nothing outside the table is read.  Enqueue only.
+int ader_topk_items_cand(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* cand, int M,
+                         const int* seen, int seen_ld, int k, unsigned long long* part, int* items, float* scores, int* status,
+                         void* stream) {
+    if (k < 1 || k > TOPK_KMAX || Bp % TB != 0 || Bp > MAXB || B > Bp || H > HP || H < 1 || N < 1 || M < 0 || (M > 0 && !cand) ||
+        (seen && seen_ld < 1)) return -2;
+    if (B <= 0) return 0;
+    TopkCandArgs ca;
+    TopkArgs& a = ca.t;
+    a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ncol = ncol; a.seen = seen; a.seen_ld = seen_ld; a.k = k;
+    a.ranges = ader_topk_ranges(M, Bp); a.part = part; a.items = items; a.scores = scores;
+    ca.cand = cand; ca.M = M; ca.status = status;
+    const size_t lds = (size_t)(2 * 64 * LDE) * sizeof(float) + (size_t)TB * (k + TI) * sizeof(u64) + TB * (2 * sizeof(u64) + sizeof(int)) +
+                       2 * sizeof(u64) + 2 * TI * sizeof(int);
+    const int rc = ader_dyn_lds<k_topk_cand>(lds);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_topk_cand, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, ca);
     hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, st, a);
     HIP_LAUNCH_CHECK();
     return 0;

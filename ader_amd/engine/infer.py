@@ -26,6 +26,26 @@ def _check_topk_dtype(v):
     return v
 
 
+def candidate_ids(candidates, N, item_num):
+    """The candidate list of Engine.recommend_among in the form ader_topk_items_cand takes: a 1-D integer array or tensor of item ids ->
+    sorted, unique int32 ids (numpy) that are <= N.  Ids in (N, item_num] are dropped silently, as seen ids above N are; a
+    non-integer dtype, more or fewer than one dimension, or an id outside [1, item_num] raise RuntimeError."""
+    if isinstance(candidates, torch.Tensor):
+        a = candidates.detach().cpu().numpy()
+    else:
+        a = np.asarray(candidates)
+        if a.size == 0 and a.ndim == 1 and not isinstance(candidates, np.ndarray):
+            a = a.astype(np.int32)                           # (an empty list has no dtype of its own)
+    _check(np.issubdtype(a.dtype, np.integer), "candidates must hold integers (got dtype %s)" % (a.dtype,))
+    _check(a.ndim == 1, "candidates must be 1-D (got %d dimensions)" % a.ndim)
+    if a.size:
+        lo, hi = int(a.min()), int(a.max())
+        _check(1 <= lo and hi <= item_num, "candidates must be item ids in [1, item_num = %d] (got %d .. %d)" % (item_num, lo, hi))
+    if a.size > 1 and not bool(np.all(a[1:] > a[:-1])):      # (a list already in the launcher's form is not sorted again)
+        a = np.unique(a)
+    return np.ascontiguousarray(a[a <= N], dtype=np.int32)
+
+
 def rank_x3_supports(H):
     """Hidden sizes of k_lx3k (lx3f_supports of csrc/logits_x3.hip)."""
     return H % 2 == 0 and 8 <= H <= 160 and H % 8 in (0, 4, 6)
@@ -200,7 +220,8 @@ class _Infer:
         dtype: "f32" (k_topk_tile on the exact-f32 MFMA chain) or "x3" (bf16 matrix cores as a filter that keeps a superset of every
         row's top-k + exact recheck of the kept pairs: the same bytes, ties included); None: the engine's topk_dtype.  "x3" takes the
         f32 kernels for a hidden size outside k_lx3t's, k > ader_topk_x3_kmax() or a table of 2^31 bytes or more.  band: keys beyond
-        k a row's kept set may hold on the "x3" path before the row is handed to the f32 kernels (None: TOPK_X3_BAND)."""
+        k a row's kept set may hold on the "x3" path before the row is handed to the f32 kernels (None: TOPK_X3_BAND).
+        recommend_among: the same over a candidate item list."""
         dtype = _check_topk_dtype(self.topk_dtype if dtype is None else dtype)
         kmax = call("ader_topk_kmax")
         k = int(k)
@@ -231,6 +252,46 @@ class _Infer:
         part = self.buf("tk_part", (call("ader_topk_ranges", N, Bp) * Bp * k,), torch.int64)
         call("ader_topk_items", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
              ptr(seen), seen.shape[1] if seen is not None else 0, k, ptr(part), ptr(items), ptr(scores), self._stream())
+
+    def recommend_among(self, seq, k, candidates, max_item=None, exclude_seen=False, dtype=None):
+        """recommend restricted to a candidate item list: candidates is a 1-D integer array / tensor of item ids, shared by all rows
+        (candidate_ids: any order, duplicates allowed, every id in [1, item_num]).  A row's candidates are set(candidates) within
+        [1, max_item], minus its seen ids under exclude_seen; scores, order, ties and padding are recommend's, so items ==
+        stable_argsort(-L)[:, :k] + 1 for L = logits() with every other column at -inf, and with all of 1..max_item the bytes are
+        recommend's.  The list's table rows are gathered inside the kernel (ader_topk_items_cand, k_topk_cand): the work follows
+        len(candidates), not max_item.  dtype is checked as recommend checks it, but "x3" takes these f32 kernels too (the x3 filter
+        walks contiguous tiles only), next to recommend's own cases that fall to f32; last_topk_stats is left None.  (A method of its
+        own: recommend's parameter list is pinned by tests/test_topk_x3_host.py; Ader.recommend takes candidates=.)"""
+        _check_topk_dtype(self.topk_dtype if dtype is None else dtype)
+        kmax = call("ader_topk_kmax")
+        k = int(k)
+        N = self.item_num if max_item is None else int(max_item)
+        _check(1 <= k <= kmax, "recommend_among: k must be in 1..%d (got %d)" % (kmax, k))
+        _check(1 <= N <= self.item_num, "recommend_among: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        return self._recommend_cand(seq, k, N, exclude_seen, candidate_ids(candidates, N, self.item_num))
+
+    def _recommend_cand(self, seq, k, N, exclude_seen, cand):
+        """recommend over cand, candidate_ids' list: copied to the device once, ader_topk_items_cand per chunk of MAX_ROWS rows, one
+        device -> host copy."""
+        self._refresh_stream()
+        self.sync_table()
+        self.last_topk_stats = None
+        seq = self._seq_in(seq)
+        n, M = seq.shape[0], int(cand.shape[0])
+        cand_d = torch.from_numpy(cand).to(self.device) if M else None
+        res = torch.empty((2, n, k), dtype=torch.int32, device=self.device)      # items | score bits: one copy back
+        scores = res[1].view(torch.float32)
+        for s in range(0, n, self.MAX_ROWS):
+            e = min(n, s + self.MAX_ROWS)
+            rep = self.forward(seq[s:e], training=False)
+            B = e - s
+            Bp = (B + 63) // 64 * 64
+            part = self.buf("tkc_part", (call("ader_topk_ranges", M, Bp) * Bp * k,), torch.int64)
+            call("ader_topk_items_cand", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)), ptr(cand_d), M,
+                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, ptr(part), ptr(res[0, s:e]), ptr(scores[s:e]),
+                 ptr(self.status), self._stream())
+        host = res.cpu().numpy()
+        return host[0], host[1].view(np.float32)
 
     def _recommend_x3(self, seq, k, N, exclude_seen, band):
         """recommend on the bf16 matrix cores (ader_topk_items_x3): per 128-row-padded chunk k_lx3t keeps every item whose x3 logit is not

@@ -363,5 +363,6 @@ class _State:
         s = int(self.status.item())
         if s:
             self.status.zero_()
-            raise _lib.AderHipError("device status %d:%s%s" % (s, " item id outside [0, item_num] in input_seq" if s & 1 else "",
-                                                               " teacher row >= the TeacherRep's row count in ex_trow" if s & 2 else ""))
+            raise _lib.AderHipError("device status %d:%s%s%s" % (s, " item id outside [0, item_num] in input_seq" if s & 1 else "",
+                                                               " teacher row >= the TeacherRep's row count in ex_trow" if s & 2 else "",
+                                                               " candidate list not strictly ascending from 1" if s & 4 else ""))

@@ -75,8 +75,11 @@ class Ader:
     def rank_targets(self, seq, pos, max_item):
         return self.engine.rank_targets(seq, pos, max_item)
 
-    def recommend(self, seq, k, max_item=None, exclude_seen=False, dtype=None):
-        """The k best items per session, (items int32 [n,k], scores float32 [n,k]): Engine.recommend (dtype None: --topk_dtype)."""
+    def recommend(self, seq, k, max_item=None, exclude_seen=False, dtype=None, candidates=None):
+        """The k best items per session, (items int32 [n,k], scores float32 [n,k]): Engine.recommend (dtype None: --topk_dtype);
+        candidates: item ids the answer may come from (Engine.recommend_among), None: the whole catalog."""
+        if candidates is not None:
+            return self.engine.recommend_among(seq, k, candidates, max_item, exclude_seen, dtype=dtype)
         return self.engine.recommend(seq, k, max_item, exclude_seen, dtype=dtype)
 
     def predict(self, sess, seq, item_idx):

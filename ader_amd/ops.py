@@ -15,6 +15,8 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
                                                                          + exact-f32 recheck of the undecided pairs)
   ader::topk_items(rep, emb, seen, N, k)                       -> (items, scores)   the k best items per row, fused with the logits:
                                                                          order and bits of argsort(-logits) (ADER.py:92, 103)
+  ader::topk_items_cand(rep, emb, cand, seen, N, k)            -> (items, scores)   topk_items over the ids of one ascending candidate
+                                                                         list, its table rows gathered in the kernel: work follows the list
   ader::topk_items_x3(rep, emb, seen, N, k)                    -> (items, scores)   the same bytes; products on the bf16 matrix cores (x3
                                                                          filter keeping a superset of the top-k + exact-f32 recheck)
   ader::teacher_rows(trep, temb, ex_trow, Np)                  -> (rows, trow_local)   teacher logits of a step's exemplar rows from
@@ -221,6 +223,43 @@ def topk_items(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor
 
 @topk_items.register_fake
 def _(rep, emb, seen, N, k):
+    return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
+
+
+@torch.library.custom_op("ader::topk_items_cand", mutates_args=())
+def topk_items_cand(rep: torch.Tensor, emb: torch.Tensor, cand: torch.Tensor, seen: Optional[torch.Tensor], N: int,
+                    k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """topk_items over the items of cand only: cand int32 [M], strictly ascending 1-based ids shared by every row (ids above N are
+    ignored; M = 0 returns padding) -> (items int32 [B,k], scores float32 [B,k]) with topk_items' scores, order, ties and padding.  The
+    list's table rows are gathered in the kernel: work follows M, not N.  The op does not sort for the caller: a list that is not
+    strictly ascending, or holds an id < 1, raises (one synchronisation to read the status)."""
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(cand, "cand", torch.int32, 1)
+    B, H = rep.shape
+    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
+        raise RuntimeError("ader::topk_items_cand: bad shapes")
+    if not (1 <= k <= call("ader_topk_kmax")):
+        raise RuntimeError("ader::topk_items_cand: k must be in 1..%d (got %d)" % (call("ader_topk_kmax"), k))
+    if seen is not None:
+        _chk(seen, "seen", torch.int32, 2)
+        if seen.shape[0] != B or seen.shape[1] < 1:
+            raise RuntimeError("ader::topk_items_cand: seen must be [B, S] with S >= 1")
+    M = cand.shape[0]
+    Bp = (B + 63) // 64 * 64
+    dev = rep.device
+    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
+    ncol[:B] = N
+    part = torch.empty(call("ader_topk_ranges", M, Bp) * Bp * k, dtype=torch.int64, device=dev)
+    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    call("ader_topk_items_cand", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(cand) if M else None, M, ptr(seen),
+         seen.shape[1] if seen is not None else 0, k, ptr(part), ptr(items), ptr(scores), ptr(status), _st())
+    if int(status.item()):
+        raise RuntimeError("ader::topk_items_cand: cand must be strictly ascending item ids >= 1")
+    return items, scores
+
+
+@topk_items_cand.register_fake
+def _(rep, emb, cand, seen, N, k):
     return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
 
 

@@ -259,6 +259,16 @@ int ader_topk_kmax(void);
 int ader_topk_ranges(int N, int Bp);
 int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
                     int k, unsigned long long* part, int* items, float* scores, void* stream);
+/* ader_topk_items restricted to a candidate list (the head of tf.argsort, ADER.py:103, over a subset of the columns): cand [M] int32,
+ * strictly ascending 1-based item ids shared by every row; row b's candidates are the ids of cand in [1, min(N, ncol[b])] minus its seen
+ * ids.  Scores, order, ties and padding are ader_topk_items': the float32 of ader_logits_store, (score descending, id ascending), item
+ * 0 / -inf when fewer than k candidates exist.  The list's table rows are gathered inside the kernel: the work follows M, not N, and no
+ * table row beyond item N is read.  M = 0 is legal (cand may be NULL): every row is padding.  part: ader_topk_ranges(M,Bp)*Bp*k 64-bit
+ * keys of scratch.  status (NULL: none): bit 4 is OR-ed in when cand is not strictly ascending or holds an id < 1 -- the result is then
+ * unspecified, but nothing outside the table is read.  Enqueue only.  -2 as ader_topk_items, and when M < 0. */
+int ader_topk_items_cand(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* cand, int M,
+                         const int* seen, int seen_ld, int k, unsigned long long* part, int* items, float* scores, int* status,
+                         void* stream);
 /* ader_topk_items with the [B,N] products on the bf16 matrix cores: k_lx3t keeps, per row and item range, every item whose x3 logit is
  * not provably below the row's k-th best by delta[b] = 2^-13 |rep_b| emax[0] (a superset of the exact top-k, at most k + band keys), and
  * k_topk3_finish merges the ranges, re-evaluates the kept pairs through the exact-f32 MFMA chain and selects: for every row with

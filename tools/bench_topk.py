@@ -17,7 +17,16 @@ forward, launches, the copy back), medians.  The kernels of (A) are timed by tor
 against its two bounds: 2 n N H over the f32 MFMA peak (157.3 TFLOP/s, v_mfma_f32_16x16x4_f32) and N H 4 bytes per 64-row chunk over
 the HBM peak (8 TB/s) -- the larger one binds; k_lx3t against 3 x 2 n N H over the bf16 MFMA peak (2.5 PFLOP/s) and against k_topk_tile
 of the same run.  --check asserts that (C) equals (A) bytewise, that the items of (A) and (B) agree on every row whose k-th and (k+1)-th
-scores of (B) differ (torch.topk does not promise an order among ties) and that the scores agree bitwise there."""
+scores of (B) differ (torch.topk does not promise an order among ties) and that the scores agree bitwise there.
+
+--cand measures the candidate-list form instead (default --out profiles/topk_cand.txt), per catalog size and for evenly spread lists
+of M = N/100, N/10 and N ids:
+(D) Engine.recommend_among(seq, k, list, N): ader_topk_items_cand -- k_topk_cand (the list's table rows gathered into the logit
+    tiles) and k_topk_merge; the list is a sorted int32 host array, its copy to the device is inside the timed call;
+(A) Engine.recommend over the whole catalog, and (B') Engine.logits + masked_fill(-inf) outside the list + torch.topk, the composition
+    a caller writes without (D): the two yardsticks of the same run, alternating with (D) inside every repetition.
+k_topk_cand is set against the larger of 2 n M H over the f32 MFMA peak and M H 4 bytes per 64-row chunk over the HBM peak; --check
+asserts that the items and score bits of (D) equal those of (B') on every row whose k-th and (k+1)-th scores of (B') differ."""
 import argparse
 import os
 import statistics
@@ -60,6 +69,78 @@ def composed(eng, seq, N, k):
     return (i + 1).to(torch.int32).cpu().numpy(), v.cpu().numpy()
 
 
+def composed_cand(eng, seq, N, k, cand_d):
+    """(B'): dense logits, every column outside the list to -inf, torch.topk, the copy back.  k + 1 columns, as composed()."""
+    lg = eng.logits(seq, N)
+    out = torch.ones(N, dtype=torch.bool, device=lg.device)
+    out[cand_d.long() - 1] = False
+    lg.masked_fill_(out, float("-inf"))
+    v, i = torch.topk(lg, min(k + 1, N), dim=1)
+    return (i + 1).to(torch.int32).cpu().numpy(), v.cpu().numpy()
+
+
+def measure_cand(name, eng, seq, N, args):
+    n, k = seq.shape[0], args.k
+    seq_d = torch.from_numpy(np.ascontiguousarray(seq)).to(eng.device)
+    med = statistics.median
+    rows = min(n, eng.MAX_ROWS)
+    Bp = (rows + 63) // 64 * 64
+    nchunk = sum((min(n, s + eng.MAX_ROWS) - s + 63) // 64 for s in range(0, n, eng.MAX_ROWS))
+    say("== %s: %d rows, k = %d, H = %d; %d repetitions after %d warm-up, medians [min .. max]" % (name, n, k, H, args.reps, args.warmup))
+    ok = True
+    for M in sorted({max(N // 100, k + 1), max(N // 10, k + 1), N}):
+        cand = (np.arange(M, dtype=np.int64) * N // M + 1).astype(np.int32)          # evenly spread, ascending, distinct
+        cand_d = torch.from_numpy(cand).to(eng.device)
+        tA, tB, tD, b, d = [], [], [], None, None
+        for it in range(args.warmup + args.reps):
+            ta, _ = ev_time(lambda: eng.recommend(seq_d, k, N))
+            tb, b = ev_time(lambda: composed_cand(eng, seq_d, N, k, cand_d))
+            td, d = ev_time(lambda: eng.recommend_among(seq_d, k, cand, N))
+            if it >= args.warmup:
+                tA.append(ta)
+                tB.append(tb)
+                tD.append(td)
+        ranges = call("ader_topk_ranges", M, Bp)
+        say("  M = %d (N / %.0f), %d tiles over %d ranges" % (M, N / M, (M + 63) // 64, ranges))
+        say("    (D) recommend_among          %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (%d ranges x %d rows x k keys of 8 B)" %
+            (med(tD) * 1e3, min(tD) * 1e3, max(tD) * 1e3, n / med(tD), ranges * Bp * k * 8, ranges, Bp))
+        say("    (A) recommend, whole catalog %9.2f ms [%.2f .. %.2f]  %9.0f rows/s" % (med(tA) * 1e3, min(tA) * 1e3, max(tA) * 1e3, n / med(tA)))
+        say("    (B') logits + mask + topk    %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (the [n, N] float32 logits)" %
+            (med(tB) * 1e3, min(tB) * 1e3, max(tB) * 1e3, n / med(tB), n * ((N + 3) // 4 * 4) * 4))
+        say("    (D) / (A) whole call %.3f; (D) / (B') whole call %.3f  (< 1: the candidate walk is faster)" % (med(tD) / med(tA), med(tD) / med(tB)))
+        kt = kernel_times(lambda: eng.recommend_among(seq_d, k, cand, N))
+        tile = sum(t for nm, t in kt.items() if "k_topk_cand" in nm)
+        merge = sum(t for nm, t in kt.items() if "k_topk_merge" in nm)
+        b_mfma, b_hbm = 2.0 * n * M * H / PEAK_F32_MFMA, float(nchunk) * M * H * 4 / PEAK_HBM
+        bound, which = max((b_mfma, "MFMA"), (b_hbm, "HBM"))
+        if tile:
+            say("    k_topk_cand %.3f ms, k_topk_merge %.3f ms (torch.profiler, one call); bounds: 2nMH over the f32 MFMA peak %.3f ms, M H 4 B x "
+                "%d chunks over the HBM peak %.3f ms -> %s binds; k_topk_cand = %.1f x its bound" %
+                (tile * 1e3, merge * 1e3, b_mfma * 1e3, nchunk, b_hbm * 1e3, which, tile / bound))
+        else:
+            say("    torch.profiler reported no k_topk_cand rows (kernels seen: %d): kernel time NOT measured; bounds: MFMA %.3f ms, HBM %.3f ms"
+                % (len(kt), b_mfma * 1e3, b_hbm * 1e3))
+        if M == N:
+            kta = kernel_times(lambda: eng.recommend(seq_d, k, N))
+            ta_k = sum(t for nm, t in kta.items() if "k_topk_tile" in nm)
+            if ta_k and tile:
+                say("    at M = N: k_topk_cand %.3f ms against k_topk_tile %.3f ms of the same run = %.2f x (what the gather costs)" %
+                    (tile * 1e3, ta_k * 1e3, tile / ta_k))
+        if args.check:
+            ib, vb = b
+            decided = vb[:, k - 1] != vb[:, k] if vb.shape[1] > k else np.ones(n, dtype=bool)
+            same_items = np.array_equal(d[0][decided], ib[decided, :k])
+            same_bits = np.array_equal(np.ascontiguousarray(d[1][decided]).view(np.int32), np.ascontiguousarray(vb[decided, :k]).view(np.int32))
+            inside = bool(np.isin(d[0], cand).all())
+            ok &= bool(same_items and same_bits and inside)
+            say("    check: %d of %d rows have distinct k-th and (k+1)-th scores in (B'); on those, items equal: %s, scores bitwise equal: %s; "
+                "every item of (D) is in the list: %s" % (int(decided.sum()), n, same_items, same_bits, inside))
+        del cand_d
+    del eng
+    torch.cuda.empty_cache()
+    return ok
+
+
 def kernel_times(fn):
     """Device time per kernel name over one call of fn (torch.profiler); {} if the profiler reports no kernels."""
     from torch.profiler import ProfilerActivity, profile
@@ -85,7 +166,7 @@ def synthetic(N, args):
     for b in range(n):
         ln = int(rs.randint(1, T + 1))
         seq[b, T - ln:] = rs.randint(1, N + 1, size=ln)
-    return measure("N = %d" % N, eng, seq, N, args)
+    return (measure_cand if args.cand else measure)("N = %d" % N, eng, seq, N, args)
 
 
 def dataset(name, args):
@@ -196,11 +277,27 @@ def main():
     ap.add_argument("--catalogs", default="25750,43105,1000000")
     ap.add_argument("--datasets", default="", help="e.g. YOOCHOOSE,DIGINETICA: also the last test period of these, on a briefly trained model")
     ap.add_argument("--train_steps", type=int, default=200)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "topk.txt"))
+    ap.add_argument("--cand", action="store_true", help="measure the candidate-list form: legs (D), (A) and (B') at M = N/100, N/10 and N")
+    ap.add_argument("--out", default=None, help="default: profiles/topk.txt, or profiles/topk_cand.txt with --cand")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "topk_cand.txt" if args.cand else "topk.txt")
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_topk.py measures on the GPU: no device found")
     _out.append(open(args.out, "w"))
+    if args.cand:
+        if args.datasets:
+            raise SystemExit("--cand measures the synthetic catalogs only")
+        say("# tools/bench_topk.py --cand%s: (D) Engine.recommend_among (k_topk_cand + k_topk_merge) against (A) Engine.recommend over "
+            "the whole catalog and (B') Engine.logits + mask + torch.topk, same process, alternating; %s" %
+            (" --check" if args.check else "", torch.cuda.get_device_name(0)))
+        ok = True
+        for N in [int(x) for x in args.catalogs.split(",") if x]:
+            ok &= synthetic(N, args)
+        say("# (D) equal to (B') wherever the yardstick's order is decided: %s" % (ok if args.check else "not checked"))
+        if args.check and not ok:
+            raise SystemExit("top-K mismatch between (D) and (B')")
+        return
     say("# tools/bench_topk.py%s: (A) Engine.recommend (k_topk_tile + k_topk_merge) against (B) Engine.logits + torch.topk and (C) "
         "Engine.recommend(dtype=\"x3\") (k_lx3t + k_topk3_finish), same process, alternating; %s" %
         (" --check" if args.check else "", torch.cuda.get_device_name(0)))
