@@ -338,6 +338,69 @@ class _Infer:
             "max_err_over_delta": float(h_diag[:, 2].copy().view(np.float32).max()) if len(chunks) else 0.0}
         return h_items, h_scores
 
+    def recommend_wide(self, seq, k, max_item=None, exclude_seen=False, cap=None):
+        """recommend's contract for wide answers, 1 <= k <= ader_topk_wide_kmax() (= 1024): (items int32 [n,k], scores float32 [n,k]) as
+        numpy, items == stable_argsort(-logits)[:, :k] + 1 on the very float32 logits() returns, order (score descending, item id
+        ascending), exclude_seen and the item 0 / -inf padding as recommend's; for k <= 64 the bytes are recommend(dtype="f32")'s.
+        Slab and select (ader_topk_items_wide, csrc/topk_wide.hip): per row a list of cap keys in global memory (cap: a multiple of 64
+        in [k + 64, ader_topk_wide_cap()]; None: the largest, 4096), cut to its exact best k between slabs of the catalog walk; no
+        [n, max_item] logits are written.  Chunks of MAX_ROWS rows, one device -> host copy of items, scores, status and diag.  A row
+        whose list overflowed between two selects (scores trending upwards with the item id) is recomputed exactly, and slowly: dense
+        logits of those rows in groups under 256 MB, the seen columns at -inf, a stable descending sort, the same padding.
+        last_topk_stats: slabs (per chunk), rows, max_list (the largest list a select after slab 0 met), overflowed_rows,
+        fallback_rows."""
+        kmax, capmax = call("ader_topk_wide_kmax"), call("ader_topk_wide_cap")
+        k = int(k)
+        N = self.item_num if max_item is None else int(max_item)
+        cap = capmax if cap is None else int(cap)
+        _check(1 <= k <= kmax, "recommend_wide: k must be in 1..%d (got %d)" % (kmax, k))
+        _check(1 <= N <= self.item_num, "recommend_wide: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        _check(cap % 64 == 0 and k + 64 <= cap <= capmax,
+               "recommend_wide: cap must be a multiple of 64 in [k + 64 = %d, %d] (got %d)" % (k + 64, capmax, cap))
+        self._refresh_stream()
+        self.sync_table()
+        seq = self._seq_in(seq)
+        n, st, dev = seq.shape[0], self._stream(), self.device
+        chunks = [(s, min(n, s + self.MAX_ROWS)) for s in range(0, n, self.MAX_ROWS)]
+        res = torch.zeros(2 * n * k + n + 2 * len(chunks), dtype=torch.int32, device=dev)      # items | score bits | status | diag
+        items, scores = res[:n * k].view(n, k), res[n * k:2 * n * k].view(n, k).view(torch.float32)
+        status, diag = res[2 * n * k:2 * n * k + n], res[2 * n * k + n:]
+        rep_all = torch.empty((n, self.H), dtype=torch.float32, device=dev)
+        for c, (s, e) in enumerate(chunks):
+            B = e - s
+            Bp = (B + 63) // 64 * 64
+            rep_all[s:e] = self.forward(seq[s:e], training=False)
+            lst, thr = self.buf("tkw_list", (Bp * cap,), torch.int64), self.buf("tkw_thr", (Bp,), torch.int64)
+            cnt, stat = self.buf("tkw_cnt", (Bp,), torch.int32), self.buf("tkw_status", (Bp,), torch.int32)
+            call("ader_topk_items_wide", ptr(rep_all[s:e]), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
+                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, cap, ptr(lst), ptr(cnt), ptr(thr), ptr(stat),
+                 ptr(diag[2 * c:]), ptr(items[s:e]), ptr(scores[s:e]), st)
+            status[s:e] = stat[:B]
+        host = res.cpu().numpy()
+        h_items, h_scores = host[:n * k].reshape(n, k).copy(), host[n * k:2 * n * k].reshape(n, k).view(np.float32).copy()
+        h_status, h_diag = host[2 * n * k:2 * n * k + n], host[2 * n * k + n:].reshape(-1, 2)
+        over = np.nonzero(h_status)[0]
+        group = max(1, 64_000_000 // ((N + 3) // 4 * 4))          # rows whose dense logits stay under 256 MB
+        m = min(k, N)
+        for g in range(0, len(over), group):
+            rows = torch.from_numpy(over[g:g + group]).to(dev)
+            lg = self.logits_from_rep(rep_all[rows], N).contiguous()
+            if exclude_seen:
+                ids = seq[rows].long()
+                ids = torch.where(ids <= N, ids, torch.zeros_like(ids))              # column 0 = "no id" (and ids above N)
+                lg = torch.cat([torch.zeros((lg.shape[0], 1), dtype=lg.dtype, device=dev), lg], 1)
+                lg.scatter_(1, ids, float("-inf"))
+                lg = lg[:, 1:]
+            v, i = torch.sort(lg, dim=1, stable=True, descending=True)
+            v, i = v[:, :m].cpu().numpy(), (i[:, :m] + 1).to(torch.int32).cpu().numpy()
+            i[np.isneginf(v)] = 0
+            h_items[over[g:g + group]], h_scores[over[g:g + group]] = 0, -np.inf
+            h_items[over[g:g + group], :m], h_scores[over[g:g + group], :m] = i, v
+        self.last_topk_stats = {
+            "slabs": int(call("ader_topk_wide_slabs", N, k, cap, None, 0)), "rows": int(n),
+            "max_list": int(h_diag[:, 0].max()) if len(chunks) else 0, "overflowed_rows": int(len(over)), "fallback_rows": int(len(over))}
+        return h_items, h_scores
+
     def row_losses(self, seq, pos, max_item):
         """Per-row cross entropy -log softmax(logits)[label] in eval mode (the quantity the reference's `loss` exemplar selector
         means to rank by, util.py:463-495; its graph fetches the batch MEAN, see ExemplarGenerator.loss_selection) -> float32 [n]

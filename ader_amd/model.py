@@ -11,7 +11,9 @@ reads the feeds by token.  Next to the shim are the fast paths that take device 
 import numpy as np
 import torch
 
+from ._lib import call
 from .engine import Engine
+from .engine.infer import _check_topk_dtype
 
 
 class _Handle:
@@ -77,9 +79,14 @@ class Ader:
 
     def recommend(self, seq, k, max_item=None, exclude_seen=False, dtype=None, candidates=None):
         """The k best items per session, (items int32 [n,k], scores float32 [n,k]): Engine.recommend (dtype None: --topk_dtype);
-        candidates: item ids the answer may come from (Engine.recommend_among), None: the whole catalog."""
+        candidates: item ids the answer may come from (Engine.recommend_among), None: the whole catalog.  k above ader_topk_kmax()
+        (= 64), up to 1024, over the whole catalog: Engine.recommend_wide, on the f32 chain whatever dtype says (it is still checked);
+        with candidates such a k raises."""
         if candidates is not None:
             return self.engine.recommend_among(seq, k, candidates, max_item, exclude_seen, dtype=dtype)
+        if int(k) > call("ader_topk_kmax"):
+            _check_topk_dtype(self.engine.topk_dtype if dtype is None else dtype)
+            return self.engine.recommend_wide(seq, k, max_item, exclude_seen)
         return self.engine.recommend(seq, k, max_item, exclude_seen, dtype=dtype)
 
     def predict(self, sess, seq, item_idx):

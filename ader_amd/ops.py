@@ -19,6 +19,8 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
                                                                          list, its table rows gathered in the kernel: work follows the list
   ader::topk_items_x3(rep, emb, seen, N, k)                    -> (items, scores)   the same bytes; products on the bf16 matrix cores (x3
                                                                          filter keeping a superset of the top-k + exact-f32 recheck)
+  ader::topk_items_wide(rep, emb, seen, N, k, cap)             -> (items, scores, overflowed)   topk_items for k up to 1024 by slab
+                                                                         and select: per-row key lists in global memory, no [B, N] logits
   ader::teacher_rows(trep, temb, ex_trow, Np)                  -> (rows, trow_local)   teacher logits of a step's exemplar rows from
                                                                          stored representations + a table snapshot: the bits of
                                                                          ader_logits_store (util.py:433, ADER.py:134-135)
@@ -303,6 +305,45 @@ def topk_items_x3(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Ten
 @topk_items_x3.register_fake
 def _(rep, emb, seen, N, k):
     return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
+
+
+@torch.library.custom_op("ader::topk_items_wide", mutates_args=())
+def topk_items_wide(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor], N: int, k: int,
+                    cap: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """topk_items' contract for 1 <= k <= ader_topk_wide_kmax() (= 1024) through ader_topk_items_wide (slab and select): cap keys of
+    list per row in global memory, a multiple of 64 in [k + 64, ader_topk_wide_cap() = 4096] -> (items int32 [B,k], scores float32
+    [B,k], overflowed int32 [B]).  Rows with overflowed != 0 lost a key between two selects and are unspecified: the operator has no
+    fallback and does not synchronise (Engine.recommend_wide recomputes such rows)."""
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
+    B, H = rep.shape
+    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
+        raise RuntimeError("ader::topk_items_wide: bad shapes")
+    if not (1 <= k <= call("ader_topk_wide_kmax")):
+        raise RuntimeError("ader::topk_items_wide: k must be in 1..%d (got %d)" % (call("ader_topk_wide_kmax"), k))
+    if cap % 64 != 0 or not (k + 64 <= cap <= call("ader_topk_wide_cap")):
+        raise RuntimeError("ader::topk_items_wide: cap must be a multiple of 64 in [k + 64 = %d, %d] (got %d)" %
+                           (k + 64, call("ader_topk_wide_cap"), cap))
+    if seen is not None:
+        _chk(seen, "seen", torch.int32, 2)
+        if seen.shape[0] != B or seen.shape[1] < 1:
+            raise RuntimeError("ader::topk_items_wide: seen must be [B, S] with S >= 1")
+    Bp = (B + 63) // 64 * 64
+    dev = rep.device
+    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
+    ncol[:B] = N
+    lst, thr = torch.empty(Bp * cap, dtype=torch.int64, device=dev), torch.empty(Bp, dtype=torch.int64, device=dev)
+    cnt, status = torch.empty(Bp, dtype=torch.int32, device=dev), torch.empty(Bp, dtype=torch.int32, device=dev)
+    diag = torch.empty(2, dtype=torch.int32, device=dev)
+    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
+    call("ader_topk_items_wide", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen.shape[1] if seen is not None else 0, k, cap,
+         ptr(lst), ptr(cnt), ptr(thr), ptr(status), ptr(diag), ptr(items), ptr(scores), _st())
+    return items, scores, status[:B].clone()
+
+
+@topk_items_wide.register_fake
+def _(rep, emb, seen, N, k, cap):
+    B = rep.shape[0]
+    return rep.new_empty((B, k), dtype=torch.int32), rep.new_empty((B, k)), rep.new_empty((B,), dtype=torch.int32)
 
 
 @torch.library.custom_op("ader::teacher_rows", mutates_args=())

@@ -284,6 +284,24 @@ int ader_topk_x3_ranges(int N, int Bp);
 int ader_topk_items_x3(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* ncol, const int* seen,
                        int seen_ld, int k, int band, void* rep_hi, void* rep_lo, float* delta, const float* emax,
                        unsigned long long* part3, int* status, int* diag, int* items, float* scores, void* stream);
+/* ader_topk_items' contract for wide answers, 1 <= k <= ader_topk_wide_kmax() (= 1024), by slab and select (csrc/topk_wide.hip): no LDS
+ * buffer grows with k.  Per row a list of cap keys in global memory; the catalog is walked in slabs of 64-item tiles, k_topk_wide_tile
+ * appends every key that beats the row's threshold, k_topk_wide_select cuts the list to its exact best k after every slab and unpacks
+ * after the last.  cap: a multiple of 64, k + 64 <= cap <= ader_topk_wide_cap() (= 4096).  ader_topk_wide_slabs: the slab schedule, a
+ * pure host function (no GPU needed) -- slab 0 = items [0, min(N, cap)); with `seen` items done the next slab has
+ * max(64, 64 floor(seen min(1, (cap - k) / (32 k)) / 64)) items; returns the slab count, and begin (NULL: none) gets the boundaries
+ * begin[0] = 0 < ... < begin[slabs] = N, as many as fit into max ints; -2 for a bad N, k or cap.
+ * Scratch, all zeroed here: list Bp*cap 64-bit keys; cnt, row_status [Bp] ints; thr [Bp] 64-bit keys; diag [2] ints.  Afterwards
+ * row_status[b] != 0: the row's list overflowed between two selects, a key was dropped and the row's items / scores are unspecified
+ * (nothing outside the list is written); the caller recomputes such rows.  diag[0] = the largest list length a select after slab 0 met
+ * (above cap: that row overflowed), diag[1] = rows with row_status != 0.  Enqueue only.  -2 as ader_topk_items, and for k or cap out of
+ * range. */
+int ader_topk_wide_kmax(void);
+int ader_topk_wide_cap(void);
+int ader_topk_wide_slabs(int N, int k, int cap, int* begin, int max);
+int ader_topk_items_wide(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
+                         int k, int cap, unsigned long long* list, int* cnt, unsigned long long* thr, int* row_status, int* diag,
+                         int* items, float* scores, void* stream);
 
 /* Teacher logits of a step's exemplar rows, regenerated from stored teacher representations (util.py:433 computes them, ADER.py:134-135
  * consumes them as softmax(exemplar_logits)): trep [E,H] = the teacher's representations, temb = the item table as it stood when the

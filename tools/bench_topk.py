@@ -2,7 +2,7 @@
 """Top-K recommendation, fused (Engine.recommend) against the composition a caller had to write before it existed.
 
     python tools/bench_topk.py [--check] [--reps 3] [--warmup 1] [--rows 1024] [--k 20] [--datasets YOOCHOOSE,DIGINETICA]
-                               [--train_steps 200] [--out profiles/topk.txt]
+                               [--train_steps 200] [--cand | --wide] [--out profiles/topk.txt]
 
 (A) Engine.recommend(seq, k, N): ader_topk_items -- k_topk_tile (logit tiles + per-row selection in LDS) and k_topk_merge;
 (B) Engine.logits(seq, N) followed by torch.topk(.., k): dense [n, N] logits in HBM, then torch's selection.  (B) is the yardstick.
@@ -26,7 +26,17 @@ of M = N/100, N/10 and N ids:
 (A) Engine.recommend over the whole catalog, and (B') Engine.logits + masked_fill(-inf) outside the list + torch.topk, the composition
     a caller writes without (D): the two yardsticks of the same run, alternating with (D) inside every repetition.
 k_topk_cand is set against the larger of 2 n M H over the f32 MFMA peak and M H 4 bytes per 64-row chunk over the HBM peak; --check
-asserts that the items and score bits of (D) equal those of (B') on every row whose k-th and (k+1)-th scores of (B') differ."""
+asserts that the items and score bits of (D) equal those of (B') on every row whose k-th and (k+1)-th scores of (B') differ.
+
+--wide measures the wide form instead (default --out profiles/topk_wide.txt), per catalog size and dataset:
+(W) Engine.recommend_wide(seq, k, N) at k = 64, 256 and 1024: ader_topk_items_wide -- k_topk_wide_tile (logit tiles, every key that
+    beats the row's threshold appended to the row's list in global memory) and k_topk_wide_select (the list cut to its best k after
+    every slab), with its scratch bytes, slab count and last_topk_stats;
+(B) Engine.logits + torch.topk(k), the only route to such a k without (W), and (A) Engine.recommend at k = 64 against (W) at k = 64:
+    the yardsticks, alternating with (W) inside every repetition.
+The two wide kernels are timed by torch.profiler over one more call, beside k_topk_tile at the same N in the same run; --check asserts
+that the items and score bits of (W) equal those of (B) on every row whose k-th and (k+1)-th scores of (B) differ, and that (W) at
+k = 64 equals (A) bytewise."""
 import argparse
 import os
 import statistics
@@ -141,6 +151,72 @@ def measure_cand(name, eng, seq, N, args):
     return ok
 
 
+def measure_wide(name, eng, seq, N, args):
+    n = seq.shape[0]
+    seq_d = torch.from_numpy(np.ascontiguousarray(seq)).to(eng.device)
+    med = statistics.median
+    rows = min(n, eng.MAX_ROWS)
+    Bp = (rows + 63) // 64 * 64
+    cap = call("ader_topk_wide_cap")
+    say("== %s: %d rows, H = %d, cap = %d; %d repetitions after %d warm-up, medians [min .. max]" % (name, n, H, cap, args.reps, args.warmup))
+    kta = kernel_times(lambda: eng.recommend(seq_d, 64, N, dtype="f32"))
+    tile_a = sum(t for nm, t in kta.items() if "k_topk_tile" in nm)
+    ok = True
+    for k in (64, 256, 1024):
+        tW, tB, tA, w, b, a = [], [], [], None, None, None
+        for it in range(args.warmup + args.reps):
+            tw, w = ev_time(lambda: eng.recommend_wide(seq_d, k, N))
+            st = dict(eng.last_topk_stats)
+            tb, b = ev_time(lambda: composed(eng, seq_d, N, k))
+            if k == 64:
+                ta, a = ev_time(lambda: eng.recommend(seq_d, k, N, dtype="f32"))
+            if it >= args.warmup:
+                tW.append(tw)
+                tB.append(tb)
+                if k == 64:
+                    tA.append(ta)
+        say("  k = %d: %d slabs" % (k, st["slabs"]))
+        say("    (W) recommend_wide          %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (%d rows x cap keys of 8 B + 16 B per row)" %
+            (med(tW) * 1e3, min(tW) * 1e3, max(tW) * 1e3, n / med(tW), Bp * cap * 8 + Bp * 16, Bp))
+        say("    (B) logits + torch.topk     %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (the [n, N] float32 logits)" %
+            (med(tB) * 1e3, min(tB) * 1e3, max(tB) * 1e3, n / med(tB), n * ((N + 3) // 4 * 4) * 4))
+        say("    (W) / (B) whole call %.3f  (< 1: the wide path is faster)" % (med(tW) / med(tB)))
+        if k == 64:
+            say("    (A) recommend, k = 64       %9.2f ms [%.2f .. %.2f]  %9.0f rows/s; (W) / (A) whole call %.3f" %
+                (med(tA) * 1e3, min(tA) * 1e3, max(tA) * 1e3, n / med(tA), med(tW) / med(tA)))
+        say("    (W) last_topk_stats %r%s" % (st, "  ** max_list above cap / 2 **" if st["max_list"] > cap // 2 else ""))
+        if st["overflowed_rows"]:
+            say("    ** %d rows overflowed at the default cap and were recomputed **" % st["overflowed_rows"])
+        kt = kernel_times(lambda: eng.recommend_wide(seq_d, k, N))
+        tile = sum(t for nm, t in kt.items() if "k_topk_wide_tile" in nm)
+        sel = sum(t for nm, t in kt.items() if "k_topk_wide_select" in nm)
+        if tile and tile_a:
+            say("    k_topk_wide_tile %.3f ms, k_topk_wide_select %.3f ms over %d slabs (torch.profiler, one call); k_topk_tile (k = 64) at the "
+                "same N in the same run %.3f ms: wide tile / k_topk_tile = %.2f x, wide tile + select / k_topk_tile = %.2f x" %
+                (tile * 1e3, sel * 1e3, st["slabs"], tile_a * 1e3, tile / tile_a, (tile + sel) / tile_a))
+        else:
+            say("    torch.profiler reported no k_topk_wide_tile / k_topk_tile rows (kernels seen: %d, %d): kernel time NOT measured" %
+                (len(kt), len(kta)))
+        if args.check:
+            ib, vb = b
+            kk = min(k, vb.shape[1])
+            decided = vb[:, k - 1] != vb[:, k] if vb.shape[1] > k else np.ones(n, dtype=bool)
+            same_items = np.array_equal(w[0][decided, :kk], ib[decided, :kk])
+            same_bits = np.array_equal(np.ascontiguousarray(w[1][decided, :kk]).view(np.int32),
+                                       np.ascontiguousarray(vb[decided, :kk]).view(np.int32))
+            ok &= bool(same_items and same_bits)
+            say("    check: %d of %d rows have distinct k-th and (k+1)-th scores in (B); on those, items equal: %s, scores bitwise equal: %s" %
+                (int(decided.sum()), n, same_items, same_bits))
+            if k == 64:
+                same_a = (np.array_equal(w[0], a[0]) and
+                          np.array_equal(np.ascontiguousarray(w[1]).view(np.int32), np.ascontiguousarray(a[1]).view(np.int32)))
+                ok &= bool(same_a)
+                say("    check: (W) at k = 64 equals (A) bytewise: %s" % same_a)
+    del eng
+    torch.cuda.empty_cache()
+    return ok
+
+
 def kernel_times(fn):
     """Device time per kernel name over one call of fn (torch.profiler); {} if the profiler reports no kernels."""
     from torch.profiler import ProfilerActivity, profile
@@ -166,7 +242,7 @@ def synthetic(N, args):
     for b in range(n):
         ln = int(rs.randint(1, T + 1))
         seq[b, T - ln:] = rs.randint(1, N + 1, size=ln)
-    return (measure_cand if args.cand else measure)("N = %d" % N, eng, seq, N, args)
+    return (measure_cand if args.cand else measure_wide if args.wide else measure)("N = %d" % N, eng, seq, N, args)
 
 
 def dataset(name, args):
@@ -193,7 +269,8 @@ def dataset(name, args):
                     eng.train_step(seq, pos, N, 5e-4, rate=0.3)
             torch.cuda.synchronize()
     seq, _ = evaluator_rows(test_sess, N, 1024)
-    return measure("%s, test period %d, N = %d, %d training steps" % (name, periods, N, args.train_steps), eng, seq[:args.rows], N, args)
+    return (measure_wide if args.wide else measure)("%s, test period %d, N = %d, %d training steps" % (name, periods, N, args.train_steps), eng,
+                                                    seq[:args.rows], N, args)
 
 
 def measure(name, eng, seq, N, args):
@@ -278,10 +355,14 @@ def main():
     ap.add_argument("--datasets", default="", help="e.g. YOOCHOOSE,DIGINETICA: also the last test period of these, on a briefly trained model")
     ap.add_argument("--train_steps", type=int, default=200)
     ap.add_argument("--cand", action="store_true", help="measure the candidate-list form: legs (D), (A) and (B') at M = N/100, N/10 and N")
-    ap.add_argument("--out", default=None, help="default: profiles/topk.txt, or profiles/topk_cand.txt with --cand")
+    ap.add_argument("--wide", action="store_true", help="measure the wide form: legs (W) at k = 64, 256, 1024, (B) and (A)")
+    ap.add_argument("--out", default=None, help="default: profiles/topk.txt, profiles/topk_cand.txt with --cand, profiles/topk_wide.txt with --wide")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "topk_cand.txt" if args.cand else "topk.txt")
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "topk_cand.txt" if args.cand else "topk_wide.txt" if args.wide else "topk.txt")
+    if args.cand and args.wide:
+        raise SystemExit("--cand and --wide are two measurements: run them one at a time")
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_topk.py measures on the GPU: no device found")
     _out.append(open(args.out, "w"))
@@ -297,6 +378,20 @@ def main():
         say("# (D) equal to (B') wherever the yardstick's order is decided: %s" % (ok if args.check else "not checked"))
         if args.check and not ok:
             raise SystemExit("top-K mismatch between (D) and (B')")
+        return
+    if args.wide:
+        say("# tools/bench_topk.py --wide%s: (W) Engine.recommend_wide (k_topk_wide_tile + k_topk_wide_select) at k = 64, 256, 1024 against "
+            "(B) Engine.logits + torch.topk and (A) Engine.recommend at k = 64, same process, alternating; %s" %
+            (" --check" if args.check else "", torch.cuda.get_device_name(0)))
+        ok = True
+        for N in [int(x) for x in args.catalogs.split(",") if x]:
+            ok &= synthetic(N, args)
+        for name in [d for d in args.datasets.split(",") if d]:
+            ok &= dataset(name, args)
+        say("# (W) equal to (B) wherever the yardstick's order is decided, (W) at k = 64 equal to (A) bytewise: %s" %
+            (ok if args.check else "not checked"))
+        if args.check and not ok:
+            raise SystemExit("top-K mismatch between (W) and its yardsticks")
         return
     say("# tools/bench_topk.py%s: (A) Engine.recommend (k_topk_tile + k_topk_merge) against (B) Engine.logits + torch.topk and (C) "
         "Engine.recommend(dtype=\"x3\") (k_lx3t + k_topk3_finish), same process, alternating; %s" %
