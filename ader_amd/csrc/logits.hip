@@ -9,24 +9,20 @@
 //   k_logits_tile<LSE>   per-row online (max, sum-exp, target.logit) partials      -> k_lse_loss
 //   k_logits_tile<RANK>  per-row count of items ranked before the target           (Evaluator, util.py:323-325)
 //   k_logits_tile<STORE> dense logits (teacher logits of selected exemplars, util.py:433; model.logits fetch)
-//   k_topk_tile/_merge   per-row best k items by (logit descending, id ascending), the STORE bits       (Engine.recommend)
-//   k_topk_cand/_merge   the same over the items of a candidate id list, its table rows gathered: work follows the list  (Engine.recommend_among)
+//   k_target_logit / k_pair_logit_rank   the RANK bits of single (row, item) pairs: a row's target, the x3 rank filter's recheck
 //   k_teacher_rows      the STORE bits of a step's exemplar rows from stored teacher representations  (TeacherRep, util.py:433)
 //   k_logits_bwd_drep    dRep[b,:] = sum_n dlogit[b,n] E[n,:]   (b-chunk x item-range workgroups, slabs)
 //   k_logits_bwd_de      dE[n,:]   = sum_b dlogit[b,n] rep[b,:] (item-tile workgroups; rows written once, no atomics)
 // with dlogit[b,n] = w_b * (softmax_b[n] - target_b[n]) for n < ncol_b, else 0.
 // Row descriptors (RowInfo): label, ncol (N for one-hot rows, Np for distilled rows), weight
 // (1/B_train or lambda/B_ex, global counts under data parallelism), teacher row + teacher log-sum-exp.
-#include "common.h"
-#include "topk_key.h"
+// The operand layout, stage_tile and the tile stream are logit_tile.h's; the exact top-K family that selects from the STORE bits
+// (Engine.recommend, recommend_among, recommend_wide) is topk.hip: a translation unit of its own, because one more caller of stage_tile
+// or mma_tile<2> in this file changes the code the compiler emits for k_logits_bwd_de / k_logits_bwd_drep (tools/isa_digest.py).
+#include "logit_tile.h"
 #include "../../include/ader_hip.h"
 
-#define HP 160
-#define LDE 162         // (row, k) operand reads conflict-free
 #define LDD 68          // 64x64 dlogit tile
-#define TI 64           // items per sub-tile
-#define TB 64           // batch rows per chunk
-#define MAXB 1024       // max (padded) batch rows per launch
 
 enum { MODE_LSE = 0, MODE_RANK = 1, MODE_STORE = 2 };
 
@@ -59,14 +55,6 @@ struct LogitArgs {
     float* slab;           // drep slabs [ranges][Bp][HP]
     int ranges;
 };
-
-__device__ __forceinline__ void stage_tile(float* dst, const float* src, int row0, int nrows, int H, int tid, int nthreads) {
-    // dst[r][c] = src[(row0+r)*H + c] for row0+r < nrows, c < H; zeros elsewhere.  [64][LDE]
-    for (int i = tid; i < 64 * LDE; i += nthreads) {
-        const int r = i / LDE, c = i - r * LDE;
-        dst[i] = (row0 + r < nrows && c < H) ? src[(size_t)(row0 + r) * H + c] : 0.0f;
-    }
-}
 
 __device__ __forceinline__ void merge_ml(float& m, float& l, float m2, float l2) {
     const float mn = fmaxf(m, m2);
@@ -443,188 +431,14 @@ __global__ __launch_bounds__(256) void k_pair_logit_rank(LogitArgs a, const floa
         }
 }
 
-// ============================================================================================= exact top-K items
-// ader_topk_items: for every row the k best items of 1..N by (score descending, item id ascending) -- the order of ader_rank_targets and
-// of tf.argsort (ADER.py:103) -- where the score of (b, n) is the float32 of k_logits_tile<MODE_STORE>: the same stage_tile layout, the
-// same mma_tile<2> call, the same ksteps.  A candidate is one 64-bit key: order-preserving float bits above, the complemented 1-based
-// item id below, so ONE unsigned compare is the total order and no two candidates of a row compare equal.  Key 0 = "no candidate".
-// (The MFMA chain starts from +0 and rounds to nearest, so it never yields -0; topk_key still folds -0 onto +0, as == does.)
-// The best k of a set under a total order do not depend on the order the set was visited in: that is the whole determinism argument --
-// LDS atomics only hand out buffer slots, the kept SET is the same however they land, and every output is derived from sorted keys.
-#define TOPK_KMAX 64
-
-struct TopkArgs {
-    const float* rep;      // [B,H]
-    const float* emb1;     // table row 1 (item 1) : [N,H]
-    int B, Bp, H, N;
-    const int* ncol;       // [Bp] N for real rows, 0 for padding rows
-    const int* seen;       // [B, seen_ld] 1-based ids never to be returned (0 = none), or NULL
-    int seen_ld, k, ranges;
-    u64* part;             // [ranges][Bp][k]
-    int* items;            // [B,k]
-    float* scores;         // [B,k]
-};
-
-// (topk_key / topk_score / topk_item: topk_key.h, shared with the x3 filter of logits_x3.hip)
-
-// Workgroup = (64-row chunk, contiguous range of 64-item tiles), block -> (range, chunk) as in k_logits_bwd_drep.  The chunk's rep rows
-// are staged once; the range's table tiles stream through E_l, the next tile's loads in flight (registers) under the current tile's MFMAs.
-// Per batch row a candidate buffer of k + 64 keys in LDS:
-//   filter   a lane proposes (row, item) only if the item is a column of the row, is not marked seen, and its key beats thr[row], the
-//            row's k-th best key at its last compaction (0 before the first);
-//   append   into buf[row][cnt[row]++] (LDS atomic: hands out the slot, nothing else);
-//   compact  a row holding more than k keys is cut to its best k, sorted, and thr[row] <- its k-th.  Workgroup-uniform, decided by one
-//            __syncthreads_or per tile.
-// INVARIANT: every row enters a tile with cnt <= k, a 64-item tile proposes at most 64 keys per row, and every row with cnt > k is
-// compacted before the next tile: cnt <= k + 64 = the buffer's size, always.
-// Seen ids: per tile, 8 threads per row fold the row's ids that fall into the tile into a 64-bit mask (no over-selection, no second pass).
-#define TOPK_STAGE_REGS ((64 * LDE + 511) / 512)
-__global__ __launch_bounds__(512) void k_topk_tile(TopkArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* E_l = smem;                                       // [TI][LDE]
-    float* R_l = E_l + TI * LDE;                             // [TB][LDE]
-    u64* buf = (u64*)(R_l + TB * LDE);                       // [TB][k + 64]
-    const int k = a.k, ldb = k + TI;
-    u64* thr = buf + TB * ldb;                               // [TB]
-    u64* msk = thr + TB;                                     // [TB] bit i: item tile0 + i is in the row's seen list
-    int* cnt = (int*)(msk + TB);                             // [TB]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mw = wave & 3, nw = wave >> 2;
-    const int H = a.H, ksteps = (H + 3) >> 2;
-    const int r16 = lane & 15, q = lane >> 4;
-    const int nchunk = a.Bp / TB;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk), bc = slot % nchunk;
-    if (range >= a.ranges) return;
-    const int nsub_total = (a.N + TI - 1) / TI;
-    const int s_begin = (int)((long)range * nsub_total / a.ranges), s_end = (int)((long)(range + 1) * nsub_total / a.ranges);
-    // stage_tile's layout, written out: one more caller of stage_tile changes the code the compiler emits for the existing ones
-    // (tools/isa_digest.py), and their instruction streams are pinned
-    for (int i = tid; i < 64 * LDE; i += 512) {
-        const int r = i / LDE, c = i - r * LDE;
-        R_l[i] = (bc * TB + r < a.B && c < H) ? a.rep[(size_t)(bc * TB + r) * H + c] : 0.0f;
-    }
-    if (tid < TB) { thr[tid] = 0; msk[tid] = 0; cnt[tid] = 0; }
-    int nc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) nc[j] = a.ncol[bc * TB + nw * 32 + j * 16 + r16];
-    float pre[TOPK_STAGE_REGS];                              // the next tile, in stage_tile's element order
-    auto load_tile = [&](int tile0) {
-#pragma unroll
-        for (int n = 0; n < TOPK_STAGE_REGS; ++n) {
-            const int i = tid + n * 512, r = i / LDE, c = i - r * LDE;
-            pre[n] = (i < 64 * LDE && tile0 + r < a.N && c < H) ? a.emb1[(size_t)(tile0 + r) * H + c] : 0.0f;
-        }
-    };
-    if (s_begin < s_end) load_tile(s_begin * TI);
-    for (int s = s_begin; s < s_end; ++s) {
-        const int tile0 = s * TI;
-        __syncthreads();                                     // the previous tile's MFMA reads, filter and compaction are done
-#pragma unroll
-        for (int n = 0; n < TOPK_STAGE_REGS; ++n)
-            if (tid + n * 512 < 64 * LDE) E_l[tid + n * 512] = pre[n];
-        if (a.seen) {                                        // thread (row = tid / 8, part = tid % 8): the 8 lanes of a row are neighbours
-            const int row = tid >> 3, b = bc * TB + row;
-            u64 m = 0;
-            if (b < a.B)
-                for (int t = tid & 7; t < a.seen_ld; t += 8) {
-                    const unsigned d = (unsigned)(a.seen[(size_t)b * a.seen_ld + t] - 1 - tile0);      // id 0 -> d wraps: never < 64
-                    if (d < 64u) m |= 1ull << d;
-                }
-            m |= __shfl_xor(m, 1, 64); m |= __shfl_xor(m, 2, 64); m |= __shfl_xor(m, 4, 64);
-            if ((tid & 7) == 0) msk[row] = m;
-        }
-        __syncthreads();
-        if (s + 1 < s_end) load_tile(tile0 + TI);
-        f32x4 acc[2];
-        acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        mma_tile<2>(E_l + mw * 16 * LDE, LDE, 1, R_l + nw * 32 * LDE, 1, LDE, ksteps, acc, lane);
-        const int il0 = mw * 16 + q * 4, item0 = tile0 + il0;      // this lane's 4 consecutive items
-        int over = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int bl = nw * 32 + j * 16 + r16;                  // batch row within the chunk
-            const u64 t = thr[bl];
-            const unsigned sm = (unsigned)(msk[bl] >> il0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int it = item0 + r;
-                const u64 key = topk_key(acc[j][r], it + 1);
-                if (it < nc[j] && !((sm >> r) & 1u) && key > t) {
-                    const int p = atomicAdd(cnt + bl, 1);           // p < k + 64 (the invariant above)
-                    buf[bl * ldb + p] = key;
-                    over |= (p >= k);
-                }
-            }
-        }
-        if (__syncthreads_or(over)) {                               // some row holds more than k keys: wave w compacts rows 8w .. 8w+7
-            for (int rr = 0; rr < TB / 8; ++rr) {
-                const int row = wave * (TB / 8) + rr, n = cnt[row];
-                if (n <= k) continue;                               // (wave-uniform)
-                u64* bp = buf + row * ldb;
-                const u64 e0 = lane < n ? bp[lane] : 0, e1 = lane + 64 < n ? bp[lane + 64] : 0;      // n <= k + 64 <= 128
-                int r0 = 0, r1 = 0;                                 // keys of a row are distinct: rank = number of larger keys
-                for (int i = 0; i < n; ++i) { const u64 x = bp[i]; r0 += x > e0; r1 += x > e1; }
-                // in place: a rank depends on every read of the loop, and one wave's LDS operations are performed in order
-                if (lane < n && r0 < k) { bp[r0] = e0; if (r0 == k - 1) thr[row] = e0; }
-                if (lane + 64 < n && r1 < k) { bp[r1] = e1; if (r1 == k - 1) thr[row] = e1; }
-                if (lane == 0) cnt[row] = k;
-            }
-        }
-    }
-    __syncthreads();
-    u64* o = a.part + ((size_t)range * a.Bp + bc * TB) * k;
-    for (int i = tid; i < TB * k; i += 512) {
-        const int row = i / k, j = i - row * k;
-        o[i] = j < cnt[row] ? buf[row * ldb + j] : 0;               // (an empty range writes zeros: no candidate)
-    }
-}
-
-// One workgroup per real row: the best k of the row's ranges * k partial keys by the same filter / append / compact over batches of 256
-// keys (buffer k + 256), a final compaction that sorts, then unpack.  Key 0 (an empty slot of a range) never beats the threshold.
-__global__ __launch_bounds__(256) void k_topk_merge(TopkArgs a) {
-    __shared__ u64 mb[TOPK_KMAX + 256];
-    __shared__ u64 mthr;
-    __shared__ int mcnt;
-    const int tid = threadIdx.x, b = blockIdx.x, k = a.k, total = a.ranges * k;
-    if (tid == 0) { mthr = 0; mcnt = 0; }
-    __syncthreads();
-    for (int base = 0; base <= total; base += 256) {                // the pass at base >= total appends nothing: the final, sorting compaction
-        const int i = base + tid;
-        const bool last = base + 256 > total;
-        u64 key = 0;
-        if (i < total) { const int rg = i / k; key = a.part[((size_t)rg * a.Bp + b) * k + (i - rg * k)]; }
-        int over = 0;
-        if (key > mthr) { const int p = atomicAdd(&mcnt, 1); mb[p] = key; over = (p >= k); }
-        if (__syncthreads_or(over | last)) {
-            const int n = mcnt;                                     // n <= k + 256 <= 320: at most two keys per thread
-            const u64 e0 = tid < n ? mb[tid] : 0, e1 = tid + 256 < n ? mb[tid + 256] : 0;
-            int r0 = 0, r1 = 0;
-            for (int j = 0; j < n; ++j) { const u64 x = mb[j]; r0 += x > e0; r1 += x > e1; }
-            __syncthreads();
-            if (tid < n && r0 < k) { mb[r0] = e0; if (r0 == k - 1) mthr = e0; }
-            if (tid + 256 < n && r1 < k) { mb[r1] = e1; if (r1 == k - 1) mthr = e1; }
-            if (tid == 0) mcnt = min(n, k);
-            __syncthreads();
-        }
-        if (last) break;
-    }
-    const int n = mcnt;
-    for (int j = tid; j < k; j += 256) {
-        const bool real = j < n;
-        a.items[(size_t)b * k + j] = real ? topk_item(mb[j]) : 0;
-        a.scores[(size_t)b * k + j] = real ? topk_score(mb[j]) : -INFINITY;
-    }
-}
-
 // ============================================================================================= teacher rows from stored representations
 // ader_teacher_rows: the teacher logits of one step's exemplar rows (util.py:433, consumed by ADER.py:134-135), regenerated from the
 // teacher's representations trep [E,H] and the item table as it stood when the teacher was taken, instead of being kept as an [E, Np]
 // tensor.  rows[e, n] is the float32 k_logits_tile<MODE_STORE> writes for representation trep[ex_trow[e]] against item n + 1: the same
 // [64][LDE] operand layout, the same mma_tile<2> call, the same ksteps -- and a (row, item) result of that chain does not depend on
-// which other rows or items share the tile, so the bits are the stored teacher's.  k_topk_tile's shape: workgroup = (64-row chunk,
-// contiguous range of 64-item tiles); the chunk's representations are gathered by ex_trow into LDS once, the range's table tiles
-// stream through E_l with the next tile's loads in flight (registers) under the current tile's MFMAs.  Every (row, item) is written by
+// which other rows or items share the tile, so the bits are the stored teacher's.  logit_tile.h's walk and tile stream: workgroup =
+// (64-row chunk, contiguous range of 64-item tiles); the chunk's representations are gathered by ex_trow into LDS once, the range's
+// table tiles stream through E_l with the next tile's loads in flight (registers) under the current tile's MFMAs.  Every (row, item) is written by
 // exactly one lane: no atomics on floats, no reduction across workgroups.  Padding rows (ex_trow < 0, e >= n_ex) are written as 0.0f
 // whatever the table holds; a teacher row >= E is never read: the row is written as padding and the status word flagged.
 struct TeachArgs {
@@ -647,12 +461,8 @@ __global__ __launch_bounds__(512) void k_teacher_rows(TeachArgs a) {
     const int mw = wave & 3, nw = wave >> 2;
     const int H = a.H, ksteps = (H + 3) >> 2;
     const int r16 = lane & 15, q = lane >> 4;
-    const int nchunk = a.Bk / TB;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk), bc = slot % nchunk;
-    if (range >= a.ranges) return;
-    const int nsub_total = (a.N + TI - 1) / TI;
-    const int s_begin = (int)((long)range * nsub_total / a.ranges), s_end = (int)((long)(range + 1) * nsub_total / a.ranges);
+    int range, bc, s_begin, s_end;
+    if (!tile_walk(a.Bk / TB, a.ranges, (a.N + TI - 1) / TI, range, bc, s_begin, s_end)) return;
     if (tid < TB) {
         const int e = bc * TB + tid;
         int t = (e < a.n_ex) ? a.ex_trow[e] : -1;
@@ -671,23 +481,14 @@ __global__ __launch_bounds__(512) void k_teacher_rows(TeachArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) real[j] = tr_l[nw * 32 + j * 16 + r16] >= 0;
     const bool vec_ok = (((uintptr_t)a.rows) & 15) == 0;               // (ldr % 4 == 0 and item0 % 4 == 0: a lane's 4 items are one 16-byte piece)
-    float pre[TOPK_STAGE_REGS];                                        // the next tile, in stage_tile's element order
-    auto load_tile = [&](int tile0) {
-#pragma unroll
-        for (int n = 0; n < TOPK_STAGE_REGS; ++n) {
-            const int i = tid + n * 512, r = i / LDE, c = i - r * LDE;
-            pre[n] = (i < 64 * LDE && tile0 + r < a.N && c < H) ? a.emb1[(size_t)(tile0 + r) * H + c] : 0.0f;
-        }
-    };
-    if (s_begin < s_end) load_tile(s_begin * TI);
+    float pre[TILE_STAGE_REGS];
+    if (s_begin < s_end) tile_load(pre, a.emb1, s_begin * TI, a.N, H, tid);
     for (int s = s_begin; s < s_end; ++s) {
         const int tile0 = s * TI;
         __syncthreads();                                               // the previous tile's MFMA reads are done (first pass: R_l is staged)
-#pragma unroll
-        for (int n = 0; n < TOPK_STAGE_REGS; ++n)
-            if (tid + n * 512 < 64 * LDE) E_l[tid + n * 512] = pre[n];
+        tile_store(E_l, pre, tid);
         __syncthreads();
-        if (s + 1 < s_end) load_tile(tile0 + TI);
+        if (s + 1 < s_end) tile_load(pre, a.emb1, tile0 + TI, a.N, H, tid);
         f32x4 acc[2];
         acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
         mma_tile<2>(E_l + mw * 16 * LDE, LDE, 1, R_l + nw * 32 * LDE, 1, LDE, ksteps, acc, lane);
@@ -705,185 +506,6 @@ __global__ __launch_bounds__(512) void k_teacher_rows(TeachArgs a) {
                     if (item0 + r < a.N) o[r] = v[r];
             }
         }
-    }
-}
-
-// ============================================================================================= exact top-K items of a candidate list
-// ader_topk_items_cand: ader_topk_items' contract over the items of one strictly ascending id list cand[M] shared by every row, with
-// work proportional to M.  k_topk_tile's shape, operand layout, mma_tile<2> call, filter / append / compact and row buffers; tile s is
-// positions [64s, 64s + 64) of the list and its 64 table rows are GATHERED into E_l, in stage_tile's element order (consecutive
-// threads cover consecutive floats of one table row).  A (row, item) result of the chain does not depend on which items share its tile
-// (k_teacher_rows relies on the same), so a score is k_logits_tile<MODE_STORE>'s float32, and the key carries the true item id: the
-// order, ties included, is ader_topk_items'.  Pipeline per tile s: its rows are written to E_l from registers, the rows of tile s + 1
-// are loaded into registers under the MFMAs, and the ids of tile s + 2 are fetched by wave 0 (the row addresses depend on the ids, so
-// the ids run one tile ahead of the rows).  The ids of a tile and the mask of its live positions sit in LDS, two slots: the loads of
-// tile s + 1 read one slot while the keys and the seen mask of tile s are built from the other.
-// Position p is live iff p < M, cand[p] >= 1, cand[p] > cand[p-1] and cand[p] <= N; for a row it also needs cand[p] <= ncol[row] and a
-// clear seen bit.  A dead position gets a zero operand row and is never proposed: no id outside [1, N] forms an address.  cand[p] < 1
-// or cand[p] <= cand[p-1] flags ADER_ST_BAD_CAND: every list that is not strictly ascending is reported, and its result is unspecified
-// (two equal keys in a row would break the rank-by-count compaction) but every access stays in bounds -- cnt <= k + 64 holds for any
-// list, since a 64-position tile proposes at most 64 keys per row.
-// Seen ids: the tile's ids are ascending (positions past M hold INT_MAX), so the 8 threads of a row look each seen id up by binary
-// search and set the bit of the position it sits at.
-struct TopkCandArgs {
-    TopkArgs t;            // N: the last item of the table that may be read; ranges, part: over the M positions
-    const int* cand;       // [M] strictly ascending 1-based item ids
-    int M;
-    int* status;           // status word or NULL
-};
-
-__global__ __launch_bounds__(512) void k_topk_cand(TopkCandArgs ca) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const TopkArgs& a = ca.t;
-    float* E_l = smem;                                       // [TI][LDE]
-    float* R_l = E_l + TI * LDE;                             // [TB][LDE]
-    u64* buf = (u64*)(R_l + TB * LDE);                       // [TB][k + 64]
-    const int k = a.k, ldb = k + TI;
-    u64* thr = buf + TB * ldb;                               // [TB]
-    u64* msk = thr + TB;                                     // [TB] bit i: the id at position i of the tile is in the row's seen list
-    u64* lm = msk + TB;                                      // [2] bit i: position i of the slot's tile is live
-    int* cnt = (int*)(lm + 2);                               // [TB]
-    int* idl = cnt + TB;                                     // [2][TI] the slot's ids
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mw = wave & 3, nw = wave >> 2;
-    const int H = a.H, ksteps = (H + 3) >> 2;
-    const int r16 = lane & 15, q = lane >> 4;
-    const int nchunk = a.Bp / TB;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk), bc = slot % nchunk;
-    if (range >= a.ranges) return;
-    const int nsub_total = (ca.M + TI - 1) / TI;
-    const int s_begin = (int)((long)range * nsub_total / a.ranges), s_end = (int)((long)(range + 1) * nsub_total / a.ranges);
-    int nid = 0;                                             // wave 0: the id at position `lane` of the tile fetched last, and that tile's
-    u64 nlm = 0;                                             // live mask
-    auto fetch_ids = [&](int s) {                            // wave 0 only
-        const int p = s * TI + lane;
-        int id = 0x7fffffff;
-        bool bad = false;
-        if (p < ca.M) {
-            id = ca.cand[p];
-            const int prev = p > 0 ? ca.cand[p - 1] : 0;
-            bad = id < 1 || id <= prev;
-        }
-        const u64 anybad = __ballot(bad);
-        if (anybad && lane == 0 && ca.status) atomicOr(ca.status, ADER_ST_BAD_CAND);
-        nid = id;
-        nlm = __ballot(p < ca.M && !bad && id <= a.N);
-    };
-    if (wave == 0 && s_begin < s_end) {
-        fetch_ids(s_begin);
-        idl[(s_begin & 1) * TI + lane] = nid;
-        if (lane == 0) lm[s_begin & 1] = nlm;
-    }
-    for (int i = tid; i < 64 * LDE; i += 512) {              // stage_tile's layout, written out (see k_topk_tile)
-        const int r = i / LDE, c = i - r * LDE;
-        R_l[i] = (bc * TB + r < a.B && c < H) ? a.rep[(size_t)(bc * TB + r) * H + c] : 0.0f;
-    }
-    if (tid < TB) { thr[tid] = 0; msk[tid] = 0; cnt[tid] = 0; }
-    int nc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) nc[j] = a.ncol[bc * TB + nw * 32 + j * 16 + r16];
-    float pre[TOPK_STAGE_REGS];                              // the next tile, in stage_tile's element order
-    auto load_tile = [&](int sl) {                           // the rows of the tile whose ids are in slot sl
-        const int* ids = idl + sl * TI;
-        const u64 live = lm[sl];
-#pragma unroll
-        for (int n = 0; n < TOPK_STAGE_REGS; ++n) {
-            const int i = tid + n * 512, r = (i / LDE) & (TI - 1), c = i - (i / LDE) * LDE;
-            const bool ok = i < 64 * LDE && c < H && ((live >> r) & 1ull);
-            pre[n] = ok ? a.emb1[(size_t)(ids[r] - 1) * H + c] : 0.0f;      // live: 1 <= ids[r] <= N
-        }
-    };
-    __syncthreads();                                         // the first tile's ids are in LDS
-    if (s_begin < s_end) load_tile(s_begin & 1);
-    if (wave == 0 && s_begin + 1 < s_end) fetch_ids(s_begin + 1);
-    for (int s = s_begin; s < s_end; ++s) {
-        const int cur = s & 1;
-        const int* ids = idl + cur * TI;
-        __syncthreads();                                     // the previous tile's MFMA reads, filter and compaction are done
-#pragma unroll
-        for (int n = 0; n < TOPK_STAGE_REGS; ++n)
-            if (tid + n * 512 < 64 * LDE) E_l[tid + n * 512] = pre[n];
-        if (wave == 0 && s + 1 < s_end) {                    // the other slot's last readers (tile s - 1) are behind the barrier above
-            idl[(cur ^ 1) * TI + lane] = nid;
-            if (lane == 0) lm[cur ^ 1] = nlm;
-        }
-        if (a.seen) {                                        // thread (row = tid / 8, part = tid % 8): the 8 lanes of a row are neighbours
-            const int row = tid >> 3, b = bc * TB + row;
-            const int lo = ids[0], hi = ids[TI - 1];
-            u64 m = 0;
-            if (b < a.B)
-                for (int t = tid & 7; t < a.seen_ld; t += 8) {
-                    const int sid = a.seen[(size_t)b * a.seen_ld + t];
-                    if (sid < lo || sid > hi) continue;
-                    int x = 0;                               // the first position whose id is >= sid: x + h - 1 <= 62, x <= 63
-#pragma unroll
-                    for (int h = TI / 2; h; h >>= 1)
-                        if (ids[x + h - 1] < sid) x += h;
-                    if (ids[x] == sid) m |= 1ull << x;
-                }
-            m |= __shfl_xor(m, 1, 64); m |= __shfl_xor(m, 2, 64); m |= __shfl_xor(m, 4, 64);
-            if ((tid & 7) == 0) msk[row] = m;
-        }
-        __syncthreads();
-        if (s + 1 < s_end) load_tile(cur ^ 1);
-        if (wave == 0 && s + 2 < s_end) fetch_ids(s + 2);
-        f32x4 acc[2];
-        acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        {   // mma_tile<2>(E_l + mw * 16 * LDE, LDE, 1, R_l + nw * 32 * LDE, 1, LDE, ksteps, acc, lane), written out: the same operands
-            // into the same instruction in the same k order, hence the same bits.  One more caller of mma_tile<2> changes the code the
-            // compiler emits for k_logits_bwd_de / _drep (tools/isa_digest.py), as one more caller of stage_tile does
-            const float* ap = E_l + (mw * 16 + r16) * LDE + q;
-            const float* bp = R_l + (nw * 32 + r16) * LDE + q;
-            for (int ks = 0; ks < ksteps; ++ks) {
-                const float av = ap[0];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bp[j * 16 * LDE], acc[j], 0, 0, 0);
-                ap += 4;
-                bp += 4;
-            }
-        }
-        const int il0 = mw * 16 + q * 4;                     // this lane's 4 consecutive positions of the tile
-        const u64 dead = ~lm[cur];
-        int id4[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) id4[r] = ids[il0 + r];
-        int over = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int bl = nw * 32 + j * 16 + r16;           // batch row within the chunk
-            const u64 t = thr[bl];
-            const unsigned sm = (unsigned)((msk[bl] | dead) >> il0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const u64 key = topk_key(acc[j][r], id4[r]);
-                if (!((sm >> r) & 1u) && id4[r] <= nc[j] && key > t) {
-                    const int p = atomicAdd(cnt + bl, 1);    // p < k + 64 (the invariant of k_topk_tile)
-                    buf[bl * ldb + p] = key;
-                    over |= (p >= k);
-                }
-            }
-        }
-        if (__syncthreads_or(over)) {                        // some row holds more than k keys: wave w compacts rows 8w .. 8w+7
-            for (int rr = 0; rr < TB / 8; ++rr) {
-                const int row = wave * (TB / 8) + rr, n = cnt[row];
-                if (n <= k) continue;                        // (wave-uniform)
-                u64* bp = buf + row * ldb;
-                const u64 e0 = lane < n ? bp[lane] : 0, e1 = lane + 64 < n ? bp[lane + 64] : 0;      // n <= k + 64 <= 128
-                int r0 = 0, r1 = 0;                          // keys of a row are distinct: rank = number of larger keys
-                for (int i = 0; i < n; ++i) { const u64 x = bp[i]; r0 += x > e0; r1 += x > e1; }
-                // in place: a rank depends on every read of the loop, and one wave's LDS operations are performed in order
-                if (lane < n && r0 < k) { bp[r0] = e0; if (r0 == k - 1) thr[row] = e0; }
-                if (lane + 64 < n && r1 < k) { bp[r1] = e1; if (r1 == k - 1) thr[row] = e1; }
-                if (lane == 0) cnt[row] = k;
-            }
-        }
-    }
-    __syncthreads();
-    u64* o = a.part + ((size_t)range * a.Bp + bc * TB) * k;
-    for (int i = tid; i < TB * k; i += 512) {
-        const int row = i / k, j = i - row * k;
-        o[i] = j < cnt[row] ? buf[row * ldb + j] : 0;        // (an empty range writes zeros: no candidate)
     }
 }
 
@@ -1053,64 +675,6 @@ int ader_rank_targets(const float* rep, const float* emb, int B, int Bp, int H, 
     hipLaunchKernelGGL(k_target_logit, dim3(Bp / TB), dim3(256), kTgtLds, st, a, tlogit);
     a.tlogit = tlogit; a.rank = rank;
     hipLaunchKernelGGL(k_logits_tile<MODE_RANK>, dim3((N + TI - 1) / TI), dim3(512), kTileLds, st, a);
-    HIP_LAUNCH_CHECK();
-    return 0;
-}
-
-// Exact top-K items of every row (kernels above).  ader_topk_ranges: item ranges per 64-row chunk -- about one workgroup per CU over the
-// Bp/64 chunks, a multiple of 8 (the block -> (range, chunk) mapping), so it may exceed the number of 64-item tiles: such ranges are empty.
-int ader_topk_kmax(void) { return TOPK_KMAX; }
-int ader_topk_ranges(int N, int Bp) {
-    const int nsub = (N + TI - 1) / TI;
-    const int nchunk = Bp / TB > 0 ? Bp / TB : 1;
-    int target = 256 / nchunk / 8 * 8;
-    if (target < 8) target = 8;
-    int r = (nsub + 7) / 8 * 8;
-    if (r > target) r = target;
-    if (r < 8) r = 8;
-    return r;
-}
-// items / scores [B,k]: the first k of items 1..N (minus the non-zero ids of seen[b, 0:seen_ld], if seen) by (score descending, id
-// ascending); fewer than k candidates: the tail is item 0, score -inf.  ncol: [Bp] = N for real rows, 0 for padding; seen: [B, seen_ld]
-// or NULL; part: ader_topk_ranges(N,Bp) * Bp * k keys of scratch.  Enqueue only.
-int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
-                    int k, unsigned long long* part, int* items, float* scores, void* stream) {
-    if (k < 1 || k > TOPK_KMAX || Bp % TB != 0 || Bp > MAXB || B > Bp || H > HP || H < 1 || N < 1 || (seen && seen_ld < 1)) return -2;
-    if (B <= 0) return 0;
-    TopkArgs a;
-    a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ncol = ncol; a.seen = seen; a.seen_ld = seen_ld; a.k = k;
-    a.ranges = ader_topk_ranges(N, Bp); a.part = part; a.items = items; a.scores = scores;
-    const size_t lds = (size_t)(2 * 64 * LDE) * sizeof(float) + (size_t)TB * (k + TI) * sizeof(u64) + TB * (2 * sizeof(u64) + sizeof(int));
-    const int rc = ader_dyn_lds<k_topk_tile>(lds);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_topk_tile, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, a);
-    hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, st, a);
-    HIP_LAUNCH_CHECK();
-    return 0;
-}
-// ader_topk_items over the items of cand[0:M] only (kernel above): a strictly ascending list of 1-based ids, shared by every row; ids
-// above N are ignored, as seen ids above N are.  N: no table row beyond item N is read.  M = 0: every row is padding (cand may be NULL).
-// part: ader_topk_ranges(M,Bp) * Bp * k keys of scratch.  status (NULL: none): ADER_ST_BAD_CAND is OR-ed in when the list is not
-// strictly ascending or holds an id < 1; the result is then unspecified, and nothing outside the table is read.  Enqueue only.
-int ader_topk_items_cand(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* cand, int M,
-                         const int* seen, int seen_ld, int k, unsigned long long* part, int* items, float* scores, int* status,
-                         void* stream) {
-    if (k < 1 || k > TOPK_KMAX || Bp % TB != 0 || Bp > MAXB || B > Bp || H > HP || H < 1 || N < 1 || M < 0 || (M > 0 && !cand) ||
-        (seen && seen_ld < 1)) return -2;
-    if (B <= 0) return 0;
-    TopkCandArgs ca;
-    TopkArgs& a = ca.t;
-    a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ncol = ncol; a.seen = seen; a.seen_ld = seen_ld; a.k = k;
-    a.ranges = ader_topk_ranges(M, Bp); a.part = part; a.items = items; a.scores = scores;
-    ca.cand = cand; ca.M = M; ca.status = status;
-    const size_t lds = (size_t)(2 * 64 * LDE) * sizeof(float) + (size_t)TB * (k + TI) * sizeof(u64) + TB * (2 * sizeof(u64) + sizeof(int)) +
-                       2 * sizeof(u64) + 2 * TI * sizeof(int);
-    const int rc = ader_dyn_lds<k_topk_cand>(lds);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_topk_cand, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, ca);
-    hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, st, a);
     HIP_LAUNCH_CHECK();
     return 0;
 }

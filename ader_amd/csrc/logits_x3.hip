@@ -25,7 +25,7 @@
 // Output partials (pm, pl, pO per item range) and the merge (k_lbf_combine<true>) are those of k_lx3_fwd.  gfx950 only.
 #include "lbf_common.h"
 #include "x3_image.h"
-#include "topk_key.h"
+#include "logit_tile.h"
 #include "../../include/ader_hip.h"
 
 #define F3_FB 32                   // items per streamed block
@@ -754,7 +754,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3k(RankX3Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Top-K recommendation on the bf16 matrix cores, byte-identical to ader_topk_items (k_topk_tile + k_topk_merge, logits.hip): the same
+// Top-K recommendation on the bf16 matrix cores, byte-identical to ader_topk_items (k_topk_tile + k_topk_merge, topk.hip): the same
 // items in the same order (score descending, id ascending) and the same float32 score bits, by construction and not by tolerance.
 // k_lx3t computes every catalog logit at x3 grade (s3) and keeps, per row, a small SUPERSET of the exact top-k; k_topk3_finish merges
 // the ranges' sets, recomputes the kept (row, item) pairs on the exact chain and selects the best k by the exact key.
@@ -791,7 +791,6 @@ __global__ __launch_bounds__(256, 2) void k_lx3k(RankX3Args a) {
 // (212 compiled, no scratch).
 #define TK3_KMAX 40
 #define TK3_BANDMAX 16
-#define TK3_LDE 162                 // logits.hip's LDE: the [64][LDE] operand layout of the exact chain
 
 struct TopkX3Args {
     const float* rep; const float* emb1; int vrows; // fp32 rep [B,H]; fp32 table, row of item 1; rows available from it (item_num)
@@ -908,7 +907,7 @@ __global__ __launch_bounds__(256, 1) void k_lx3t(TopkX3Args a) {
 __global__ __launch_bounds__(256) void k_topk3_finish(TopkX3Args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* E_l = smem;                                     // [keep rounded up to 16][LDE] table rows of the kept pairs
-    float* R_l = E_l + ((a.keep + 15) & ~15) * TK3_LDE;    // [LDE] the row's rep: every pair's second operand (column stride 0)
+    float* R_l = E_l + ((a.keep + 15) & ~15) * LDE;        // [LDE] the row's rep: every pair's second operand (column stride 0)
     __shared__ u64 mb[TK3_KMAX + TK3_BANDMAX + 256];
     __shared__ u64 ek[64];
     __shared__ float mlo;
@@ -952,16 +951,16 @@ __global__ __launch_bounds__(256) void k_topk3_finish(TopkX3Args a) {
         return;
     }
     const int H = a.H, ksteps = (H + 3) >> 2;
-    for (int i = tid; i < ((n + 15) & ~15) * TK3_LDE; i += 256) {
-        const int r = i / TK3_LDE, c = i - r * TK3_LDE;
+    for (int i = tid; i < ((n + 15) & ~15) * LDE; i += 256) {
+        const int r = i / LDE, c = i - r * LDE;
         E_l[i] = (r < n && c < H) ? a.emb1[(size_t)(topk_item(mb[r]) - 1) * H + c] : 0.0f;
     }
-    for (int c = tid; c < TK3_LDE; c += 256) R_l[c] = c < H ? a.rep[(size_t)b * H + c] : 0.0f;
+    for (int c = tid; c < LDE; c += 256) R_l[c] = c < H ? a.rep[(size_t)b * H + c] : 0.0f;
     __syncthreads();
     f32x4 acc[1];
     acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (wave * 16 < n)                                     // (wave-uniform) the same fma chain in k order whatever the neighbours
-        mma_tile<1>(E_l + wave * 16 * TK3_LDE, TK3_LDE, 1, R_l, 1, 0, ksteps, acc, lane);
+        mma_tile<1>(E_l + wave * 16 * LDE, LDE, 1, R_l, 1, 0, ksteps, acc, lane);
     const int col = lane & 15, q = lane >> 4;
     const int p = wave * 16 + col;
 #pragma unroll
@@ -1062,7 +1061,7 @@ int ader_topk_items_x3(const float* rep, const float* emb, int item_num, int B, 
     a.ncol = ncol; a.seen = seen; a.seen_ld = seen_ld; a.delta = delta; a.part3 = part3; a.status = status; a.diag = diag;
     a.items = items; a.scores = scores;
     const size_t lds = 3 * X3B_IMG_B + (size_t)G3_ROWS * (a.keep + F3_FB) * sizeof(u64) + G3_ROWS * sizeof(int);
-    const size_t lds_fin = (size_t)((((a.keep + 15) & ~15) + 1) * TK3_LDE) * sizeof(float);
+    const size_t lds_fin = (size_t)((((a.keep + 15) & ~15) + 1) * LDE) * sizeof(float);
     if (int e = ader_dyn_lds<k_lx3t>(lds)) return e;
     if (int e = ader_dyn_lds<k_topk3_finish>(lds_fin)) return e;
     hipStream_t st = (hipStream_t)stream;

@@ -1,4 +1,4 @@
-// The 64-bit candidate key of the top-K kernels (logits.hip: k_topk_tile / k_topk_merge; logits_x3.hip: k_lx3t / k_topk3_finish):
+// The 64-bit candidate key of the top-K kernels (topk.hip: k_topk_tile / k_topk_merge; logits_x3.hip: k_lx3t / k_topk3_finish):
 // order-preserving float bits above, the complemented 1-based item id below, so ONE unsigned compare is the total order (score
 // descending, item id ascending) and no two candidates of a row compare equal.  Key 0 = "no candidate".
 #pragma once

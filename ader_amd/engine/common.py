@@ -241,7 +241,7 @@ def issue_table_job(job, lists, table, item_num, H, shadow, rep_img, lr_t, b1, b
 
 
 LDR = 168           # bf16 elements of an operand-plane / shadow row (csrc/lbf_common.h)
-HP = 160            # padded hidden width: floats of a readout / slab row (csrc/lbf_common.h; gemm.hip and logits.hip define the same)
+HP = 160            # padded hidden width: floats of a readout / slab row (csrc/lbf_common.h; gemm.hip and logit_tile.h define the same)
 PART_LD = 152       # floats of a shard partial {max, sum, O[H]} per row (csrc/logits_bf16.hip)
 X3_IMG_ROW_B = 22528 // 32      # x3 operand image bytes per batch row: X3_IMG_B (csrc/x3_image.h) per X3_CH rows (csrc/table_update_x3.hip)
 FlashSizes = collections.namedtuple("FlashSizes", "plane pm pl pO pO2 row part")

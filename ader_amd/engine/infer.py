@@ -342,7 +342,7 @@ class _Infer:
         """recommend's contract for wide answers, 1 <= k <= ader_topk_wide_kmax() (= 1024): (items int32 [n,k], scores float32 [n,k]) as
         numpy, items == stable_argsort(-logits)[:, :k] + 1 on the very float32 logits() returns, order (score descending, item id
         ascending), exclude_seen and the item 0 / -inf padding as recommend's; for k <= 64 the bytes are recommend(dtype="f32")'s.
-        Slab and select (ader_topk_items_wide, csrc/topk_wide.hip): per row a list of cap keys in global memory (cap: a multiple of 64
+        Slab and select (ader_topk_items_wide, csrc/topk.hip): per row a list of cap keys in global memory (cap: a multiple of 64
         in [k + 64, ader_topk_wide_cap()]; None: the largest, 4096), cut to its exact best k between slabs of the catalog walk; no
         [n, max_item] logits are written.  Chunks of MAX_ROWS rows, one device -> host copy of items, scores, status and diag.  A row
         whose list overflowed between two selects (scores trending upwards with the item id) is recomputed exactly, and slowly: dense

@@ -197,35 +197,44 @@ def _(rep, emb, target, N):
     return target.new_empty(rep.shape[0])
 
 
+def _topk_prologue(op, rep, emb, seen, N, k, kmax, pad=64):
+    """What the topk_items* operators check and allocate alike -> (B, Bp, H, seen_ld, ncol, items, scores): Bp = B padded to `pad` rows,
+    ncol int32 [Bp] = N for real rows and 0 for padding rows, items int32 / scores float32 [B,k] uninitialised."""
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
+    B, H = rep.shape
+    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
+        raise RuntimeError("ader::%s: bad shapes" % op)
+    if not (1 <= k <= kmax):
+        raise RuntimeError("ader::%s: k must be in 1..%d (got %d)" % (op, kmax, k))
+    if seen is not None:
+        _chk(seen, "seen", torch.int32, 2)
+        if seen.shape[0] != B or seen.shape[1] < 1:
+            raise RuntimeError("ader::%s: seen must be [B, S] with S >= 1" % op)
+    Bp = (B + pad - 1) // pad * pad
+    dev = rep.device
+    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
+    ncol[:B] = N
+    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
+    return B, Bp, H, seen.shape[1] if seen is not None else 0, ncol, items, scores
+
+
+def _topk_fake(rep, *rest):
+    k = rest[-1]                # every (items, scores) operator ends its arguments with (N, k)
+    return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
+
+
 @torch.library.custom_op("ader::topk_items", mutates_args=())
 def topk_items(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor], N: int, k: int) -> tuple[torch.Tensor, torch.Tensor]:
     """rep [B,H], emb [V,H] (row 0 = padding item), seen int32 [B,S] ids to leave out (0 = none, ids above N ignored) or None ->
     (items int32 [B,k], scores float32 [B,k]): the first k of items 1..N by (logit descending, id ascending), the logits of
     ader_logits_store bit for bit; fewer than k candidates: item 0, score -inf."""
-    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
-    B, H = rep.shape
-    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
-        raise RuntimeError("ader::topk_items: bad shapes")
-    if not (1 <= k <= call("ader_topk_kmax")):
-        raise RuntimeError("ader::topk_items: k must be in 1..%d (got %d)" % (call("ader_topk_kmax"), k))
-    if seen is not None:
-        _chk(seen, "seen", torch.int32, 2)
-        if seen.shape[0] != B or seen.shape[1] < 1:
-            raise RuntimeError("ader::topk_items: seen must be [B, S] with S >= 1")
-    Bp = (B + 63) // 64 * 64
-    dev = rep.device
-    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
-    ncol[:B] = N
-    part = torch.empty(call("ader_topk_ranges", N, Bp) * Bp * k, dtype=torch.int64, device=dev)
-    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
-    call("ader_topk_items", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen.shape[1] if seen is not None else 0, k,
-         ptr(part), ptr(items), ptr(scores), _st())
+    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items", rep, emb, seen, N, k, call("ader_topk_kmax"))
+    part = torch.empty(call("ader_topk_ranges", N, Bp) * Bp * k, dtype=torch.int64, device=rep.device)
+    call("ader_topk_items", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen_ld, k, ptr(part), ptr(items), ptr(scores), _st())
     return items, scores
 
 
-@topk_items.register_fake
-def _(rep, emb, seen, N, k):
-    return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
+topk_items.register_fake(_topk_fake)
 
 
 @torch.library.custom_op("ader::topk_items_cand", mutates_args=())
@@ -235,34 +244,19 @@ def topk_items_cand(rep: torch.Tensor, emb: torch.Tensor, cand: torch.Tensor, se
     ignored; M = 0 returns padding) -> (items int32 [B,k], scores float32 [B,k]) with topk_items' scores, order, ties and padding.  The
     list's table rows are gathered in the kernel: work follows M, not N.  The op does not sort for the caller: a list that is not
     strictly ascending, or holds an id < 1, raises (one synchronisation to read the status)."""
-    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(cand, "cand", torch.int32, 1)
-    B, H = rep.shape
-    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
-        raise RuntimeError("ader::topk_items_cand: bad shapes")
-    if not (1 <= k <= call("ader_topk_kmax")):
-        raise RuntimeError("ader::topk_items_cand: k must be in 1..%d (got %d)" % (call("ader_topk_kmax"), k))
-    if seen is not None:
-        _chk(seen, "seen", torch.int32, 2)
-        if seen.shape[0] != B or seen.shape[1] < 1:
-            raise RuntimeError("ader::topk_items_cand: seen must be [B, S] with S >= 1")
+    _chk(cand, "cand", torch.int32, 1)
+    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_cand", rep, emb, seen, N, k, call("ader_topk_kmax"))
     M = cand.shape[0]
-    Bp = (B + 63) // 64 * 64
-    dev = rep.device
-    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
-    ncol[:B] = N
-    part = torch.empty(call("ader_topk_ranges", M, Bp) * Bp * k, dtype=torch.int64, device=dev)
-    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    call("ader_topk_items_cand", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(cand) if M else None, M, ptr(seen),
-         seen.shape[1] if seen is not None else 0, k, ptr(part), ptr(items), ptr(scores), ptr(status), _st())
+    part = torch.empty(call("ader_topk_ranges", M, Bp) * Bp * k, dtype=torch.int64, device=rep.device)
+    status = torch.zeros(1, dtype=torch.int32, device=rep.device)
+    call("ader_topk_items_cand", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(cand) if M else None, M, ptr(seen), seen_ld, k,
+         ptr(part), ptr(items), ptr(scores), ptr(status), _st())
     if int(status.item()):
         raise RuntimeError("ader::topk_items_cand: cand must be strictly ascending item ids >= 1")
     return items, scores
 
 
-@topk_items_cand.register_fake
-def _(rep, emb, cand, seen, N, k):
-    return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
+topk_items_cand.register_fake(_topk_fake)
 
 
 @torch.library.custom_op("ader::topk_items_x3", mutates_args=())
@@ -270,31 +264,17 @@ def topk_items_x3(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Ten
     """topk_items' contract and result, byte for byte, through ader_topk_items_x3 (k <= ader_topk_x3_kmax(), H as rank_of_target_x3).
     Reads the row status back (one synchronisation): rows whose kept set outgrew k + TOPK_X3_BAND keys take topk_items' answer."""
     from .engine.infer import TOPK_X3_BAND, rank_x3_supports
-    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
-    B, H = rep.shape
-    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
-        raise RuntimeError("ader::topk_items_x3: bad shapes")
+    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_x3", rep, emb, seen, N, k, call("ader_topk_x3_kmax"), pad=128)
     if not rank_x3_supports(H):
         raise RuntimeError("ader::topk_items_x3: H must be even, 8 <= H <= 160, H mod 8 in {0, 4, 6} (got %d)" % H)
-    if not (1 <= k <= call("ader_topk_x3_kmax")):
-        raise RuntimeError("ader::topk_items_x3: k must be in 1..%d (got %d)" % (call("ader_topk_x3_kmax"), k))
-    if seen is not None:
-        _chk(seen, "seen", torch.int32, 2)
-        if seen.shape[0] != B or seen.shape[1] < 1:
-            raise RuntimeError("ader::topk_items_x3: seen must be [B, S] with S >= 1")
-    Bp = (B + 127) // 128 * 128
     dev = rep.device
-    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
-    ncol[:B] = N
     delta, emax = torch.empty(Bp, device=dev), torch.empty(1, device=dev)
     rep_hi, rep_lo = (torch.empty(Bp * LDR, dtype=torch.bfloat16, device=dev) for _ in range(2))
     part3 = torch.empty(call("ader_topk_x3_ranges", N, Bp) * Bp * (k + TOPK_X3_BAND), dtype=torch.int64, device=dev)
     status, diag = torch.empty(Bp, dtype=torch.int32, device=dev), torch.empty(3, dtype=torch.int32, device=dev)
-    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
     call("ader_rank_emax", ptr(emb), emb.shape[0] - 1, H, N, ptr(emax), _st())
-    call("ader_topk_items_x3", ptr(rep), ptr(emb), emb.shape[0] - 1, B, Bp, H, N, ptr(ncol), ptr(seen),
-         seen.shape[1] if seen is not None else 0, k, TOPK_X3_BAND, ptr(rep_hi), ptr(rep_lo), ptr(delta), ptr(emax), ptr(part3),
-         ptr(status), ptr(diag), ptr(items), ptr(scores), _st())
+    call("ader_topk_items_x3", ptr(rep), ptr(emb), emb.shape[0] - 1, B, Bp, H, N, ptr(ncol), ptr(seen), seen_ld, k, TOPK_X3_BAND,
+         ptr(rep_hi), ptr(rep_lo), ptr(delta), ptr(emax), ptr(part3), ptr(status), ptr(diag), ptr(items), ptr(scores), _st())
     over = status[:B] != 0
     if bool(over.any().item()):
         fi, fs = topk_items(rep, emb, seen, N, k)
@@ -302,9 +282,7 @@ def topk_items_x3(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Ten
     return items, scores
 
 
-@topk_items_x3.register_fake
-def _(rep, emb, seen, N, k):
-    return rep.new_empty((rep.shape[0], k), dtype=torch.int32), rep.new_empty((rep.shape[0], k))
+topk_items_x3.register_fake(_topk_fake)
 
 
 @torch.library.custom_op("ader::topk_items_wide", mutates_args=())
@@ -314,28 +292,15 @@ def topk_items_wide(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.T
     list per row in global memory, a multiple of 64 in [k + 64, ader_topk_wide_cap() = 4096] -> (items int32 [B,k], scores float32
     [B,k], overflowed int32 [B]).  Rows with overflowed != 0 lost a key between two selects and are unspecified: the operator has no
     fallback and does not synchronise (Engine.recommend_wide recomputes such rows)."""
-    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
-    B, H = rep.shape
-    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
-        raise RuntimeError("ader::topk_items_wide: bad shapes")
-    if not (1 <= k <= call("ader_topk_wide_kmax")):
-        raise RuntimeError("ader::topk_items_wide: k must be in 1..%d (got %d)" % (call("ader_topk_wide_kmax"), k))
+    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_wide", rep, emb, seen, N, k, call("ader_topk_wide_kmax"))
     if cap % 64 != 0 or not (k + 64 <= cap <= call("ader_topk_wide_cap")):
         raise RuntimeError("ader::topk_items_wide: cap must be a multiple of 64 in [k + 64 = %d, %d] (got %d)" %
                            (k + 64, call("ader_topk_wide_cap"), cap))
-    if seen is not None:
-        _chk(seen, "seen", torch.int32, 2)
-        if seen.shape[0] != B or seen.shape[1] < 1:
-            raise RuntimeError("ader::topk_items_wide: seen must be [B, S] with S >= 1")
-    Bp = (B + 63) // 64 * 64
     dev = rep.device
-    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
-    ncol[:B] = N
     lst, thr = torch.empty(Bp * cap, dtype=torch.int64, device=dev), torch.empty(Bp, dtype=torch.int64, device=dev)
     cnt, status = torch.empty(Bp, dtype=torch.int32, device=dev), torch.empty(Bp, dtype=torch.int32, device=dev)
     diag = torch.empty(2, dtype=torch.int32, device=dev)
-    items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
-    call("ader_topk_items_wide", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen.shape[1] if seen is not None else 0, k, cap,
+    call("ader_topk_items_wide", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen_ld, k, cap,
          ptr(lst), ptr(cnt), ptr(thr), ptr(status), ptr(diag), ptr(items), ptr(scores), _st())
     return items, scores, status[:B].clone()
 

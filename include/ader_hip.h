@@ -284,7 +284,7 @@ int ader_topk_x3_ranges(int N, int Bp);
 int ader_topk_items_x3(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* ncol, const int* seen,
                        int seen_ld, int k, int band, void* rep_hi, void* rep_lo, float* delta, const float* emax,
                        unsigned long long* part3, int* status, int* diag, int* items, float* scores, void* stream);
-/* ader_topk_items' contract for wide answers, 1 <= k <= ader_topk_wide_kmax() (= 1024), by slab and select (csrc/topk_wide.hip): no LDS
+/* ader_topk_items' contract for wide answers, 1 <= k <= ader_topk_wide_kmax() (= 1024), by slab and select (csrc/topk.hip): no LDS
  * buffer grows with k.  Per row a list of cap keys in global memory; the catalog is walked in slabs of 64-item tiles, k_topk_wide_tile
  * appends every key that beats the row's threshold, k_topk_wide_select cuts the list to its exact best k after every slab and unpacks
  * after the last.  cap: a multiple of 64, k + 64 <= cap <= ader_topk_wide_cap() (= 4096).  ader_topk_wide_slabs: the slab schedule, a

@@ -364,7 +364,7 @@ def emulate(inp, chunk=None, ncol=None, shards=None, fault=None, frow=None, unfu
 
 # =============================================================================================== exact-f32 kernels (logits.hip)
 def logits_ranges(N, Bp):
-    """ader_logits_ranges (logits.hip:775-781): item ranges of the dRep launch -- 8, doubled while the launch stays within ~1024
+    """ader_logits_ranges (logits.hip): item ranges of the dRep launch -- 8, doubled while the launch stays within ~1024
     workgroups and every range can hold a 64-item sub-tile."""
     nsub = (N + TI - 1) // TI
     target = 1024 // (Bp // 64)
@@ -388,19 +388,19 @@ def _chain_mm(A, Bm):
 def emulate_f32(inp, ncol=None, no_teacher=None, label_shift=None):
     """The arithmetic logits.hip states, in float32 (Engine.loss_and_grad with logits_dtype = "f32": ader_logits_loss_fwd,
     ader_logits_bwd_drep, ader_logits_bwd_demb, then the ordered scatter):
-      s        = rep . E^T in float32 (mma_tile on v_mfma_f32_16x16x4_f32: logits.hip:103, 288, 353).  mma_tile (common.h:93-107)
+      s        = rep . E^T in float32 (mma_tile on v_mfma_f32_16x16x4_f32, in k_logits_tile, k_logits_bwd_de, k_logits_bwd_drep).  mma_tile (common.h)
                is ONE accumulator per output carried through the k steps in order, and the f32 MFMA is a chain of fmaf: every product
                of these kernels is emulated as that chain (_chain_mm), not as a blocked sum;
-      lse      from per-row online (max, sum-exp) partials, merged by merge_ml (logits.hip:69-74, 128-164, 199-221) -- here one
-               partial per 64-item sub-tile, merged in tile order -- lse = m + logf(l) (line 217);
-      target   dot = s at the label column + sum_n expf(t_n - tlse) s_n over a distilled row's teacher columns (lines 139-140),
-               tlse = m + logf(sum expf(t - m)) (k_row_lse, lines 238-257); rowloss = w (lse - dot) (line 219), loss = their sum;
-      dlogit   (lines 259-265) p = expf(s - lse); p -= 1 at the label column; p -= expf(t - tlse) for a distilled row; every
+      lse      from per-row online (max, sum-exp) partials, merged by merge_ml (k_logits_tile<MODE_LSE>, k_lse_loss) -- here one
+               partial per 64-item sub-tile, merged in tile order -- lse = m + logf(l) (k_lse_loss);
+      target   dot = s at the label column + sum_n expf(t_n - tlse) s_n over a distilled row's teacher columns (k_logits_tile<MODE_LSE>),
+               tlse = m + logf(sum expf(t - m)) (k_row_lse); rowloss = w (lse - dot) (k_lse_loss), loss = their sum;
+      dlogit   (dlogit()) p = expf(s - lse); p -= 1 at the label column; p -= expf(t - tlse) for a distilled row; every
                column >= ncol is 0; c = w p;
-      dE       = c^T rep accumulated in 64-row batch chunks (k_logits_bwd_de, lines 282-302) into accumulators that live across the
-               chunks (line 279): one fmaf chain over ALL batch rows in order; every row written once (303-312);
+      dE       = c^T rep accumulated in 64-row batch chunks (k_logits_bwd_de) into accumulators that live across the
+               chunks (dacc): one fmaf chain over ALL batch rows in order; every row written once;
       dRep     = c . E over logits_ranges(N, Bp) item ranges of per = ceil(sub-tiles / ranges) sub-tiles each -- a range beyond the
-               catalog holds none and contributes zeros -- accumulated tile by tile (lines 327-365), the ranges then summed;
+               catalog holds none and contributes zeros -- accumulated tile by tile (k_logits_bwd_drep), the ranges then summed;
       inputs   added in (id, position) order with the factor sqrt(H) as float32 (_scatter_ordered).
     The first GPU run found this emulation short of that stated step: with dE as blocked float32 sums per chunk (torch's matmul) the
     device sat at 10.1x the emulated error in the rows only the GEMM writes at B = 1024 (2.0e-06 against 2.0e-07; 1.0 .. 2.5x at the

@@ -115,6 +115,36 @@ def test_all_ids_equal_the_contiguous_walk_and_the_masked_argsort(i, exclude):
     assert eng.last_topk_stats is None
 
 
+@functools.lru_cache(maxsize=None)
+def _three_entry_case():
+    """B = 70: two chunks, six rows in the second.  N = 8,300: 130 tiles over ader_topk_ranges = 128 ranges per chunk, so two workgroups
+    per chunk carry a row's threshold from one tile into the next; k = 64 = K_MAX."""
+    B, N, T = 70, 8300, 20
+    eng = _engine(N, T, 150, 1, 1)
+    seq = _seqs(np.random.RandomState(77), B, T, N)
+    lg = eng.logits(seq, N).cpu().numpy()
+    lg.setflags(write=False)
+    seq.setflags(write=False)
+    return eng, seq, lg, N, 64
+
+
+@pytest.mark.parametrize("exclude", [False, True])
+def test_the_three_entry_points_of_the_shared_row_buffer_return_equal_bytes(exclude):
+    """recommend (k_topk_tile), recommend_among over all ids (k_topk_cand) and recommend_wide (k_topk_wide_tile) share the walk, the
+    tile stream and -- the first two -- the row buffer of csrc/logit_tile.h: the same bytes, and the stable argsort of the logits."""
+    from ader_amd._lib import call
+    eng, seq, lg, N, k = _three_entry_case()
+    assert (N + 63) // 64 == 130 and call("ader_topk_ranges", N, 128) == 128
+    full = np.arange(1, N + 1)
+    tile = eng.recommend(seq, k, N, exclude_seen=exclude, dtype="f32")
+    among = eng.recommend_among(seq, k, full, N, exclude_seen=exclude)
+    wide = eng.recommend_wide(seq, k, N, exclude_seen=exclude)
+    assert eng.last_topk_stats["overflowed_rows"] == 0             # the wide rows are k_topk_wide_tile's, not a recomputation
+    for name, got in (("recommend_among", among), ("recommend_wide", wide)):
+        assert got[0].tobytes() == tile[0].tobytes() and got[1].tobytes() == tile[1].tobytes(), name
+    _assert_same(tile, _reference(lg, full, seq, k, exclude))
+
+
 @pytest.mark.parametrize("exclude", [False, True])
 @pytest.mark.parametrize("i", range(len(SHAPES)))
 def test_candidate_patterns_are_the_head_of_the_masked_stable_argsort(i, exclude):

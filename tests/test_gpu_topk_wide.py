@@ -1,5 +1,5 @@
 """Exact top-K recommendation for wide answers, k up to 1024 (Engine.recommend_wide, Ader.recommend, torch.ops.ader.topk_items_wide,
-ader_topk_items_wide: slab and select, csrc/topk_wide.hip).  The contract is Engine.recommend's: items ==
+ader_topk_items_wide: slab and select, csrc/topk.hip).  The contract is Engine.recommend's: items ==
 stable_argsort(-Engine.logits)[:, :k] + 1 with the gathered device logits as scores, bit for bit, order (score descending, item id
 ascending), item 0 / -inf padding.  No tolerance anywhere.  Every contract case asserts overflowed_rows == 0 and max_list <= cap, so
 the exact fallback of recommend_wide cannot stand in for the kernels (tests/test_topk_wide_host.py holds the premise: Gaussian operands

@@ -1,4 +1,4 @@
-"""Wide top-K (csrc/topk_wide.hip, Engine.recommend_wide) without a GPU: the exports, the slab schedule ader_topk_wide_slabs as a pure
+"""Wide top-K (csrc/topk.hip, Engine.recommend_wide) without a GPU: the exports, the slab schedule ader_topk_wide_slabs as a pure
 host function, and a numpy emulation of slab-and-select on the library's own slab boundaries -- per row a list of 64-bit keys, every
 key of a slab that beats the row's threshold appended, the list cut to its best k after the slab -- against the head of the stable
 argsort.  The emulation also backs the premise of tests/test_gpu_topk_wide.py: on Gaussian operands at its shapes no list outgrows cap,
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-GROWTH = 32     # the slab rule's constant (csrc/topk_wide.hip: WIDE_GROWTH; DESIGN.md says how it was chosen)
+GROWTH = 32     # the slab rule's constant (csrc/topk.hip: WIDE_GROWTH; DESIGN.md says how it was chosen)
 NAMES = ("ader_topk_wide_kmax", "ader_topk_wide_cap", "ader_topk_wide_slabs", "ader_topk_items_wide")
 # the shapes of tests/test_gpu_topk_wide.py: item_num, T, H, L, heads, B, N, k, cap (None: the default)
 GPU_SHAPES = [(700, 50, 150, 2, 1, 70, 650, 100, 256),
