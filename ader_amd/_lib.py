@@ -58,7 +58,6 @@ _SIGS = {
     "ader_lbf_ranges_kd": [I, I, I],
     "ader_lbf_readout_ranges": [I, I, I],
     "ader_lx3_readout_ranges": [I, I],
-    "ader_lx3_fwd_kd": [P, P, I, I, I, I, I, I, I, I, P, P, P, L, P, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "ader_tab_update_sh_kd": [P, P, I, I, I, I, I, I, P, P, P, P, I, P, F, P, P, P, I, P, P, L, P, P, P, P, P, F, F, F, F, P],
     "ader_lbf_merge_parts": [P, I, I, I, I, P, P, P, P, P, P, P, P, P],
     "ader_gather_owned": [P, P, I, I, I, I, P, P],
@@ -69,8 +68,6 @@ _SIGS = {
     "ader_lx3_merge_parts": [P, I, I, I, I, P, P, P, P, P, P, P, P, P],
     "ader_lx3_readout_shard": [P, I, I, I, I, I, I, P, L, P, P, P, P, P],
     "ader_lx3_merge_parts_kd": [P, P, I, I, I, I, P, P, P, P, P, P, P],
-    "ader_lx3_fwd": [P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    "ader_lx3_fwd_img": [P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "ader_lx3_fwd_img_lnf": [P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "ader_lx3_fwd_kd_lnf": [P, P, I, I, I, I, I, I, I, I, P, P, P, L, P, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "ader_tab_grad": [P, P, P, I, I, I, I, I, P, P, P, P, P],

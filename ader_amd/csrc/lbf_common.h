@@ -96,7 +96,7 @@ struct TabArgs {
     int tile_end;           // k_tab32x3: first 64-row tile beyond the launch (its workgroups own PAIRS of tiles)
     float* demb1;           // !ADAM: gradient row of item 1
     // KD rows (ADER.py:132-137): batch rows [kd_row0, Bp) are distilled exemplar rows: dlogit = w (softmax(s[:Np]) - softmax(t)),
-    // zero for items >= Np.  kd_row0 % 128 == 0; = Bp: none.  trow / tlse2: [Bp] as written by ader_lx3_fwd_kd.
+    // zero for items >= Np.  kd_row0 % 128 == 0; = Bp: none.  trow / tlse2: [Bp] as written by ader_lx3_fwd_kd_lnf.
     int kd_row0, Np;
     const float* teacher; long ldt; const int* trow; const float* tlse2;
 };
@@ -137,3 +137,10 @@ static inline void lx3_args_kd(Lx3Args& x, int kd_row0, int Np, const float* tea
                                float* pO2, int ranges2) {
     x.kd_row0 = kd_row0; x.Np = Np; x.teacher = teacher; x.ldt = ldt; x.trow = trow; x.tlse2 = tlse2; x.pO2 = pO2; x.ranges2 = ranges2;
 }
+// the launchers of logits_x3.hip that the C ABI (logits_bf16.hip) calls: the x3 forward on conflict-free block images where
+// lx3f_supports(H) (k_lx3p; it launches k_lx3g itself for H != 150), and the teacher readout of distilled steps k_lx3r where
+// lx3r_supports(x) (H = 150, 16-byte aligned teacher rows, at least one whole block)
+bool lx3f_supports(int H);
+int lx3p_launch(const Lx3Args& x, void* stream);
+bool lx3r_supports(const Lx3Args& x);
+int lx3r_launch(const Lx3Args& x, void* stream);

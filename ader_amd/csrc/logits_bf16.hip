@@ -3,6 +3,9 @@
 // This file holds the bf16 flash forward (k_lbf_fwd) and the merges of its partials, the generic float32-grade (x3) forward k_lx3_fwd
 // (three bf16 MFMAs per product on the fp32 table; the block-image x3 forwards are in logits_x3.hip and share the merges), and the
 // C ABI of both grades, one-hot and distilled rows, including the catalog-sharded forms (_shard / _merge_parts).
+// The forward is stated once: block span, online softmax, P split and epilogues are flash_walk.h's (shared with logits_x3.hip), the
+// ring walk, the transposed readout and the teacher probabilities of this file's row layout stand in front of k_lbf_fwd; each of the
+// four kernel bodies (k_lbf_fwd, its teacher readout, k_lx3_fwd<false / true>) names its phases.
 //
 // Two streaming passes over the table instead of the TF graph's materialised [B,N] logits/softmax/one-hot:
 //
@@ -29,9 +32,21 @@
 //
 // LDS tiles are row-major bf16 with a 168-element (336 B) row stride: ds_read_b128 operand reads are conflict-free
 // (20 r mod 64 covers 16 distinct 4-bank slots).  gfx950 only.
-#include "lbf_common.h"
+#include "flash_walk.h"
 #include "x3_image.h"
 #include "../../include/ader_hip.h"
+
+// Element (row b, column c) of the x3 operand rows, hi = h and lo = l, into the LDS images of the 32-row chunks that the fused update
+// streams (img != NULL: ader_x3_rep_image's output, x3_image.h): both prep kernels of the x3 grade write them on the way.
+// (The hi / lo rows themselves stay written out in the three prep kernels: k_lx3_prep splits before its first store, k_lbf_prep_kd
+// behind it and under its rep_lo test, and one function for all three keeps only one of the two instruction streams.)
+__device__ __forceinline__ void lx3_img_put(char* img, int b, int c, bf16 h, bf16 l) {
+    if (img && c < HP) {
+        char* p = img + (size_t)(b >> 5) * X3_IMG_B + x3_kc_off(c >> 3) + 16 * (b & 31) + 2 * (c & 7);
+        *(bf16*)p = h;
+        *(bf16*)(p + X3_PLANE_B) = l;
+    }
+}
 
 // rep fp32 [B,H] -> rep_bf [Bp, LDR] bf16, zero padded (rows >= B, cols >= H)
 __global__ __launch_bounds__(256) void k_lbf_prep(const float* __restrict__ rep, bf16* __restrict__ rep_bf, int B, int Bp, int H) {
@@ -60,14 +75,10 @@ __global__ __launch_bounds__(256) void k_lbf_prep_kd(const float* __restrict__ r
         const float x = (src >= 0 && c < H) ? rep[(size_t)src * H + c] : 0.0f;
         const bf16 h = (bf16)x;
         rep_bf[i] = h;
-        if (rep_lo) {                                          // x3 mode: low-order operand rows
+        if (rep_lo) {                                          // x3 mode: low-order operand rows and the fused update's operand images
             const bf16 l = (bf16)(x - (float)h);
             rep_lo[i] = l;
-            if (img && c < HP) {                               // ... and the fused update's operand images (as k_lx3_prep)
-                char* p = img + (size_t)(b >> 5) * X3_IMG_B + x3_kc_off(c >> 3) + 16 * (b & 31) + 2 * (c & 7);
-                *(bf16*)p = h;
-                *(bf16*)(p + X3_PLANE_B) = l;
-            }
+            lx3_img_put(img, b, c, h, l);
         }
     }
     if (c == 0) {
@@ -133,7 +144,6 @@ static inline LbfArgs lbf_args_of(const Lx3Args& x, int n_train, int n_ex) {
     return a;
 }
 
-#define FB 32                      // items per streamed block
 #define PCS_ROW (LDR * 2 / 16)     // 16-byte pieces per shadow row (21)
 #define PCS_BLK (FB * PCS_ROW)     // pieces per block (672)
 #define PPT 3                      // pieces per thread per block (256*3 >= 672)
@@ -159,25 +169,68 @@ static inline LbfArgs lbf_args_of(const Lx3Args& x, int n_train, int n_ex) {
         }                                                                                                \
     }
 
-// Teacher readout of 128 KD rows over one item range:  O2[b,:] = sum_j softmax(teacher_b)_j * E_j  (j < Np), accumulated on the
-// matrix cores exactly like the softmax-weighted readout of the forward (probabilities as the A operand, the table block read
-// k-major from LDS).  With it the distillation term needs no second softmax pass:  sum_j pt_j * s_j = rep . O2  and
-// dRep = w (O1/l - O2)  (ADER.py:135-137).  Partials go to pO2 [range][kd row][HP].
-__device__ __forceinline__ void lbf_teacher_readout(const LbfArgs& a, bf16* E_l, int range, int b0, int blk_begin, int nb_blocks,
-                                                    int Np) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int r = lane & 31, hh = lane >> 5;
-    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
-    f32x16 O[5];
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
-    const int tr = a.trow[b0 + r];
-    const float tl2 = a.tlse2[b0 + r];
-    const float* trp = a.teacher + (size_t)(tr < 0 ? 0 : tr) * a.ldt;
+// ---- the pieces of the flash forward (flash_walk.h) that the row layout [FB][LDR] of this file's LDS blocks shapes: stated once for
+// k_lbf_fwd, its teacher readout and both forms of k_lx3_fwd.  Macros over the kernel's locals, as flash_walk.h's.
+// The ring walk over a range's blocks: LOAD_ (global -> ring slot) and STORE_ (ring slot -> LDS buffer `cur`) are LBF_LOAD / LBF_STORE
+// at depth RD or LX3_LOAD / LX3_STORE at depth XRING.  RING_PRIME requests the first blocks.  Between RING_WALK_BEGIN and
+// RING_WALK_END stands the kernel's per-block body with i (block of the range), blk, i0 (its first item) and cur in scope: block i is
+// on its way into LDS buffer cur and block i + depth_ requested; the body places its own loads ahead (teacher logits) in front of the
+// __syncthreads() behind which it reads the block
+#define RING_PRIME(depth_, LOAD_)                                                                        \
+    _Pragma("unroll") for (int s_ = 0; s_ < (depth_); ++s_) if (s_ < nb_blocks) LOAD_(s_, blk_begin + s_);
+#define RING_WALK_BEGIN(depth_, LOAD_, STORE_)                                                           \
+    int cur = 0, i = 0;                                                                                  \
+    while (i < nb_blocks) {                                                                              \
+        _Pragma("unroll") for (int s_ = 0; s_ < (depth_); ++s_) {                                        \
+            if (i >= nb_blocks) break;                  /* workgroup-uniform */                          \
+            const int blk = blk_begin + i;                                                               \
+            const int i0 = blk * FB;                                                                     \
+            STORE_(s_, cur);                                                                             \
+            if (i + (depth_) < nb_blocks) LOAD_(s_, blk + (depth_));
+#define RING_WALK_END()                                                                                  \
+            cur ^= 1;                                                                                    \
+            ++i;                                                                                         \
+        }                                                                                                \
+    }
+// O += P^T . E of a row block, read k-major (items on k) by ds_read_b64_tr_b16.  LDR_T_OFF: the lane's place in a transposed read (item
+// 4 hh + q4, channels 16 g1 + 4 p4.. of a 32-channel block).  LDR_TREAD: the B operands v0_ (items 0..15) and v1_ (16..31) of the
+// 32-channel block at base_.  LBF_READOUT: bf16 grade, P = pa0 / pa1 on the block at Eb_ (10 MFMAs).  LX3_READOUT: x3 grade on the
+// planes at Eh_ (hi) and Eh_ + FB * LDR (lo): P hi and P lo (pl0 / pl1) on the hi plane, P hi on the lo plane (30 MFMAs)
+#define LDR_T_OFF() const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
+#define LDR_TREAD(v0_, v1_, base_)                                                                       \
+            bf16x8 v0_, v1_;                                                                             \
+            {                                                                                            \
+                const bf16x4 l0 = tr_read(base_), h0 = tr_read((base_) + 8 * LDR);                       \
+                const bf16x4 l1 = tr_read((base_) + 16 * LDR), h1 = tr_read((base_) + 24 * LDR);         \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) { v0_[j] = l0[j]; v0_[4 + j] = h0[j]; v1_[j] = l1[j]; v1_[4 + j] = h1[j]; } \
+            }
+#define LBF_READOUT(Eb_)                                                                                 \
+        _Pragma("unroll") for (int nb = 0; nb < 5; ++nb) {                                               \
+            const bf16* base = (Eb_) + (4 * hh + q4) * LDR + 32 * nb + 16 * g1 + 4 * p4;                 \
+            LDR_TREAD(b0v, b1v, base)                                                                    \
+            O[nb] = mfma_bf16(pa0, b0v, O[nb]);                                                          \
+            O[nb] = mfma_bf16(pa1, b1v, O[nb]);                                                          \
+        }
+#define LX3_READOUT(Eh_)                                                                                 \
+        _Pragma("unroll") for (int nb = 0; nb < 5; ++nb) {                                               \
+            const bf16* base = (Eh_) + (4 * hh + q4) * LDR + 32 * nb + 16 * g1 + 4 * p4;                 \
+            LDR_TREAD(b0v, b1v, base)                                                                    \
+            O[nb] = mfma_bf16(pa0, b0v, O[nb]);                                                          \
+            O[nb] = mfma_bf16(pa1, b1v, O[nb]);                                                          \
+            O[nb] = mfma_bf16(pl0, b0v, O[nb]);                                                          \
+            O[nb] = mfma_bf16(pl1, b1v, O[nb]);                                                          \
+            LDR_TREAD(c0v, c1v, base + FB * LDR)                                                         \
+            O[nb] = mfma_bf16(pa0, c0v, O[nb]);                                                          \
+            O[nb] = mfma_bf16(pa1, c1v, O[nb]);                                                          \
+        }
+// The teacher of 32 distilled rows b_.. (lane: row b_ + r32): its row tr (-1: padding), the row's log2-domain log-sum-exp tl2 and its
+// logits trp.  LBF_TLOAD: the logits of the lane's 16 items of block blk_ (4 runs of 4 consecutive items; reg j = item i0 +
+// acc_row(j, hh)).  LBF_TPROBS: S = softmax(teacher) of block i0 from the logits tc, zero beyond the Np columns
+#define LBF_TEACHER_ROW(b_)                                                                              \
+    const int tr = a.trow[(b_) + r32];                                                                   \
+    const float tl2 = a.tlse2[(b_) + r32];                                                               \
+    const float* trp = a.teacher + (size_t)(tr < 0 ? 0 : tr) * a.ldt;                                    \
     const bool vec = ((a.ldt & 3) == 0) && (((uintptr_t)a.teacher & 15) == 0);
-    // teacher logits of this lane's batch row for its 16 items of a block (4 runs of 4 consecutive items)
 #define LBF_TLOAD(t_, blk_)                                                                              \
     _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                      \
         const int it = (blk_) * FB + 8 * g + 4 * hh;                                                     \
@@ -188,60 +241,46 @@ __device__ __forceinline__ void lbf_teacher_readout(const LbfArgs& a, bf16* E_l,
             _Pragma("unroll") for (int k = 0; k < 4; ++k) t_[4 * g + k] = (it + k < Np) ? trp[it + k] : -INFINITY; \
         }                                                                                                \
     }
+#define LBF_TPROBS()                                                                                     \
+            f32x16 S;                                                                                    \
+            _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                             \
+                const float x = (tr >= 0) ? __builtin_amdgcn_exp2f(fmaf(tc[j], LOG2E, -tl2)) : 0.0f;     \
+                S[j] = (i0 + acc_row(j, hh) < Np) ? x : 0.0f;                                            \
+            }
+
+// Teacher readout of 128 KD rows over one item range:  O2[b,:] = sum_j softmax(teacher_b)_j * E_j  (j < Np), accumulated on the
+// matrix cores exactly like the softmax-weighted readout of the forward (probabilities as the A operand, the table block read
+// k-major from LDS).  With it the distillation term needs no second softmax pass:  sum_j pt_j * s_j = rep . O2  and
+// dRep = w (O1/l - O2)  (ADER.py:135-137).  Partials go to pO2 [range][kd row][HP].
+__device__ __forceinline__ void lbf_teacher_readout(const LbfArgs& a, bf16* E_l, int range, int b0, int blk_begin, int nb_blocks,
+                                                    int Np) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int r32 = lane & 31, hh = lane >> 5;
+    LDR_T_OFF()
+    FW_O_ZERO()
+    LBF_TEACHER_ROW(b0)
     uint4 ring[RD][PPT];
     float tc[16], tn[16];
-#pragma unroll
-    for (int s_ = 0; s_ < RD; ++s_) if (s_ < nb_blocks) LBF_LOAD(s_, blk_begin + s_);
+    RING_PRIME(RD, LBF_LOAD)
     if (nb_blocks > 0) LBF_TLOAD(tc, blk_begin);
-    int cur = 0, i = 0;
-    while (i < nb_blocks) {
-#pragma unroll
-        for (int s_ = 0; s_ < RD; ++s_) {
-            if (i >= nb_blocks) break;                  // workgroup-uniform
-            const int blk = blk_begin + i;
-            const int i0 = blk * FB;
-            LBF_STORE(s_, cur);
-            if (i + RD < nb_blocks) LBF_LOAD(s_, blk + RD);
+    RING_WALK_BEGIN(RD, LBF_LOAD, LBF_STORE)
             if (i + 1 < nb_blocks) { LBF_TLOAD(tn, blk + 1); }
             __syncthreads();
             const bf16* Eb = E_l + cur * FB * LDR;
-            f32x16 S;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                // reg j of lane (r, hh) = item i0 + acc_row(j, hh) = i0 + 8 (j >> 2) + 4 hh + (j & 3): tc[] is in that order
-                const float x = (tr >= 0) ? __builtin_amdgcn_exp2f(fmaf(tc[j], LOG2E, -tl2)) : 0.0f;
-                S[j] = (i0 + acc_row(j, hh) < Np) ? x : 0.0f;
-            }
-            const bf16x8 pa0 = pack8(S, 0), pa1 = pack8(S, 1);
-#pragma unroll
-            for (int nb = 0; nb < 5; ++nb) {
-                const bf16* base = Eb + (4 * hh + q4) * LDR + 32 * nb + 16 * g1 + 4 * p4;
-                const bf16x4 l0 = tr_read(base), h0 = tr_read(base + 8 * LDR);
-                const bf16x4 l1 = tr_read(base + 16 * LDR), h1 = tr_read(base + 24 * LDR);
-                bf16x8 b0v, b1v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { b0v[j] = l0[j]; b0v[4 + j] = h0[j]; b1v[j] = l1[j]; b1v[4 + j] = h1[j]; }
-                O[nb] = mfma_bf16(pa0, b0v, O[nb]);
-                O[nb] = mfma_bf16(pa1, b1v, O[nb]);
-            }
+            LBF_TPROBS()
+            FW_PPACK()
+            LBF_READOUT(Eb)
 #pragma unroll
             for (int j = 0; j < 16; ++j) tc[j] = tn[j];
-            cur ^= 1;
-            ++i;
-        }
-    }
-    float* o = a.pO2 + ((size_t)range * (a.Bp - a.kd_row0) + (b0 - a.kd_row0)) * HP;
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r] = O[nb][j];
+    RING_WALK_END()
+    FW_STORE_O(a.pO2 + ((size_t)range * (a.Bp - a.kd_row0) + (b0 - a.kd_row0)) * HP)
 }
 
 __global__ __launch_bounds__(256, 2) void k_lbf_fwd(LbfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16* E_l = (bf16*)smem_raw;                       // [2][FB][LDR]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hh = lane >> 5;
+    const int r32 = lane & 31, hh = lane >> 5;
     // chunks: Bp/128 softmax chunks, then one TEACHER-READOUT chunk per 128 KD rows (same item ranges, same XCD grouping, so
     // the table blocks they stream are shared through L2)
     // The readout chunks come after all softmax workgroups and have their OWN, finer partition of the item blocks (ranges2 >=
@@ -257,102 +296,85 @@ __global__ __launch_bounds__(256, 2) void k_lbf_fwd(LbfArgs a) {
     int bc = readout ? (a.kd_row0 >> 7) + slot % nkd : slot % nsm;
     if (range >= nranges) return;
     const int N = (bc * 128 >= a.kd_row0) ? a.Np : a.N;              // columns of this chunk's softmax
-    const int nblk_all = (a.N + FB - 1) / FB;                         // ranges partition the blocks of the whole catalog
-    const int per = (nblk_all + nranges - 1) / nranges;
-    const int blk_begin = range * per, blk_end = min((N + FB - 1) / FB, blk_begin + per);
-    const int nb_blocks = max(0, blk_end - blk_begin);
+    FW_WG_SPAN(nranges, a.N, N)                                       // ranges partition the blocks of the whole catalog
     const int b0 = bc * 128 + wave * 32;
     if (readout) { lbf_teacher_readout(a, E_l, range, b0, blk_begin, nb_blocks, N); return; }
     bf16x8 bfrag[10];
 #pragma unroll
-    for (int ks = 0; ks < 10; ++ks) bfrag[ks] = *(const bf16x8*)(a.rep_bf + (size_t)(b0 + r) * LDR + 16 * ks + 8 * hh);
-    f32x16 O[5];
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
+    for (int ks = 0; ks < 10; ++ks) bfrag[ks] = *(const bf16x8*)(a.rep_bf + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
+    FW_O_ZERO()
     float m_run = -INFINITY, l_run = 0.0f;
     uint4 ring[RD][PPT];
-#pragma unroll
-    for (int s_ = 0; s_ < RD; ++s_) if (s_ < nb_blocks) LBF_LOAD(s_, blk_begin + s_);
-    int cur = 0, i = 0;
-    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
-    while (i < nb_blocks) {
-#pragma unroll
-        for (int s_ = 0; s_ < RD; ++s_) {
-            if (i >= nb_blocks) break;                  // workgroup-uniform
-            const int blk = blk_begin + i;
-            LBF_STORE(s_, cur);
-            if (i + RD < nb_blocks) LBF_LOAD(s_, blk + RD);
+    RING_PRIME(RD, LBF_LOAD)
+    LDR_T_OFF()
+    RING_WALK_BEGIN(RD, LBF_LOAD, LBF_STORE)
             __syncthreads();
             const bf16* Eb = E_l + cur * FB * LDR;
-            const int i0 = blk * FB;
             f32x16 S;
 #pragma unroll
             for (int j = 0; j < 16; ++j) S[j] = 0.0f;
 #pragma unroll
             for (int ks = 0; ks < 10; ++ks) {
-                const bf16x8 af = *(const bf16x8*)(Eb + r * LDR + 16 * ks + 8 * hh);
+                const bf16x8 af = *(const bf16x8*)(Eb + r32 * LDR + 16 * ks + 8 * hh);
                 S = mfma_bf16(af, bfrag[ks], S);
             }
-            if (i0 + FB > N) {                          // tail block: items >= N are outside the softmax
-#pragma unroll
-                for (int j = 0; j < 16; ++j) if (i0 + acc_row(j, hh) >= N) S[j] = -INFINITY;
-            }
-            float tmax = S[0];
-#pragma unroll
-            for (int j = 1; j < 16; ++j) tmax = fmaxf(tmax, S[j]);
-            // the two half-waves of a lane pair (l, l+32) hold different items of the SAME batch row; m_run is kept equal in
-            // both, so the cross-half exchange is only needed on the (rare) rescale path
-            float t2 = tmax * LOG2E;
-            if (__any(t2 > m_run + RESCALE_THR)) {
-                t2 = fmaxf(t2, __shfl_xor(t2, 32, 64));
-                const float m_new = (t2 > m_run + RESCALE_THR) ? t2 : m_run;
-                const float alpha = (m_new == -INFINITY) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);
-                l_run *= alpha;
-                m_run = m_new;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const float ar = __shfl(alpha, acc_row(j, hh), 64);     // O rows are batch rows
-#pragma unroll
-                    for (int nb = 0; nb < 5; ++nb) O[nb][j] *= ar;
-                }
-            }
-            const float nm = -m_run;
-            float ls = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) { S[j] = __builtin_amdgcn_exp2f(fmaf(S[j], LOG2E, nm)); ls += S[j]; }
-            l_run += ls;
-            const bf16x8 pa0 = pack8(S, 0), pa1 = pack8(S, 1);
-#pragma unroll
-            for (int nb = 0; nb < 5; ++nb) {
-                const bf16* base = Eb + (4 * hh + q4) * LDR + 32 * nb + 16 * g1 + 4 * p4;
-                const bf16x4 l0 = tr_read(base), h0 = tr_read(base + 8 * LDR);
-                const bf16x4 l1 = tr_read(base + 16 * LDR), h1 = tr_read(base + 24 * LDR);
-                bf16x8 b0v, b1v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { b0v[j] = l0[j]; b0v[4 + j] = h0[j]; b1v[j] = l1[j]; b1v[4 + j] = h1[j]; }
-                O[nb] = mfma_bf16(pa0, b0v, O[nb]);
-                O[nb] = mfma_bf16(pa1, b1v, O[nb]);
-            }
-            cur ^= 1;
-            ++i;
-        }
-    }
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (hh == 0) {
-        a.pm[(size_t)range * a.Bp + b0 + r] = m_run;
-        a.pl[(size_t)range * a.Bp + b0 + r] = l_tot;
-    }
-    float* o = a.pO + ((size_t)range * a.Bp + b0) * HP;
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r] = O[nb][j];
+            FW_SOFTMAX_HEAD()
+            FW_EXP_SUM()
+            FW_PPACK()
+            LBF_READOUT(Eb)
+    RING_WALK_END()
+    FW_STORE_ML()
+    FW_STORE_O(a.pO + ((size_t)range * a.Bp + b0) * HP)
 }
 
+// ---- what the merge kernels share.  Functions where a kernel keeps its instruction stream with one, macros over its locals elsewhere.
+// A row without a loss term (padding): no loss, no gradient
+__device__ __forceinline__ void lbf_row_pad(int b, float* lse, float* off, float* rowloss) {
+    lse[b] = 0.0f; rowloss[b] = 0.0f; off[b] = -INFINITY;
+}
+// Row b's scalars from its log2-domain log-sum-exp lse2, weight w and target term s_tgt_: lse (natural log), the loss row
+// w (lse - s_tgt_) (has_loss_ false: 0) and the backward's exponent offset.  (A macro: as a function's argument has_loss_ is evaluated
+// in front of the division, which reorders k_lbf_combine's scalar epilogue.)
+#define LBF_ROW_OUT(s_tgt_, has_loss_)                                                                   \
+    {                                                                                                    \
+        const float z = lse2 / LOG2E;                                                                    \
+        lse[b] = z;                                                                                      \
+        rowloss[b] = (has_loss_) ? w * (z - (s_tgt_)) : 0.0f;                                            \
+        off[b] = (w > 0.0f) ? log2f(w) - lse2 : -INFINITY;                                               \
+    }
+// The merge of row b's range partials by a workgroup of 640 threads (macros over the kernel's locals a, b, tid and its LDS arrays sc,
+// red, sM: k_lbf_combine keeps its instruction stream only so).  LBF_RANGES_SCALE: M = max over the ranges of pm (log2 domain), sc[i] =
+// 2^(pm_i - M) (0 for empty ranges) and, in red[tid], this thread's share of L = sum_i pl_i sc[i], behind a barrier.  (How red[] is
+// summed is the kernel's: the summation order is behaviour, and the two kernels differ in it.)
+#define LBF_RANGES_SCALE()                                                                               \
+    float m = -INFINITY;                                                                                 \
+    for (int i = tid; i < R; i += 640) m = fmaxf(m, a.pm[(size_t)i * a.Bp + b]);                         \
+    red[tid] = m;                                                                                        \
+    __syncthreads();                                                                                     \
+    if (tid < 64) {                                                                                      \
+        float v = red[tid];                                                                              \
+        for (int k = tid + 64; k < 640; k += 64) v = fmaxf(v, red[k]);                                   \
+        v = wave_max(v);                                                                                 \
+        if (tid == 0) sM = v;                                                                            \
+    }                                                                                                    \
+    __syncthreads();                                                                                     \
+    const float M = sM;                                                                                  \
+    float l = 0.0f;                                                                                      \
+    for (int i = tid; i < R; i += 640) {                                                                 \
+        const float pm = a.pm[(size_t)i * a.Bp + b];                                                     \
+        const float s_ = (pm != -INFINITY) ? __builtin_amdgcn_exp2f(pm - M) : 0.0f;                      \
+        sc[i] = s_;                                                                                      \
+        l += a.pl[(size_t)i * a.Bp + b] * s_;                                                            \
+    }                                                                                                    \
+    red[tid] = l;                                                                                        \
+    __syncthreads();
+// LBF_RANGES_O: thread (g = tid / 160, h = tid % 160) adds to oh_ the scaled O partials of the ranges i = g mod 4 of channel h (fixed
+// order: deterministic); lbf_sum4: channel tid's four group sums, once they stand in red[]
+#define LBF_RANGES_O(oh_)                                                                                \
+        _Pragma("unroll 8") for (int i = g; i < R; i += 4) oh_ += a.pO[((size_t)i * a.Bp + b) * HP + h] * sc[i];
+__device__ __forceinline__ float lbf_sum4(const float* red, int tid) { return ((red[tid] + red[160 + tid]) + red[320 + tid]) + red[480 + tid]; }
+
 // One workgroup per batch row: merge range partials -> lse (natural log), loss row, dRep row, backward offset.
-// 640 threads: thread (g = tid/160, h = tid%160) sums ranges i = g mod 4 of channel h (fixed order: deterministic).
 // X3: the target logit and the target row come from the fp32 operands (emb1_f = table row of item 1, rep_f [B,H]).
 template <bool X3>
 __global__ __launch_bounds__(640) void k_lbf_combine(LbfArgs a, const int* __restrict__ lab, const float* __restrict__ wrow,
@@ -365,32 +387,12 @@ __global__ __launch_bounds__(640) void k_lbf_combine(LbfArgs a, const int* __res
     const int b = blockIdx.x, tid = threadIdx.x;
     const int R = a.ranges, H = a.H;
     const bool kd = b >= a.kd_row0;
-    if (kd ? (b - a.kd_row0 >= a.n_ex) : (b >= a.n_train)) {     // padding rows: no loss, no gradient
-        if (tid == 0) { lse[b] = 0.0f; rowloss[b] = 0.0f; off[b] = -INFINITY; }
+    if (kd ? (b - a.kd_row0 >= a.n_ex) : (b >= a.n_train)) {     // padding rows
+        if (tid == 0) lbf_row_pad(b, lse, off, rowloss);
         return;
     }
     const int bc_ = kd ? a.n_train + (b - a.kd_row0) : b;        // row of the compact [n_train + n_ex, H] tensors (rep_f, drep)
-    float m = -INFINITY;
-    for (int i = tid; i < R; i += 640) m = fmaxf(m, a.pm[(size_t)i * a.Bp + b]);
-    red[tid] = m;
-    __syncthreads();
-    if (tid < 64) {
-        float v = red[tid];
-        for (int k = tid + 64; k < 640; k += 64) v = fmaxf(v, red[k]);
-        v = wave_max(v);
-        if (tid == 0) sM = v;
-    }
-    __syncthreads();
-    const float M = sM;
-    float l = 0.0f;
-    for (int i = tid; i < R; i += 640) {
-        const float pm = a.pm[(size_t)i * a.Bp + b];
-        const float s_ = (pm != -INFINITY) ? __builtin_amdgcn_exp2f(pm - M) : 0.0f;
-        sc[i] = s_;
-        l += a.pl[(size_t)i * a.Bp + b] * s_;
-    }
-    red[tid] = l;
-    __syncthreads();
+    LBF_RANGES_SCALE()
     if (tid < 64) {                                  // fixed order: ten strided terms per lane, then the wave butterfly (a single thread
         float v = 0.0f;                              // walking the 640 partials was a quarter of this kernel on the shipped catalogs)
 #pragma unroll
@@ -406,8 +408,7 @@ __global__ __launch_bounds__(640) void k_lbf_combine(LbfArgs a, const int* __res
     const int g = tid / 160, h = tid - g * 160;
     float oh = 0.0f, o2 = 0.0f;
     if (h < H) {
-#pragma unroll 8
-        for (int i = g; i < R; i += 4) oh += a.pO[((size_t)i * a.Bp + b) * HP + h] * sc[i];
+        LBF_RANGES_O(oh)
         if (kd) {
             // distilled row: the teacher readout O2 = sum_j softmax(t)_j E_j, range partials summed like the student's (four
             // interleaved groups, fixed order; a single thread walking all ranges was 0.16 ms of dependent loads at 512 ranges)
@@ -422,10 +423,10 @@ __global__ __launch_bounds__(640) void k_lbf_combine(LbfArgs a, const int* __res
     __syncthreads();
     float part = 0.0f, et = 0.0f;
     if (tid < H) {
-        oh = ((red[tid] + red[160 + tid]) + red[320 + tid]) + red[480 + tid];
+        oh = lbf_sum4(red, tid);
         if (kd) {
             // the target "row" of a distilled row is O2, and  sum_j pt_j s_j = rep . O2  with the operands the MFMA path multiplied
-            et = ((red2[tid] + red2[160 + tid]) + red2[320 + tid]) + red2[480 + tid];
+            et = lbf_sum4(red2, tid);
             part = (X3 ? rep_f[(size_t)bc_ * H + tid] : (float)a.rep_bf[(size_t)b * LDR + tid]) * et;
         } else if (t >= 0) {                         // target logit with the same bf16-rounded operands as the MFMA path
             if (X3) { et = emb1_f[(size_t)t * H + tid]; part = rep_f[(size_t)bc_ * H + tid] * et; }
@@ -468,10 +469,7 @@ __global__ __launch_bounds__(640) void k_lbf_combine(LbfArgs a, const int* __res
         float s_lab = (red[tid] + red[tid + 64]) + red[tid + 128];      // (H <= 160: three terms per lane, fixed order)
         s_lab = wave_sum(s_lab);
         if (tid != 0) return;
-        const float z = lse2 / LOG2E;
-        lse[b] = z;
-        rowloss[b] = (t >= 0 || kd) ? w * (z - s_lab) : 0.0f;
-        off[b] = (w > 0.0f) ? log2f(w) - lse2 : -INFINITY;
+        LBF_ROW_OUT(s_lab, t >= 0 || kd)
     }
 }
 
@@ -485,28 +483,8 @@ __global__ __launch_bounds__(640) void k_lbf_combine_partial(LbfArgs a, float* _
     __shared__ float sM;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int R = a.ranges, H = a.H;
-    float m = -INFINITY;
-    for (int i = tid; i < R; i += 640) m = fmaxf(m, a.pm[(size_t)i * a.Bp + b]);
-    red[tid] = m;
-    __syncthreads();
-    if (tid < 64) {
-        float v = red[tid];
-        for (int k = tid + 64; k < 640; k += 64) v = fmaxf(v, red[k]);
-        v = wave_max(v);
-        if (tid == 0) sM = v;
-    }
-    __syncthreads();
-    const float M = sM;
-    float l = 0.0f;
-    for (int i = tid; i < R; i += 640) {
-        const float pm = a.pm[(size_t)i * a.Bp + b];
-        const float s_ = (pm != -INFINITY) ? __builtin_amdgcn_exp2f(pm - M) : 0.0f;
-        sc[i] = s_;
-        l += a.pl[(size_t)i * a.Bp + b] * s_;
-    }
-    red[tid] = l;
-    __syncthreads();
-    if (tid == 0) {
+    LBF_RANGES_SCALE()
+    if (tid == 0) {                                  // (one thread walks the 640 terms: another order than k_lbf_combine's, and it stays)
         float v = 0.0f;
         for (int k = 0; k < 640; ++k) v += red[k];
         part[(size_t)b * PART_LD + 0] = M;
@@ -514,15 +492,30 @@ __global__ __launch_bounds__(640) void k_lbf_combine_partial(LbfArgs a, float* _
     }
     const int g = tid / 160, h = tid - g * 160;
     float oh = 0.0f;
-    if (h < H) {
-#pragma unroll 8
-        for (int i = g; i < R; i += 4) oh += a.pO[((size_t)i * a.Bp + b) * HP + h] * sc[i];
-    }
+    if (h < H) { LBF_RANGES_O(oh) }
     __syncthreads();
     red[tid] = oh;
     __syncthreads();
-    if (tid < H) part[(size_t)b * PART_LD + 2 + tid] = ((red[tid] + red[160 + tid]) + red[320 + tid]) + red[480 + tid];
+    if (tid < H) part[(size_t)b * PART_LD + 2 + tid] = lbf_sum4(red, tid);
 }
+
+// The merge of row b's rank partials by one wave (lane: channels c = lane, lane + 64, lane + 128), shared by the cross-rank merges
+// below: over parts_ [W][Bp_][PART_LD] in rank order (fixed: deterministic) L = sum_i L_i 2^(M_i - M) and, into the kernel's zeroed
+// o[3], O likewise, as the range merge forms them, and the row's log2-domain log-sum-exp lse2.  more_: what the kernel adds per (rank
+// i, channel c, register k) -- the distilled form its plain sum o2 of the teacher readout's partials.  (A macro, and o[] the
+// kernel's own declaration: as a function, or with o[] declared here, the two kernels take other registers.)
+#define LBF_MERGE_RANKS(parts_, Bp_, more_)                                                              \
+    float M = -INFINITY;                                                                                 \
+    for (int i = 0; i < W; ++i) M = fmaxf(M, (parts_)[((size_t)i * (Bp_) + b) * PART_LD]);               \
+    float L = 0.0f;                                                                                      \
+    for (int i = 0; i < W; ++i) {                                                                        \
+        const float* pr = (parts_) + ((size_t)i * (Bp_) + b) * PART_LD;                                  \
+        const float m = pr[0];                                                                           \
+        const float sc = (m != -INFINITY) ? __builtin_amdgcn_exp2f(m - M) : 0.0f;                        \
+        L += pr[1] * sc;                                                                                 \
+        _Pragma("unroll") for (int k = 0; k < 3; ++k) { const int c = lane + 64 * k; if (c < H) { o[k] += pr[2 + c] * sc; more_; } } \
+    }                                                                                                    \
+    const float lse2 = M + log2f(L);
 
 // Cross-rank merge for one batch row of THIS rank: parts [W][Bp][PART_LD] (slice i = the partials rank i computed over its
 // items) -> lse (natural log), backward offset, loss row, dRep row.  e_lab: fp32 table row of the label (fetched from its
@@ -538,21 +531,11 @@ __global__ __launch_bounds__(256) void k_lbf_merge_parts(const float* __restrict
     const int b = blockIdx.x * 4 + wave;
     if (b >= Bp) return;
     if (b >= B) {
-        if (lane == 0) { lse[b] = 0.0f; rowloss[b] = 0.0f; off[b] = -INFINITY; }
+        if (lane == 0) lbf_row_pad(b, lse, off, rowloss);
         return;
     }
-    float M = -INFINITY;
-    for (int i = 0; i < W; ++i) M = fmaxf(M, parts[((size_t)i * Bp + b) * PART_LD]);
-    float L = 0.0f, o[3] = {0.0f, 0.0f, 0.0f};
-    for (int i = 0; i < W; ++i) {                                   // fixed order: deterministic
-        const float* pr = parts + ((size_t)i * Bp + b) * PART_LD;
-        const float m = pr[0];
-        const float sc = (m != -INFINITY) ? __builtin_amdgcn_exp2f(m - M) : 0.0f;
-        L += pr[1] * sc;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const int c = lane + 64 * k; if (c < H) o[k] += pr[2 + c] * sc; }
-    }
-    const float lse2 = M + log2f(L);
+    float o[3] = {0.0f, 0.0f, 0.0f};
+    LBF_MERGE_RANKS(parts, Bp, (void)0)
     const float w = wrow[b];
     float dot = 0.0f;
 #pragma unroll
@@ -565,12 +548,7 @@ __global__ __launch_bounds__(256) void k_lbf_merge_parts(const float* __restrict
         }
     }
     dot = wave_sum(dot);
-    if (lane == 0) {
-        const float z = lse2 / LOG2E;
-        lse[b] = z;
-        rowloss[b] = w * (z - dot);
-        off[b] = (w > 0.0f) ? log2f(w) - lse2 : -INFINITY;
-    }
+    if (lane == 0) LBF_ROW_OUT(dot, true)
 }
 
 __global__ __launch_bounds__(256) void k_lbf_sum(const float* __restrict__ x, int n, float* __restrict__ out) {
@@ -599,11 +577,7 @@ __global__ __launch_bounds__(256) void k_lx3_prep(const float* __restrict__ rep,
     const bf16 h = (bf16)x, l = (bf16)(x - (float)h);
     rep_hi[i] = h;
     rep_lo[i] = l;
-    if (img && c < HP) {
-        char* p = img + (size_t)(b >> 5) * X3_IMG_B + x3_kc_off(c >> 3) + 16 * (b & 31) + 2 * (c & 7);
-        *(bf16*)p = h;
-        *(bf16*)(p + X3_PLANE_B) = l;
-    }
+    lx3_img_put(img, b, c, h, l);
 }
 
 
@@ -616,39 +590,27 @@ __global__ __launch_bounds__(256, 2) void k_lx3_fwd(Lx3Args a) {
     typedef float f32x4_t __attribute__((ext_vector_type(4)));
     typedef float f32x2_t __attribute__((ext_vector_type(2)));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hh = lane >> 5;
+    const int r32 = lane & 31, hh = lane >> 5;
     // READOUT = false: the Bp/128 softmax chunks; READOUT = true (own launch: its registers would otherwise push the softmax path
     // into spills): one teacher-readout chunk per 128 KD rows, O2 = sum_j softmax(teacher)_j E_j as in lbf_teacher_readout
-    const int nchunk = READOUT ? (a.Bp - a.kd_row0) >> 7 : a.Bp >> 7;
     const int nranges = READOUT ? a.ranges2 : a.ranges;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int range = xcd + 8 * (slot / nchunk);
-    int bc = slot % nchunk;
-    if (range >= nranges) return;
-    constexpr bool readout = READOUT;
-    if (readout) bc += a.kd_row0 >> 7;
+    FW_XCD_MAP(nranges, READOUT ? (a.Bp - a.kd_row0) >> 7 : a.Bp >> 7)
+    const int bcr = READOUT ? bc + (a.kd_row0 >> 7) : bc;             // 128-row chunk of the padded batch
     const int H = a.H;
-    const int N = (bc * 128 >= a.kd_row0) ? a.Np : a.N;              // columns of this chunk's softmax
-    const int nblk_all = ((READOUT ? N : a.N) + FB - 1) / FB;          // (the readout partitions only the Np columns it reads)
-    const int per = (nblk_all + nranges - 1) / nranges;
-    const int blk_begin = range * per, blk_end = min((N + FB - 1) / FB, blk_begin + per);
-    const int nb_blocks = max(0, blk_end - blk_begin);
-    const int b0 = bc * 128 + wave * 32;
+    const int N = (bcr * 128 >= a.kd_row0) ? a.Np : a.N;             // columns of this chunk's softmax
+    FW_WG_SPAN(nranges, READOUT ? N : a.N, N)                         // (the readout partitions only the Np columns it reads)
+    const int b0 = bcr * 128 + wave * 32;
     // K padding (columns >= H) of both planes of both buffers stays zero: the block stores never touch it
     for (int i = tid; i < 2 * 2 * FB * LDR / 8; i += 256) ((uint4*)E_l)[i] = make_uint4(0u, 0u, 0u, 0u);
     bf16x8 bh_[10], bl_[10];
-    if (!readout) {
+    if (!READOUT) {
 #pragma unroll
         for (int ks = 0; ks < 10; ++ks) {
-            bh_[ks] = *(const bf16x8*)(a.rep_hi + (size_t)(b0 + r) * LDR + 16 * ks + 8 * hh);
-            bl_[ks] = *(const bf16x8*)(a.rep_lo + (size_t)(b0 + r) * LDR + 16 * ks + 8 * hh);
+            bh_[ks] = *(const bf16x8*)(a.rep_hi + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
+            bl_[ks] = *(const bf16x8*)(a.rep_lo + (size_t)(b0 + r32) * LDR + 16 * ks + 8 * hh);
         }
     }
-    f32x16 O[5];
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
+    FW_O_ZERO()
     float m_run = -INFINITY, l_run = 0.0f;
     // A block = FB consecutive table rows = one flat run of FB*H floats whose 16-byte phase is the table's (H even): vector j
     // of thread t covers floats e = head + 4 t + 1024 j; its LDS position (row, col) does not depend on the block
@@ -696,181 +658,73 @@ __global__ __launch_bounds__(256, 2) void k_lx3_fwd(Lx3Args a) {
         }                                                                                                \
         if (head && tid == 0) LX3_PUT2(dst_, 0, ringh[slot_][0], ringh[slot_][1]);                       \
     }
-    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
+    LDR_T_OFF()
     if constexpr (READOUT) {
         // teacher readout of 128 KD rows (see lbf_teacher_readout): O2 += PT^T . E with PT = softmax(teacher) split hi/lo
-        const int tr = a.trow[b0 + r];
-        const float tl2 = a.tlse2[b0 + r];
-        const float* trp = a.teacher + (size_t)(tr < 0 ? 0 : tr) * a.ldt;
-        const bool vec = ((a.ldt & 3) == 0) && (((uintptr_t)a.teacher & 15) == 0);
+        LBF_TEACHER_ROW(b0)
         const int Np = N;
         float tc[16], tn[16];
-#pragma unroll
-        for (int s_ = 0; s_ < XRING; ++s_) if (s_ < nb_blocks) LX3_LOAD(s_, blk_begin + s_);
+        RING_PRIME(XRING, LX3_LOAD)
         if (nb_blocks > 0) LBF_TLOAD(tc, blk_begin);
-        __syncthreads();
-        int cur = 0, i = 0;
-        while (i < nb_blocks) {
-#pragma unroll
-            for (int s_ = 0; s_ < XRING; ++s_) {
-                if (i >= nb_blocks) break;
-                const int blk = blk_begin + i;
-                const int i0 = blk * FB;
-                LX3_STORE(s_, cur);
-                if (i + XRING < nb_blocks) LX3_LOAD(s_, blk + XRING);
+        __syncthreads();                                // zero fill done before the first block store
+        RING_WALK_BEGIN(XRING, LX3_LOAD, LX3_STORE)
                 if (i + 1 < nb_blocks) { LBF_TLOAD(tn, blk + 1); }
                 __syncthreads();
                 const bf16* Eh = E_l + cur * 2 * FB * LDR;
-                f32x16 S;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const float x = (tr >= 0) ? __builtin_amdgcn_exp2f(fmaf(tc[j], LOG2E, -tl2)) : 0.0f;
-                    S[j] = (i0 + acc_row(j, hh) < Np) ? x : 0.0f;
-                }
-                const bf16x8 pa0 = pack8(S, 0), pa1 = pack8(S, 1);
-                bf16x8 pl0, pl1;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { pl0[j] = (bf16)(S[j] - (float)pa0[j]); pl1[j] = (bf16)(S[8 + j] - (float)pa1[j]); }
-#pragma unroll
-                for (int nb = 0; nb < 5; ++nb) {
-                    const bf16* base = Eh + (4 * hh + q4) * LDR + 32 * nb + 16 * g1 + 4 * p4;
-                    const bf16x4 l0 = tr_read(base), h0 = tr_read(base + 8 * LDR);
-                    const bf16x4 l1 = tr_read(base + 16 * LDR), h1 = tr_read(base + 24 * LDR);
-                    bf16x8 b0v, b1v;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { b0v[j] = l0[j]; b0v[4 + j] = h0[j]; b1v[j] = l1[j]; b1v[4 + j] = h1[j]; }
-                    O[nb] = mfma_bf16(pa0, b0v, O[nb]);
-                    O[nb] = mfma_bf16(pa1, b1v, O[nb]);
-                    O[nb] = mfma_bf16(pl0, b0v, O[nb]);
-                    O[nb] = mfma_bf16(pl1, b1v, O[nb]);
-                    const bf16* bl = base + FB * LDR;
-                    const bf16x4 m0 = tr_read(bl), n0 = tr_read(bl + 8 * LDR);
-                    const bf16x4 m1 = tr_read(bl + 16 * LDR), n1 = tr_read(bl + 24 * LDR);
-                    bf16x8 c0v, c1v;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { c0v[j] = m0[j]; c0v[4 + j] = n0[j]; c1v[j] = m1[j]; c1v[4 + j] = n1[j]; }
-                    O[nb] = mfma_bf16(pa0, c0v, O[nb]);
-                    O[nb] = mfma_bf16(pa1, c1v, O[nb]);
-                }
+                LBF_TPROBS()
+                FW_PSPLIT()
+                LX3_READOUT(Eh)
 #pragma unroll
                 for (int j = 0; j < 16; ++j) tc[j] = tn[j];
-                cur ^= 1;
-                ++i;
-            }
-        }
-        float* o2 = a.pO2 + ((size_t)range * (a.Bp - a.kd_row0) + (b0 - a.kd_row0)) * HP;
-#pragma unroll
-        for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) o2[(size_t)acc_row(j, hh) * HP + 32 * nb + r] = O[nb][j];
-        return;
-    }
-    else {
-#pragma unroll
-    for (int s_ = 0; s_ < XRING; ++s_) if (s_ < nb_blocks) LX3_LOAD(s_, blk_begin + s_);
-    __syncthreads();                                    // zero fill done before the first block store
-    int cur = 0, i = 0;
-    while (i < nb_blocks) {
-#pragma unroll
-        for (int s_ = 0; s_ < XRING; ++s_) {
-            if (i >= nb_blocks) break;                  // workgroup-uniform
-            const int blk = blk_begin + i;
-            LX3_STORE(s_, cur);
-            if (i + XRING < nb_blocks) LX3_LOAD(s_, blk + XRING);
+        RING_WALK_END()
+        FW_STORE_O(a.pO2 + ((size_t)range * (a.Bp - a.kd_row0) + (b0 - a.kd_row0)) * HP)
+    } else {
+        RING_PRIME(XRING, LX3_LOAD)
+        __syncthreads();                                // zero fill done before the first block store
+        RING_WALK_BEGIN(XRING, LX3_LOAD, LX3_STORE)
             __syncthreads();
             const bf16* Eh = E_l + cur * 2 * FB * LDR;
             const bf16* El = Eh + FB * LDR;
-            const int i0 = blk * FB;
             f32x16 S;
 #pragma unroll
             for (int j = 0; j < 16; ++j) S[j] = 0.0f;
 #pragma unroll
             for (int ks = 0; ks < 10; ++ks) {
-                const bf16x8 ah = *(const bf16x8*)(Eh + r * LDR + 16 * ks + 8 * hh);
-                const bf16x8 al = *(const bf16x8*)(El + r * LDR + 16 * ks + 8 * hh);
+                const bf16x8 ah = *(const bf16x8*)(Eh + r32 * LDR + 16 * ks + 8 * hh);
+                const bf16x8 al = *(const bf16x8*)(El + r32 * LDR + 16 * ks + 8 * hh);
                 S = mfma_bf16(ah, bh_[ks], S);
                 S = mfma_bf16(al, bh_[ks], S);
                 S = mfma_bf16(ah, bl_[ks], S);
             }
-            if (i0 + FB > N) {                          // tail block: items >= N are outside the softmax
-#pragma unroll
-                for (int j = 0; j < 16; ++j) if (i0 + acc_row(j, hh) >= N) S[j] = -INFINITY;
-            }
-            float tmax = S[0];
-#pragma unroll
-            for (int j = 1; j < 16; ++j) tmax = fmaxf(tmax, S[j]);
-            float t2 = tmax * LOG2E;
-            if (__any(t2 > m_run + RESCALE_THR)) {
-                t2 = fmaxf(t2, __shfl_xor(t2, 32, 64));
-                const float m_new = (t2 > m_run + RESCALE_THR) ? t2 : m_run;
-                const float alpha = (m_new == -INFINITY) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);
-                l_run *= alpha;
-                m_run = m_new;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const float ar = __shfl(alpha, acc_row(j, hh), 64);     // O rows are batch rows
-#pragma unroll
-                    for (int nb = 0; nb < 5; ++nb) O[nb][j] *= ar;
-                }
-            }
-            const float nm = -m_run;
-            float ls = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) { S[j] = __builtin_amdgcn_exp2f(fmaf(S[j], LOG2E, nm)); ls += S[j]; }
-            l_run += ls;
-            const bf16x8 pa0 = pack8(S, 0), pa1 = pack8(S, 1);
-            bf16x8 pl0, pl1;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { pl0[j] = (bf16)(S[j] - (float)pa0[j]); pl1[j] = (bf16)(S[8 + j] - (float)pa1[j]); }
-#pragma unroll
-            for (int nb = 0; nb < 5; ++nb) {
-                const bf16* base = Eh + (4 * hh + q4) * LDR + 32 * nb + 16 * g1 + 4 * p4;
-                const bf16x4 l0 = tr_read(base), h0 = tr_read(base + 8 * LDR);
-                const bf16x4 l1 = tr_read(base + 16 * LDR), h1 = tr_read(base + 24 * LDR);
-                bf16x8 b0v, b1v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { b0v[j] = l0[j]; b0v[4 + j] = h0[j]; b1v[j] = l1[j]; b1v[4 + j] = h1[j]; }
-                O[nb] = mfma_bf16(pa0, b0v, O[nb]);
-                O[nb] = mfma_bf16(pa1, b1v, O[nb]);
-                O[nb] = mfma_bf16(pl0, b0v, O[nb]);
-                O[nb] = mfma_bf16(pl1, b1v, O[nb]);
-                const bf16* bl = base + FB * LDR;
-                const bf16x4 m0 = tr_read(bl), n0 = tr_read(bl + 8 * LDR);
-                const bf16x4 m1 = tr_read(bl + 16 * LDR), n1 = tr_read(bl + 24 * LDR);
-                bf16x8 c0v, c1v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { c0v[j] = m0[j]; c0v[4 + j] = n0[j]; c1v[j] = m1[j]; c1v[4 + j] = n1[j]; }
-                O[nb] = mfma_bf16(pa0, c0v, O[nb]);
-                O[nb] = mfma_bf16(pa1, c1v, O[nb]);
-            }
-            cur ^= 1;
-            ++i;
-        }
-    }
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (hh == 0) {
-        a.pm[(size_t)range * a.Bp + b0 + r] = m_run;
-        a.pl[(size_t)range * a.Bp + b0 + r] = l_tot;
-    }
-    float* o = a.pO + ((size_t)range * a.Bp + b0) * HP;
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r] = O[nb][j];
+            FW_SOFTMAX_HEAD()
+            FW_EXP_SUM()
+            FW_PSPLIT()
+            LX3_READOUT(Eh)
+        RING_WALK_END()
+        FW_STORE_ML()
+        FW_STORE_O(a.pO + ((size_t)range * a.Bp + b0) * HP)
     }
 }
-
-// the x3 forwards of logits_x3.hip on conflict-free block images: k_lx3p (k_lx3g, 32x32x16, with the vector work inside the MFMA
-// phases; it launches k_lx3g itself for H != 150) and the teacher readout of distilled steps k_lx3r
-bool lx3f_supports(int H);
-int lx3p_launch(const Lx3Args& x, void* stream);
-// lx3r_supports: H = 150, 16-byte aligned teacher rows, at least one whole block
-bool lx3r_supports(const Lx3Args& x);
-int lx3r_launch(const Lx3Args& x, void* stream);
 
 // ============================================================================================= C ABI
 static const size_t kFwdLds = (size_t)2 * FB * LDR * sizeof(bf16);          // k_lbf_fwd: two buffers of one block
 static const size_t kLx3FwdLds = 2 * kFwdLds;                               // k_lx3_fwd: ... of two planes (hi, lo)
+
+// What every flash entry point asks of its shapes: whole 128-row chunks, an even H of 2..160, N items of the table; flash_kd_ok: the
+// padded row layout of a distilled step and its Np columns; x3_table_ok: an fp32 table whose rows the 8-byte loads can take
+static bool flash_shapes_ok(int Bp, int H, int N, int item_num) { return Bp % 128 == 0 && H <= HP && !(H & 1) && H >= 2 && N <= item_num; }
+static bool flash_kd_ok(int n_train, int n_ex, int kd_row0, int Bp, int N, int Np) {
+    return kd_row0 % 128 == 0 && n_train <= kd_row0 && kd_row0 + n_ex <= Bp && Np <= N && Np >= 1;
+}
+static bool x3_table_ok(const float* emb) { return !((uintptr_t)emb & 7); }
+// the launch of a prep kernel (one thread per element of the [Bp][LDR] operand rows), and of the closing sum of the loss rows
+template <class K, class... A>
+static void launch_prep(K kernel, int Bp, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, args...);
+}
+static void launch_sum(const float* rowloss, int n, float* loss, hipStream_t st) {
+    hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, n, loss);
+}
 
 // x3 forward of x.ranges item ranges x Bp / 128 chunks: the block-image kernels where they take H, else k_lx3_fwd
 static int lx3_forward(const Lx3Args& x, void* stream) {
@@ -888,9 +742,6 @@ static int lx3_readout(const Lx3Args& x, void* stream) {
 }
 
 extern "C" {
-
-int ader_lbf_ranges_kd(int N, int Bp, int kd_row0);
-int ader_lbf_readout_ranges(int N, int Bp, int kd_row0);
 
 // shadow [rows][168] bf16 <- emb [rows][H] fp32  (initialisation / checkpoint load; ader_adam_step keeps it in sync afterwards)
 int ader_lbf_shadow_refresh(const float* emb, void* shadow, size_t rows, int H, void* stream) {
@@ -921,47 +772,19 @@ int ader_lbf_fwd(const float* rep, const void* shadow, int item_num, int B, int 
                  void* rep_bf, float* pm, float* pl, float* pO, float* lse, float* off, float* rowloss, float* loss, float* drep,
                  void* stream) {
     if (B <= 0) return 0;
-    if (Bp % 128 != 0 || B > Bp || H > HP || (H & 1) || H < 2) return -2;
+    if (!flash_shapes_ok(Bp, H, N, item_num) || B > Bp) return -2;
     if (int e = ader_dyn_lds<k_lbf_fwd>(kFwdLds)) return e;
-    if (N > item_num) return -2;
     hipStream_t st = (hipStream_t)stream;
     const LbfArgs a = lbf_args((const bf16*)shadow + LDR, item_num, rep_bf, B, Bp, H, N, ader_lbf_ranges(N, Bp), pm, pl, pO);
-    hipLaunchKernelGGL(k_lbf_prep, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_bf, B, Bp, H);
+    launch_prep(k_lbf_prep, Bp, st, rep, (bf16*)rep_bf, B, Bp, H);
     hipLaunchKernelGGL(k_lbf_fwd, dim3(a.ranges * (Bp / 128)), dim3(256), kFwdLds, st, a);
     hipLaunchKernelGGL(k_lbf_combine<false>, dim3(Bp), dim3(640), 0, st, a, lab, wrow, lse, off, rowloss, drep, (const float*)nullptr,
                        (const float*)nullptr, AderLnfBwd{});
-    hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, B, loss);
+    launch_sum(rowloss, B, loss, st);
     HIP_LAUNCH_CHECK();
     return 0;
 }
 
-// Forward of a DISTILLED step (ADER.py:108-137) on the bf16 flash path: n_train one-hot rows (labels pos, weight w_train) and n_ex
-// exemplar rows distilled against softmax(teacher[ex_trow[e], :Np]) (weight w_ex = lambda / n_ex), student softmax over the first Np
-// items only.  rep is the compact [n_train + n_ex, H] tensor (exemplar rows last, main.py:229); inside, rows are laid out
-// [train rows padded to 128 | exemplar rows padded to 128] (Bp = both paddings; kd_row0 = first exemplar row): lab / wrow / trow /
-// tlse2 / lse / off / rowloss are [Bp] in THAT layout (they feed ader_tab_update_sh_kd), drep is compact.  tlse_all[r] = natural
-// log-sum-exp of teacher row r over [0, Np).  Scratch as ader_lbf_fwd plus pO2: ranges * (Bp - kd_row0) * 160 floats.
-int ader_lbf_fwd_kd(const float* rep, const void* shadow, int item_num, int n_train, int n_ex, int kd_row0, int Bp, int H, int N,
-                    int Np, const int* pos, const int* ex_trow, const float* teacher, long ldt, const float* tlse_all, float w_train,
-                    float w_ex, int* lab, float* wrow, int* trow, float* tlse2, void* rep_bf, float* pm, float* pl, float* pO,
-                    float* pO2, float* lse, float* off, float* rowloss, float* loss, float* drep, void* stream) {
-    if (n_train + n_ex <= 0) return 0;
-    if (Bp % 128 != 0 || kd_row0 % 128 != 0 || n_train > kd_row0 || kd_row0 + n_ex > Bp || H > HP || (H & 1) || H < 2 || N > item_num ||
-        Np > N || Np < 1) return -2;
-    if (int e = ader_dyn_lds<k_lbf_fwd>(kFwdLds)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    LbfArgs a = lbf_args((const bf16*)shadow + LDR, item_num, rep_bf, n_train + n_ex, Bp, H, N, ader_lbf_ranges_kd(N, Bp, kd_row0), pm, pl, pO);
-    lbf_args_kd(a, kd_row0, Np, n_train, n_ex, teacher, ldt, trow, tlse2, pO2, ader_lbf_readout_ranges(N, Bp, kd_row0));
-    const int nsm = Bp / 128, nkd = (Bp - kd_row0) / 128;
-    hipLaunchKernelGGL(k_lbf_prep_kd, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_bf, (bf16*)nullptr, n_train, n_ex,
-                       kd_row0, Bp, H, pos, ex_trow, tlse_all, w_train, w_ex, lab, wrow, trow, tlse2, (char*)nullptr);
-    hipLaunchKernelGGL(k_lbf_fwd, dim3(a.ranges * nsm + a.ranges2 * nkd), dim3(256), kFwdLds, st, a);
-    hipLaunchKernelGGL(k_lbf_combine<false>, dim3(Bp), dim3(640), 0, st, a, (const int*)lab, (const float*)wrow, lse, off, rowloss, drep,
-                       (const float*)nullptr, (const float*)nullptr, AderLnfBwd{});
-    hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, Bp, loss);
-    HIP_LAUNCH_CHECK();
-    return 0;
-}
 // ranges used by ader_lbf_fwd_kd (scratch sizing): pm / pl: R*Bp, pO: R*Bp*160 with R = ader_lbf_ranges_kd; pO2: R2*(Bp-kd_row0)*160
 // with R2 = ader_lbf_readout_ranges (the readout chunks take the workgroup slots the softmax chunks leave of the 512 resident ones)
 int ader_lbf_ranges_kd(int N, int Bp, int kd_row0) { return ader_lbf_ranges(N, (Bp / 128 + (Bp - kd_row0) / 128) * 128); }
@@ -976,11 +799,38 @@ int ader_lbf_readout_ranges(int N, int Bp, int kd_row0) {
     return r2 < R ? R : r2;
 }
 
+// Forward of a DISTILLED step (ADER.py:108-137) on the bf16 flash path: n_train one-hot rows (labels pos, weight w_train) and n_ex
+// exemplar rows distilled against softmax(teacher[ex_trow[e], :Np]) (weight w_ex = lambda / n_ex), student softmax over the first Np
+// items only.  rep is the compact [n_train + n_ex, H] tensor (exemplar rows last, main.py:229); inside, rows are laid out
+// [train rows padded to 128 | exemplar rows padded to 128] (Bp = both paddings; kd_row0 = first exemplar row): lab / wrow / trow /
+// tlse2 / lse / off / rowloss are [Bp] in THAT layout (they feed ader_tab_update_sh_kd), drep is compact.  tlse_all[r] = natural
+// log-sum-exp of teacher row r over [0, Np).  Scratch as ader_lbf_fwd plus pO2: ranges * (Bp - kd_row0) * 160 floats.
+int ader_lbf_fwd_kd(const float* rep, const void* shadow, int item_num, int n_train, int n_ex, int kd_row0, int Bp, int H, int N,
+                    int Np, const int* pos, const int* ex_trow, const float* teacher, long ldt, const float* tlse_all, float w_train,
+                    float w_ex, int* lab, float* wrow, int* trow, float* tlse2, void* rep_bf, float* pm, float* pl, float* pO,
+                    float* pO2, float* lse, float* off, float* rowloss, float* loss, float* drep, void* stream) {
+    if (n_train + n_ex <= 0) return 0;
+    if (!flash_shapes_ok(Bp, H, N, item_num) || !flash_kd_ok(n_train, n_ex, kd_row0, Bp, N, Np)) return -2;
+    if (int e = ader_dyn_lds<k_lbf_fwd>(kFwdLds)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    LbfArgs a = lbf_args((const bf16*)shadow + LDR, item_num, rep_bf, n_train + n_ex, Bp, H, N, ader_lbf_ranges_kd(N, Bp, kd_row0), pm, pl, pO);
+    lbf_args_kd(a, kd_row0, Np, n_train, n_ex, teacher, ldt, trow, tlse2, pO2, ader_lbf_readout_ranges(N, Bp, kd_row0));
+    const int nsm = Bp / 128, nkd = (Bp - kd_row0) / 128;
+    launch_prep(k_lbf_prep_kd, Bp, st, rep, (bf16*)rep_bf, nullptr, n_train, n_ex, kd_row0, Bp, H, pos, ex_trow, tlse_all, w_train, w_ex, lab,
+                wrow, trow, tlse2, nullptr);
+    hipLaunchKernelGGL(k_lbf_fwd, dim3(a.ranges * nsm + a.ranges2 * nkd), dim3(256), kFwdLds, st, a);
+    hipLaunchKernelGGL(k_lbf_combine<false>, dim3(Bp), dim3(640), 0, st, a, (const int*)lab, (const float*)wrow, lse, off, rowloss, drep,
+                       (const float*)nullptr, (const float*)nullptr, AderLnfBwd{});
+    launch_sum(rowloss, Bp, loss, st);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+
 // rep fp32 [B,H] -> rep_bf [Bp,168] bf16 (zero padded): the operand layout of the bf16 logit kernels
 int ader_lbf_prep(const float* rep, void* rep_bf, int B, int Bp, int H, void* stream) {
     if (Bp <= 0) return 0;
     if (B > Bp || H > HP) return -2;
-    hipLaunchKernelGGL(k_lbf_prep, dim3((Bp * LDR + 255) / 256), dim3(256), 0, (hipStream_t)stream, rep, (bf16*)rep_bf, B, Bp, H);
+    launch_prep(k_lbf_prep, Bp, (hipStream_t)stream, rep, (bf16*)rep_bf, B, Bp, H);
     HIP_LAUNCH_CHECK();
     return 0;
 }
@@ -991,7 +841,7 @@ int ader_lbf_prep(const float* rep, void* rep_bf, int B, int Bp, int H, void* st
 int ader_lbf_fwd_shard(const void* rep_bf, const void* shadow, int item_num, int Bp, int H, int N, int item_begin, int item_count,
                        float* pm, float* pl, float* pO, float* part, void* stream) {
     if (Bp <= 0) return 0;
-    if (Bp % 128 != 0 || H > HP || (H & 1) || H < 2 || N > item_num || item_begin < 0) return -2;
+    if (!flash_shapes_ok(Bp, H, N, item_num) || item_begin < 0) return -2;
     if (int e = ader_dyn_lds<k_lbf_fwd>(kFwdLds)) return e;
     hipStream_t st = (hipStream_t)stream;
     const int n_loc = shard_items(N, item_begin, item_count);
@@ -1012,7 +862,7 @@ int ader_lbf_merge_parts(const float* parts, int world, int Bp, int B, int H, co
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_lbf_merge_parts<false>, dim3((Bp + 3) / 4), dim3(256), 0, st, parts, world, Bp, B, H, e_lab,
                        (const bf16*)rep_bf, (const float*)nullptr, wrow, lse, off, rowloss, drep);
-    hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, B, loss);
+    launch_sum(rowloss, B, loss, st);
     HIP_LAUNCH_CHECK();
     return 0;
 }
@@ -1021,47 +871,30 @@ int ader_lbf_merge_parts(const float* parts, int world, int Bp, int B, int H, co
 int ader_lx3_prep(const float* rep, void* rep_hi, void* rep_lo, int B, int Bp, int H, void* stream) {
     if (Bp <= 0) return 0;
     if (B > Bp || H > HP) return -2;
-    hipLaunchKernelGGL(k_lx3_prep, dim3((Bp * LDR + 255) / 256), dim3(256), 0, (hipStream_t)stream, rep, (bf16*)rep_hi, (bf16*)rep_lo,
-                       B, Bp, H, (char*)nullptr);
+    launch_prep(k_lx3_prep, Bp, (hipStream_t)stream, rep, (bf16*)rep_hi, (bf16*)rep_lo, B, Bp, H, nullptr);
     HIP_LAUNCH_CHECK();
     return 0;
 }
 
 // Forward of the one-hot softmax CE over items 1..N at float32 grade (three bf16 MFMAs per product), streaming the fp32
 // table itself.  Same scratch and outputs as ader_lbf_fwd; rep_hi / rep_lo: Bp*168 bf16 each.
-int ader_lx3_fwd_img(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* lab, const float* wrow,
-                     void* rep_hi, void* rep_lo, float* pm, float* pl, float* pO, float* lse, float* off, float* rowloss, float* loss,
-                     float* drep, void* rep_img, void* stream);
-int ader_lx3_fwd(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* lab, const float* wrow,
-                 void* rep_hi, void* rep_lo, float* pm, float* pl, float* pO, float* lse, float* off, float* rowloss, float* loss,
-                 float* drep, void* stream) {
-    return ader_lx3_fwd_img(rep, emb, item_num, B, Bp, H, N, lab, wrow, rep_hi, rep_lo, pm, pl, pO, lse, off, rowloss, loss, drep, nullptr,
-                            stream);
-}
-// ... rep_img != NULL: ader_x3_rep_image's output (ader_x3_rep_image_bytes(Bp) bytes, 16-byte aligned, pads zero) is written by the same
+// rep_img != NULL: ader_x3_rep_image's output (ader_x3_rep_image_bytes(Bp) bytes, 16-byte aligned, pads zero) is written by the same
 // launch that cuts the operand planes: the fused update finds it ready (one launch and one kernel boundary fewer on the critical path)
-int ader_lx3_fwd_img(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* lab, const float* wrow,
-                     void* rep_hi, void* rep_lo, float* pm, float* pl, float* pO, float* lse, float* off, float* rowloss, float* loss,
-                     float* drep, void* rep_img, void* stream) {
-    return ader_lx3_fwd_img_lnf(rep, emb, item_num, B, Bp, H, N, lab, wrow, rep_hi, rep_lo, pm, pl, pO, lse, off, rowloss, loss, drep, rep_img,
-                                nullptr, stream);
-}
-// ... with the backward of the FINAL LayerNorm fused into the merge (lnf != NULL; include/ader_hip.h AderLnfBwd): rep = LN_f(x) (ADER.py:83-85),
+// lnf != NULL (include/ader_hip.h AderLnfBwd): the backward of the FINAL LayerNorm fused into the merge: rep = LN_f(x) (ADER.py:83-85),
 // so the row that has just formed dRep also forms dx = LN_f'(dRep) -- one launch and one kernel boundary fewer on the critical path of every step
 int ader_lx3_fwd_img_lnf(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* lab, const float* wrow,
                          void* rep_hi, void* rep_lo, float* pm, float* pl, float* pO, float* lse, float* off, float* rowloss, float* loss,
                          float* drep, void* rep_img, const AderLnfBwd* lnf, void* stream) {
     if (B <= 0) return 0;
-    if (rep_img && ((uintptr_t)rep_img & 15)) return -2;
-    if (Bp % 128 != 0 || B > Bp || H > HP || (H & 1) || H < 2 || N > item_num || ((uintptr_t)emb & 7)) return -2;
+    if (!flash_shapes_ok(Bp, H, N, item_num) || B > Bp || !x3_table_ok(emb) || ((uintptr_t)rep_img & 15)) return -2;
     hipStream_t st = (hipStream_t)stream;
     const Lx3Args x = lx3_args(emb + H, item_num, rep_hi, rep_lo, Bp, H, N, ader_lbf_ranges(N, Bp), pm, pl, pO);
     const LbfArgs a = lbf_args_of(x, B, 0);
-    hipLaunchKernelGGL(k_lx3_prep, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_hi, (bf16*)rep_lo, B, Bp, H, (char*)rep_img);
+    launch_prep(k_lx3_prep, Bp, st, rep, (bf16*)rep_hi, (bf16*)rep_lo, B, Bp, H, (char*)rep_img);
     if (int rc = lx3_forward(x, stream)) return rc;
     hipLaunchKernelGGL(k_lbf_combine<true>, dim3(Bp), dim3(640), 0, st, a, lab, wrow, lse, off, rowloss, drep, emb + H, rep,
                        lnf ? *lnf : AderLnfBwd{});
-    if (loss) hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, B, loss);     // NULL: ader_lbf_sum later (off the critical path)
+    if (loss) launch_sum(rowloss, B, loss, st);               // NULL: ader_lbf_sum later (off the critical path)
     HIP_LAUNCH_CHECK();
     return 0;
 }
@@ -1069,7 +902,7 @@ int ader_lx3_fwd_img_lnf(const float* rep, const float* emb, int item_num, int B
 // loss = sum of the per-row losses a flash forward left in rowloss[0..n) (fixed order), for callers that passed loss = NULL
 int ader_lbf_sum(const float* rowloss, int n, float* loss, void* stream) {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, (hipStream_t)stream, rowloss, n, loss);
+    launch_sum(rowloss, n, loss, (hipStream_t)stream);
     HIP_LAUNCH_CHECK();
     return 0;
 }
@@ -1086,33 +919,26 @@ int ader_lx3_readout_ranges(int Np, int Bk) {
 }
 
 // ader_lbf_fwd_kd at float32 grade: the distilled step's forward on the x3 kernels (arguments as ader_lbf_fwd_kd, with the fp32
-// table instead of the shadow and the two operand planes rep_hi / rep_lo).
-int ader_lx3_fwd_kd(const float* rep, const float* emb, int item_num, int n_train, int n_ex, int kd_row0, int Bp, int H, int N,
-                    int Np, const int* pos, const int* ex_trow, const float* teacher, long ldt, const float* tlse_all, float w_train,
-                    float w_ex, int* lab, float* wrow, int* trow, float* tlse2, void* rep_hi, void* rep_lo, float* pm, float* pl,
-                    float* pO, float* pO2, float* lse, float* off, float* rowloss, float* loss, float* drep, void* stream) {
-    return ader_lx3_fwd_kd_lnf(rep, emb, item_num, n_train, n_ex, kd_row0, Bp, H, N, Np, pos, ex_trow, teacher, ldt, tlse_all, w_train, w_ex,
-                               lab, wrow, trow, tlse2, rep_hi, rep_lo, pm, pl, pO, pO2, lse, off, rowloss, loss, drep, nullptr, nullptr, stream);
-}
+// table instead of the shadow and the two operand planes rep_hi / rep_lo; rep_img and lnf as in ader_lx3_fwd_img_lnf).
 int ader_lx3_fwd_kd_lnf(const float* rep, const float* emb, int item_num, int n_train, int n_ex, int kd_row0, int Bp, int H, int N,
                         int Np, const int* pos, const int* ex_trow, const float* teacher, long ldt, const float* tlse_all, float w_train,
                         float w_ex, int* lab, float* wrow, int* trow, float* tlse2, void* rep_hi, void* rep_lo, float* pm, float* pl,
                         float* pO, float* pO2, float* lse, float* off, float* rowloss, float* loss, float* drep, void* rep_img,
                         const AderLnfBwd* lnf, void* stream) {
     if (n_train + n_ex <= 0) return 0;
-    if (Bp % 128 != 0 || kd_row0 % 128 != 0 || n_train > kd_row0 || kd_row0 + n_ex > Bp || H > HP || (H & 1) || H < 2 || N > item_num ||
-        Np > N || Np < 1 || ((uintptr_t)emb & 7) || ((uintptr_t)rep_img & 15)) return -2;
+    if (!flash_shapes_ok(Bp, H, N, item_num) || !flash_kd_ok(n_train, n_ex, kd_row0, Bp, N, Np) || !x3_table_ok(emb) ||
+        ((uintptr_t)rep_img & 15)) return -2;
     hipStream_t st = (hipStream_t)stream;
     Lx3Args x = lx3_args(emb + H, item_num, rep_hi, rep_lo, Bp, H, N, ader_lbf_ranges(N, Bp), pm, pl, pO);
     lx3_args_kd(x, kd_row0, Np, teacher, ldt, trow, tlse2, pO2, ader_lx3_readout_ranges(Np, Bp - kd_row0));
     const LbfArgs a = lbf_args_of(x, n_train, n_ex);
-    hipLaunchKernelGGL(k_lbf_prep_kd, dim3((Bp * LDR + 255) / 256), dim3(256), 0, st, rep, (bf16*)rep_hi, (bf16*)rep_lo, n_train, n_ex,
-                       kd_row0, Bp, H, pos, ex_trow, tlse_all, w_train, w_ex, lab, wrow, trow, tlse2, (char*)rep_img);
+    launch_prep(k_lbf_prep_kd, Bp, st, rep, (bf16*)rep_hi, (bf16*)rep_lo, n_train, n_ex, kd_row0, Bp, H, pos, ex_trow, tlse_all, w_train, w_ex,
+                lab, wrow, trow, tlse2, (char*)rep_img);
     if (int rc = lx3_forward(x, stream)) return rc;
     if (int rc = lx3_readout(x, stream)) return rc;
     hipLaunchKernelGGL(k_lbf_combine<true>, dim3(Bp), dim3(640), 0, st, a, (const int*)lab, (const float*)wrow, lse, off, rowloss, drep,
                        emb + H, rep, lnf ? *lnf : AderLnfBwd{});
-    if (loss) hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, Bp, loss);     // NULL: ader_lbf_sum(rowloss, Bp) later
+    if (loss) launch_sum(rowloss, Bp, loss, st);              // NULL: ader_lbf_sum(rowloss, Bp) later
     HIP_LAUNCH_CHECK();
     return 0;
 }
@@ -1124,7 +950,7 @@ int ader_lx3_fwd_kd_lnf(const float* rep, const float* emb, int item_num, int n_
 int ader_lx3_fwd_shard(const void* rep_hi, const void* rep_lo, const float* emb, int item_num, int Bp, int H, int N, int item_begin,
                        int item_count, float* pm, float* pl, float* pO, float* part, void* stream) {
     if (Bp <= 0) return 0;
-    if (Bp % 128 != 0 || H > HP || (H & 1) || H < 2 || N > item_num || item_begin < 0 || ((uintptr_t)emb & 7)) return -2;
+    if (!flash_shapes_ok(Bp, H, N, item_num) || item_begin < 0 || !x3_table_ok(emb)) return -2;
     hipStream_t st = (hipStream_t)stream;
     const int n_loc = shard_items(N, item_begin, item_count);
     const Lx3Args x = lx3_args(emb + (size_t)H * (1 + item_begin), item_num - item_begin, rep_hi, rep_lo, Bp, H, n_loc,
@@ -1157,8 +983,8 @@ __global__ __launch_bounds__(256) void k_lx3_sum_ranges(const float* __restrict_
 int ader_lx3_readout_shard(const float* emb, int item_num, int Bk, int H, int Np, int item_begin, int item_count, const float* teacher,
                            long ldt, const int* trow, const float* tlse2, float* pO2, float* part2, void* stream) {
     if (Bk <= 0) return 0;
-    if (Bk % 128 != 0 || H > HP || (H & 1) || H < 2 || Np > item_num || item_begin < 0 || (item_begin & 3) || ((uintptr_t)emb & 7) ||
-        !teacher || !trow || !tlse2) return -2;
+    if (!flash_shapes_ok(Bk, H, Np, item_num) || item_begin < 0 || (item_begin & 3) || !x3_table_ok(emb) || !teacher || !trow || !tlse2)
+        return -2;
     hipStream_t st = (hipStream_t)stream;
     const int n_loc = shard_items(Np, item_begin, item_count);
     const int ranges2 = n_loc > 0 ? ader_lx3_readout_ranges(n_loc, Bk) : 0;
@@ -1187,22 +1013,11 @@ __global__ __launch_bounds__(256) void k_lx3_merge_parts_kd(const float* __restr
     if (b >= Bk) return;
     const float w = b < B ? wrow[b] : 0.0f;
     if (b >= B) {
-        if (lane == 0) { lse[b] = 0.0f; rowloss[b] = 0.0f; off[b] = -INFINITY; }
+        if (lane == 0) lbf_row_pad(b, lse, off, rowloss);
         return;
     }
-    float M = -INFINITY;
-    for (int i = 0; i < W; ++i) M = fmaxf(M, parts_s[((size_t)i * Bk + b) * PART_LD]);
-    float L = 0.0f, o[3] = {0.0f, 0.0f, 0.0f}, o2[3] = {0.0f, 0.0f, 0.0f};
-    for (int i = 0; i < W; ++i) {
-        const float* pr = parts_s + ((size_t)i * Bk + b) * PART_LD;
-        const float* pt = parts_t + ((size_t)i * Bk + b) * PART_LD;
-        const float m = pr[0];
-        const float sc = (m != -INFINITY) ? __builtin_amdgcn_exp2f(m - M) : 0.0f;
-        L += pr[1] * sc;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const int c = lane + 64 * k; if (c < H) { o[k] += pr[2 + c] * sc; o2[k] += pt[2 + c]; } }
-    }
-    const float lse2 = M + log2f(L);
+    float o[3] = {0.0f, 0.0f, 0.0f}, o2[3] = {0.0f, 0.0f, 0.0f};
+    LBF_MERGE_RANKS(parts_s, Bk, o2[k] += parts_t[((size_t)i * Bk + b) * PART_LD + 2 + c])
     float dot = 0.0f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -1213,12 +1028,7 @@ __global__ __launch_bounds__(256) void k_lx3_merge_parts_kd(const float* __restr
         }
     }
     dot = wave_sum(dot);
-    if (lane == 0) {
-        const float z = lse2 / LOG2E;
-        lse[b] = z;
-        rowloss[b] = w * (z - dot);
-        off[b] = (w > 0.0f) ? log2f(w) - lse2 : -INFINITY;
-    }
+    if (lane == 0) LBF_ROW_OUT(dot, true)
 }
 int ader_lx3_merge_parts_kd(const float* parts_s, const float* parts_t, int world, int Bk, int B, int H, const float* rep,
                             const float* wrow, float* lse, float* off, float* rowloss, float* drep, void* stream) {
@@ -1239,7 +1049,7 @@ int ader_lx3_merge_parts(const float* parts, int world, int Bp, int B, int H, co
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_lbf_merge_parts<true>, dim3((Bp + 3) / 4), dim3(256), 0, st, parts, world, Bp, B, H, e_lab,
                        (const bf16*)nullptr, rep, wrow, lse, off, rowloss, drep);
-    hipLaunchKernelGGL(k_lbf_sum, dim3(1), dim3(256), 0, st, rowloss, B, loss);
+    launch_sum(rowloss, B, loss, st);
     HIP_LAUNCH_CHECK();
     return 0;
 }

@@ -2,7 +2,8 @@
 // Reference: ADER.py:88-93 (logits = rep . item_emb^T, one-hot softmax CE) in float32: every product as three bf16 MFMAs on hi/lo
 // operand splits (hi.hi + lo.hi + hi.lo, ~2^-16 relative, fp32 accumulate, fp32 softmax).
 //
-// Same algorithm as k_lx3_fwd (logits_bf16.hip): per 32-item block S^T = E.rep^T, online max / sum-exp, and the probabilities go
+// The flash forward of flash_walk.h, whose block span, online softmax, P split and epilogues k_lx3_fwd (logits_bf16.hip) expands
+// too: per 32-item block S^T = E.rep^T, online max / sum-exp, and the probabilities go
 // back into the matrix core as the A operand of O[b,:] += P^T.E (the softmax-weighted readout = dRep up to the target term), so
 // nothing [rows, N]-sized is ever written.  The table block is split into hi/lo on its way into LDS as the bank-conflict-free image
 // of x3_image.h (16-byte k-chunks [kc][item][8 channels]), and both operand reads -- ds_read_b128 rows for S^T, ds_read_b64_tr_b16
@@ -23,42 +24,35 @@
 // (k_lx3f, 16 rows per wave on 16x16x32 tiles, and k_lx3h, k_lx3g's blocking on 16x16x32 tiles, were measured 25 % and 4 % slower in
 // round 3 -- NOTEBOOK.md -- and removed in round 4.)
 // Output partials (pm, pl, pO per item range) and the merge (k_lbf_combine<true>) are those of k_lx3_fwd.  gfx950 only.
-#include "lbf_common.h"
+#include "flash_walk.h"
 #include "x3_image.h"
 #include "logit_tile.h"
 #include "../../include/ader_hip.h"
 
-#define F3_FB 32                   // items per streamed block
-#define F3_RND 3                   // staging rounds of k_lx3g: 12 units of (8 items x 8 k-chunks), 4 waves
+#define F3_RND 3                  // staging rounds of k_lx3g: 12 units of (8 items x 8 k-chunks), 4 waves
 #define G3_ROWS 128                // batch rows per workgroup
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 // ===========================================================================================================================
-// The shared walk.  Every piece is a macro over the kernel's locals, expanded in the kernel, and not a function: as functions the
-// operand reads compile to other streams.  Names a piece expects in scope are the ones the pieces before it define.
+// The shared walk: the layout-independent pieces (FW_*: workgroup map and block span, online softmax, P split, epilogues) are
+// flash_walk.h's; here stand the pieces of the block images.  Every piece is a macro over the kernel's locals, expanded in the kernel,
+// and not a function: as functions the operand reads compile to other streams.  Names a piece expects in scope are the ones the
+// pieces before it define.
 
-// ---- workgroup prologue.  G3_WG_MAP: tid / lane / wave / r32 / hh, block -> (item range `range`, row chunk `bc` of nchunk_).  The
-// row chunks of an item range sit on one XCD: the table block is fetched from HBM once and served to the others by that XCD's L2
+// ---- workgroup prologue.  G3_WG_MAP: tid / lane / wave / r32 / hh, then FW_XCD_MAP's (range, bc)
 #define G3_WG_MAP(ranges_, nchunk_)                                                                       \
     const int tid = threadIdx.x, lane = tid & 63;                                                         \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                                            \
     const int r32 = lane & 31, hh = lane >> 5;                                                            \
-    const int nchunk = (nchunk_);                                                                         \
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;                                               \
-    const int range = xcd + 8 * (slot / nchunk);                                                          \
-    const int bc = slot % nchunk;                                                                         \
-    if (range >= (ranges_)) return;
-// G3_WG_BLOCKS: the range's span [blk_begin, blk_end) of the ncat_ items' 32-item blocks, cut at the ncol_ columns these rows see,
-// nb_blocks of them; b0 = the wave's first row; and the LDS zero fill: pads of every image (k-chunks >= ceil(H/8), bytes between the
-// quads) stay zero, the block stores never touch them.  (b0 stands behind nb_blocks and not in G3_WG_MAP: in front of the span's
-// divisions hipcc schedules the scalar prologue of all five kernels differently -- profiles/logits_x3_refactor_isa.txt)
+    FW_XCD_MAP(ranges_, nchunk_)
+// G3_WG_BLOCKS: FW_WG_SPAN's block span; b0 = the wave's first row; and the LDS zero fill: pads of every image (k-chunks >=
+// ceil(H/8), bytes between the quads) stay zero, the block stores never touch them.  (b0 stands behind nb_blocks and not in
+// G3_WG_MAP: in front of the span's divisions hipcc schedules the scalar prologue of all five kernels differently --
+// profiles/logits_x3_refactor_isa.txt)
 #define G3_WG_BLOCKS(ranges_, ncat_, ncol_)                                                               \
-    const int nblk_all = ((ncat_) + F3_FB - 1) / F3_FB;                                                   \
-    const int per = (nblk_all + (ranges_) - 1) / (ranges_);                                               \
-    const int blk_begin = range * per, blk_end = min(((ncol_) + F3_FB - 1) / F3_FB, blk_begin + per);     \
-    const int nb_blocks = max(0, blk_end - blk_begin);                                                    \
+    FW_WG_SPAN(ranges_, ncat_, ncol_)                                                                     \
     const int b0 = bc * G3_ROWS + wave * 32;                                                              \
     for (int i = tid; i < 3 * X3B_IMG_B / 16; i += 256) ((uint4*)smem_raw)[i] = make_uint4(0u, 0u, 0u, 0u);
 // rep fragments: lane (batch row r32, k-half hh) holds rep[b0 + r32][16 ks + 8 hh + 0..7]
@@ -112,43 +106,10 @@ __device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; } 
         }                                                                                                 \
     }
 
-// ---- the online softmax's head of block i0 (logits S of the chunk's N columns; running m_run, l_run, O): tail mask, running
-// maximum, (rare) rescale of l and O.  Leaves nm = -m_run and the block's sum ls = 0 for the exp that follows.
-// The two half-waves of a lane pair (l, l + 32) hold different items of the SAME batch row; m_run is kept equal in both, so the
-// cross-half exchange is only needed on the (rare) rescale path
-#define G3_SOFTMAX_HEAD()                                                                                 \
-        if (i0 + F3_FB > N) {                              /* tail block: items >= N are outside the softmax */ \
-            _Pragma("unroll") for (int j = 0; j < 16; ++j) if (i0 + acc_row(j, hh) >= N) S[j] = -INFINITY; \
-        }                                                                                                 \
-        float tmax = S[0];                                                                                \
-        _Pragma("unroll") for (int j = 1; j < 16; ++j) tmax = fmaxf(tmax, S[j]);                          \
-        float t2 = tmax * LOG2E;                                                                          \
-        if (__any(t2 > m_run + RESCALE_THR)) {                                                            \
-            t2 = fmaxf(t2, __shfl_xor(t2, 32, 64));                                                       \
-            const float m_new = (t2 > m_run + RESCALE_THR) ? t2 : m_run;                                  \
-            const float alpha = (m_new == -INFINITY) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);      \
-            l_run *= alpha;                                                                               \
-            m_run = m_new;                                                                                \
-            _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                              \
-                const float ar = __shfl(alpha, acc_row(j, hh), 64);     /* O rows are batch rows */       \
-                _Pragma("unroll") for (int nb = 0; nb < 5; ++nb) O[nb][j] *= ar;                          \
-            }                                                                                             \
-        }                                                                                                 \
-        const float nm = -m_run;                                                                          \
-        float ls = 0.0f;
-
-// ---- the plain readout O += P^T . E of the block image at Bh.  G3_PSPLIT: the probabilities in S as the A operands pa0 / pa1 (hi)
-// and pl0 / pl1 (lo).  G3_READOUT_LOADS: the first transposed reads (ft: half sets {items 4hh.., 8 + 4hh.., 16 + 4hh.., 24 + 4hh..} of
-// ONE plane; hi, lo, hi, lo ...), which do not depend on P.  G3_READOUT: ten half steps, 30 MFMAs, the reads three half steps ahead
-#define G3_O_ZERO()                                                                                       \
-    f32x16 O[5];                                                                                          \
-    _Pragma("unroll") for (int nb = 0; nb < 5; ++nb)                                                      \
-        _Pragma("unroll") for (int j = 0; j < 16; ++j) O[nb][j] = 0.0f;
-#define G3_PSPLIT()                                                                                       \
-        const bf16x8 pa0 = pack8(S, 0), pa1 = pack8(S, 1);                                                \
-        bf16x8 pl0, pl1;                                                                                  \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) { pl0[j] = (bf16)(S[j] - (float)pa0[j]); pl1[j] = (bf16)(S[8 + j] - (float)pa1[j]); }
-#define G3_READOUT_LOADS()                                                                                \
+// ---- the plain readout O += P^T . E of the block image at Bh, with FW_PSPLIT's A operands pa0 / pa1 (hi) and pl0 / pl1 (lo).
+// G3_READOUT_LOADS: the first transposed reads (ft: half sets {items 4hh.., 8 + 4hh.., 16 + 4hh.., 24 + 4hh..} of ONE plane; hi, lo,
+// hi, lo ...), which do not depend on P.  G3_READOUT: ten half steps, 30 MFMAs, the reads three half steps ahead
+#define G3_READOUT_LOADS()                                                                              \
         bf16x4 ft[3][4];                                                                                  \
         G3_LOADT(ft[0], 0, 0);                                                                            \
         G3_LOADT(ft[1], 0, 1);                                                                            \
@@ -171,22 +132,6 @@ __device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; } 
             if (hs + 3 < 10) G3_LOADT(ft[hs % 3], (hs + 3) >> 1, (hs + 3) & 1);                           \
             __builtin_amdgcn_sched_barrier(0);                                                            \
         }
-
-// ---- epilogues: the wave's 32 rows of O to o_ [rows][HP]; a forward's (m, l) partials of its range
-#define G3_STORE_O(o_)                                                                                    \
-    {                                                                                                     \
-        float* o = (o_);                                                                                  \
-        _Pragma("unroll") for (int nb = 0; nb < 5; ++nb)                                                  \
-            _Pragma("unroll") for (int j = 0; j < 16; ++j) o[(size_t)acc_row(j, hh) * HP + 32 * nb + r32] = O[nb][j]; \
-    }
-#define G3_STORE_ML()                                                                                     \
-    {                                                                                                     \
-        const float l_tot = l_run + __shfl_xor(l_run, 32, 64);                                            \
-        if (hh == 0) {                                                                                    \
-            a.pm[(size_t)range * a.Bp + b0 + r32] = m_run;                                                \
-            a.pl[(size_t)range * a.Bp + b0 + r32] = l_tot;                                                \
-        }                                                                                                 \
-    }
 
 // ---- F3 staging (k_lx3g / k_lx3k / k_lx3t): a table block = 32 rows of H floats on its way into an LDS block image, by k-chunks.
 // Round r (0..2) of wave w covers items 8 w.. and k-chunks 8 r..: lane l -> item + (l & 7), k-chunk + (l >> 3): the 8 lanes of an
@@ -211,7 +156,7 @@ __device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; } 
 // here -- a select would make hipcc wait for each load right behind its issue.
 #define F3_LOAD(blk_)                                                                                     \
     {                                                                                                     \
-        const int so_ = (blk_) * (F3_FB * 4) * H;              /* byte offset of the block (< 2^31: checked by the launcher) */ \
+        const int so_ = (blk_) * (FB * 4) * H;              /* byte offset of the block (< 2^31: checked by the launcher) */ \
         _Pragma("unroll") for (int r = 0; r < F3_RND; ++r) {                                              \
             const u32x4_t va_ = __builtin_amdgcn_raw_buffer_load_b128(trs, voff + 256 * r, so_, 0);         \
             const u32x4_t vb_ = __builtin_amdgcn_raw_buffer_load_b128(trs, (F3_PART(r) ? voffp : voff + 16) + 256 * r, so_, 0); \
@@ -250,7 +195,7 @@ __device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; } 
         const bool more = i + 2 < nb_blocks;                                                              \
         if (more) F3_LOAD(blk_begin + i + 2);                                                             \
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);                                      \
-        const int i0 = (blk_begin + i) * F3_FB;                                                           \
+        const int i0 = (blk_begin + i) * FB;                                                           \
         f32x16 S;                                                                                         \
         G3_SPHASE(S, Bh)                                                                                  \
         if (more) F3_STORE(g3_buf_new(bcur));
@@ -268,7 +213,7 @@ __device__ __forceinline__ int g3_buf_new(int b) { return b == 0 ? 2 : b - 1; } 
 // instruction stream only with its own order of qb and itb, so one shared statement of them serves one kernel and not the other.)
 #define P3_LOAD(sc_, blk_)                                                                              \
     {                                                                                                     \
-        const int so_ = (blk_) * (F3_FB * 4) * H;              /* byte offset of the block (< 2^31: checked by the launcher) */ \
+        const int so_ = (blk_) * (FB * 4) * H;              /* byte offset of the block (< 2^31: checked by the launcher) */ \
         _Pragma("unroll") for (int r = 0; r < 5; ++r)                                                     \
             sc_[r] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(trs, voffb + 128 * r, so_, 0)); \
     }
@@ -298,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
     const int N = (bc * G3_ROWS >= a.kd_row0) ? a.Np : a.N;            // columns of this chunk's softmax (distilled rows: first Np)
     G3_WG_BLOCKS(a.ranges, a.N, N)
     G3_REP_FRAGS()
-    G3_O_ZERO()
+    FW_O_ZERO()
     float m_run = -INFINITY, l_run = 0.0f;
     F3_LOCALS()
     G3_T_OFF()
@@ -307,15 +252,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3g(Lx3Args a) {
         __builtin_amdgcn_sched_barrier(0);
         G3_READOUT_LOADS()                                 // they do not depend on S: in flight under the softmax section
         __builtin_amdgcn_sched_barrier(0);
-        G3_SOFTMAX_HEAD()
-#pragma unroll
-        for (int j = 0; j < 16; ++j) { S[j] = __builtin_amdgcn_exp2f(fmaf(S[j], LOG2E, nm)); ls += S[j]; }
-        l_run += ls;
-        G3_PSPLIT()
+        FW_SOFTMAX_HEAD()
+        FW_EXP_SUM()
+        FW_PSPLIT()
         G3_READOUT()
     F3_WALK_END()
-    G3_STORE_ML()
-    G3_STORE_O(a.pO + ((size_t)range * a.Bp + b0) * HP)
+    FW_STORE_ML()
+    FW_STORE_O(a.pO + ((size_t)range * a.Bp + b0) * HP)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -335,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
     const int N = (bc * G3_ROWS >= a.kd_row0) ? a.Np : a.N;            // columns of this chunk's softmax (distilled rows: first Np)
     G3_WG_BLOCKS(a.ranges, a.N, N)
     G3_REP_FRAGS()
-    G3_O_ZERO()
+    FW_O_ZERO()
     float m_run = -INFINITY, l_run = 0.0f;
     const int qb = lane & 7, ib = lane >> 3;               // P3 staging locals
     const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);
@@ -379,8 +322,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
         const int bnext = g3_buf_next(bcur), bnew = g3_buf_new(bcur);
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
         const char* Bs = (const char*)(smem_raw + bnext * X3B_IMG_B);
-        const int i0 = (blk_begin + i) * F3_FB;
-        G3_SOFTMAX_HEAD()
+        const int i0 = (blk_begin + i) * FB;
+        FW_SOFTMAX_HEAD()
         uint32_t ph2[8], pl2[8];                           // P hi / lo as packed bf16 pairs
         // ---- the NEXT block's S phase, with this block's softmax in the shadows of its MFMAs: a matrix instruction holds the SIMD's
         // vector issue for 8 of its 32 clocks, so a few vector instructions placed BETWEEN the three MFMAs of a k-step cost nothing
@@ -491,8 +434,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
         const int bnext = g3_buf_next(bcur);
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);
         const char* Bs = (const char*)(smem_raw + bnext * X3B_IMG_B);
-        const int i0 = (blk_begin + i) * F3_FB;
-        G3_SOFTMAX_HEAD()
+        const int i0 = (blk_begin + i) * FB;
+        FW_SOFTMAX_HEAD()
         uint32_t ph2[8], pl2[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) P3_PAIR(q);
@@ -510,8 +453,8 @@ __global__ __launch_bounds__(256, 2) void k_lx3p(Lx3Args a) {
     }
 #undef P3_PACK
 #undef P3_PAIR
-    G3_STORE_ML()
-    G3_STORE_O(a.pO + ((size_t)range * a.Bp + b0) * HP)
+    FW_STORE_ML()
+    FW_STORE_O(a.pO + ((size_t)range * a.Bp + b0) * HP)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -530,7 +473,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
     const int Bk = a.Bp - a.kd_row0, Np = a.Np;
     G3_WG_MAP(a.ranges2, Bk / G3_ROWS)                     // b0 = first exemplar row of the wave (row of the padded batch: + kd_row0)
     G3_WG_BLOCKS(a.ranges2, Np, Np)
-    G3_O_ZERO()
+    FW_O_ZERO()
     const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc((void*)a.emb1, 0, a.vrows * H * 4, 0x00020000);     // P3 staging locals
     const int itb = 8 * wave + (lane >> 3), qb = lane & 7;
     const int voffb = itb * (4 * H) + 16 * qb;
@@ -545,10 +488,10 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
     // a whole staging set: loads straight into scratch).  Table blocks past the range are real rows (or zeros from the descriptor's
     // range check) that are stored into a buffer nobody reads; teacher blocks are clamped to the last FULL block of [0, Np).  The one
     // partial block of a launch (Np % 32 != 0; last range only) is peeled: element-wise clamped loads, validity applied to p.
-    const int nfull_all = Np / F3_FB;                      // >= 1 (launcher)
+    const int nfull_all = Np / FB;                      // >= 1 (launcher)
 #define R3_TLOAD(set_, blk_)                                                                              \
     {                                                                                                     \
-        const int i0_ = min((blk_), nfull_all - 1) * F3_FB;                                               \
+        const int i0_ = min((blk_), nfull_all - 1) * FB;                                               \
         _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                   \
             const f32x4_t v_ = *(const f32x4_t*)(trp + i0_ + 8 * q);                                      \
             tt[set_][4 * q] = v_[0]; tt[set_][4 * q + 1] = v_[1]; tt[set_][4 * q + 2] = v_[2]; tt[set_][4 * q + 3] = v_[3]; \
@@ -556,7 +499,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
     }
 #define R3_TSLOW(set_, blk_)                                                                              \
     {                                                                                                     \
-        const int i0_ = (blk_) * F3_FB;                                                                   \
+        const int i0_ = (blk_) * FB;                                                                   \
         _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                     \
             _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                 \
                 tt[set_][4 * q + k] = trp[min(i0_ + 8 * q + k, Np - 1 - 4 * hh)];                         \
@@ -584,13 +527,13 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
         const char* Bh = (const char*)(smem_raw + bcur * X3B_IMG_B);                                      \
         G3_READOUT_LOADS()                                                                                \
         f32x16 S;                                                                                         \
-        const int lim_ = (tr >= 0) ? Np - (blk_begin + i) * F3_FB - 4 * hh : 0;     /* items of this lane's positions inside [0, Np) */ \
+        const int lim_ = (tr >= 0) ? Np - (blk_begin + i) * FB - 4 * hh : 0;     /* items of this lane's positions inside [0, Np) */ \
         _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                                  \
             const float x_ = __builtin_amdgcn_exp2f(fmaf(tt[e_][j], LOG2E, -tl2));                        \
             S[j] = ((j & 3) + 8 * (j >> 2) < lim_) ? x_ : 0.0f;                                           \
         }                                                                                                 \
         R3_TLOAD(e_, blk_begin + i + 2);                                                                  \
-        G3_PSPLIT()                                                                                       \
+        FW_PSPLIT()                                                                                       \
         G3_READOUT()                                                                                      \
         bcur = g3_buf_next(bcur);                                                                         \
         ++i;                                                                                              \
@@ -607,7 +550,7 @@ __global__ __launch_bounds__(256, 2) void k_lx3r(Lx3Args a) {
 #undef R3_TSLOW
 #undef R3_ITER
 #undef R3_TLOAD
-    G3_STORE_O(a.pO2 + ((size_t)range * Bk + b0) * HP)
+    FW_STORE_O(a.pO2 + ((size_t)range * Bk + b0) * HP)
 }
 
 // ---- launchers.  The grid of the shared walk: one workgroup per (item range, 128-row chunk)
@@ -617,7 +560,7 @@ static bool x3_table_fits(int vrows, int H) { return (long)vrows * H * 4 < (1l <
 
 // teacher readout launch: x.ranges2 item ranges x (Bp - kd_row0) / 128 chunks.  false: the shape is not k_lx3r's (caller falls back)
 bool lx3r_supports(const Lx3Args& x) {
-    return x.H == 150 && x.Np >= F3_FB && (x.ldt & 3) == 0 && (((uintptr_t)x.teacher) & 15) == 0 && (long)(x.vrows + 5 * F3_FB) * x.H * 4 < (1l << 31);      // (block offsets are 32-bit; the stream runs 4 blocks ahead)
+    return x.H == 150 && x.Np >= FB && (x.ldt & 3) == 0 && (((uintptr_t)x.teacher) & 15) == 0 && (long)(x.vrows + 5 * FB) * x.H * 4 < (1l << 31);      // (block offsets are 32-bit; the stream runs 4 blocks ahead)
 }
 int lx3r_launch(const Lx3Args& x, void* stream) {
     if (int e = ader_dyn_lds<k_lx3r>(3 * X3B_IMG_B)) return e;
@@ -810,7 +753,7 @@ __global__ __launch_bounds__(256, 1) void k_lx3t(TopkX3Args a) {
     G3_WG_MAP(a.ranges, a.Bp / G3_ROWS)
     const int H = a.H, N = a.N;
     G3_WG_BLOCKS(a.ranges, N, N)
-    const int k = a.k, keep = a.keep, ldb = keep + F3_FB;
+    const int k = a.k, keep = a.keep, ldb = keep + FB;
     u64* buf = (u64*)(smem_raw + 3 * X3B_IMG_B);
     int* cnt = (int*)(buf + G3_ROWS * ldb);
     if (tid < G3_ROWS) cnt[tid] = 0;
@@ -829,7 +772,7 @@ __global__ __launch_bounds__(256, 1) void k_lx3t(TopkX3Args a) {
     int any_seen = 0;
     if (srow)
         for (int t = hh; t < a.seen_ld; t += 2)
-            any_seen |= (unsigned)(srow[t] - 1 - blk_begin * F3_FB) < (unsigned)(nb_blocks * F3_FB);        // id 0 wraps: never inside
+            any_seen |= (unsigned)(srow[t] - 1 - blk_begin * FB) < (unsigned)(nb_blocks * FB);        // id 0 wraps: never inside
     any_seen |= __shfl_xor(any_seen, 32, 64);
     F3_LOCALS()
     G3_A_OFF()
@@ -838,7 +781,7 @@ __global__ __launch_bounds__(256, 1) void k_lx3t(TopkX3Args a) {
         if (any_seen)
             for (int t = hh; t < a.seen_ld; t += 2) {
                 const unsigned d = (unsigned)(srow[t] - 1 - i0);
-                if (d < (unsigned)F3_FB) sm |= 1u << d;
+                if (d < (unsigned)FB) sm |= 1u << d;
             }
         sm |= __shfl_xor(sm, 32, 64);
         // filter + append: a key goes in unless its x3 score is provably outside the band below the row's running k-th best
@@ -1036,7 +979,7 @@ int ader_rank_targets_x3(const float* rep, const float* emb, int item_num, int B
 // multiple of 8 (the block -> (range, chunk) mapping), so it may exceed the number of 32-item blocks: such ranges are empty.
 int ader_topk_x3_kmax(void) { return TK3_KMAX; }
 int ader_topk_x3_ranges(int N, int Bp) {
-    const int nblk = (N + F3_FB - 1) / F3_FB;
+    const int nblk = (N + FB - 1) / FB;
     const int nchunk = Bp / G3_ROWS > 0 ? Bp / G3_ROWS : 1;
     int target = 256 / nchunk / 8 * 8;
     if (target < 8) target = 8;
@@ -1060,7 +1003,7 @@ int ader_topk_items_x3(const float* rep, const float* emb, int item_num, int B, 
     a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ranges = ader_topk_x3_ranges(N, Bp); a.k = k; a.keep = k + band;
     a.ncol = ncol; a.seen = seen; a.seen_ld = seen_ld; a.delta = delta; a.part3 = part3; a.status = status; a.diag = diag;
     a.items = items; a.scores = scores;
-    const size_t lds = 3 * X3B_IMG_B + (size_t)G3_ROWS * (a.keep + F3_FB) * sizeof(u64) + G3_ROWS * sizeof(int);
+    const size_t lds = 3 * X3B_IMG_B + (size_t)G3_ROWS * (a.keep + FB) * sizeof(u64) + G3_ROWS * sizeof(int);
     const size_t lds_fin = (size_t)((((a.keep + 15) & ~15) + 1) * LDE) * sizeof(float);
     if (int e = ader_dyn_lds<k_lx3t>(lds)) return e;
     if (int e = ader_dyn_lds<k_topk3_finish>(lds_fin)) return e;

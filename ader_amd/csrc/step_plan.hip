@@ -50,8 +50,7 @@ struct FnEntry {
 const FnEntry kFns[] = {
     ADER_PLAN_FN(ader_build_rowinfo),      ADER_PLAN_FN(ader_seq_fwd),             ADER_PLAN_FN(ader_seqp_fwd),
     ADER_PLAN_FN(ader_seq_pack_plan),      ADER_PLAN_FN(ader_sparse_lists_meta),   ADER_PLAN_FN(ader_sparse_lists),
-    ADER_PLAN_FN(ader_lx3_fwd_img_lnf),    ADER_PLAN_FN(ader_lx3_fwd_kd_lnf),      ADER_PLAN_FN(ader_lx3_fwd_img),
-    ADER_PLAN_FN(ader_lx3_fwd),            ADER_PLAN_FN(ader_lx3_fwd_kd),          ADER_PLAN_FN(ader_seq_bwd_ffn),
+    ADER_PLAN_FN(ader_lx3_fwd_img_lnf),    ADER_PLAN_FN(ader_lx3_fwd_kd_lnf),      ADER_PLAN_FN(ader_seq_bwd_ffn),
     ADER_PLAN_FN(ader_seq_bwd_qkv),        ADER_PLAN_FN(ader_seqp_bwd_ffn),        ADER_PLAN_FN(ader_seqp_bwd_qkv),
     ADER_PLAN_FN(ader_attn_last_bwd),      ADER_PLAN_FN(ader_attn_x3_bwd),         ADER_PLAN_FN(ader_attn_bwd),
     ADER_PLAN_FN(ader_attnp_bwd),          ADER_PLAN_FN(ader_attnp_last_bwd),      ADER_PLAN_FN(ader_x3_rep_image),

@@ -487,7 +487,7 @@ int ader_tab_grad(const void* rep_hi, const void* rep_lo, const float* emb, int 
     return 0;
 }
 
-// The same for a DISTILLED step (padded row layout of ader_lbf_fwd_kd / ader_lx3_fwd_kd: rows [kd_row0, Bp) are exemplar rows with
+// The same for a DISTILLED step (padded row layout of ader_lbf_fwd_kd / ader_lx3_fwd_kd_lnf: rows [kd_row0, Bp) are exemplar rows with
 // dlogit = w (softmax(s[:Np]) - softmax(teacher row))): the gradient-only form that feeds the dense data-parallel exchange.
 int ader_tab_grad_kd(const void* rep_hi, const void* rep_lo, const float* emb, int item_num, int Bp, int kd_row0, int H, int N, int Np,
                      const int* lab, const float* wrow, const float* off, const float* teacher, long ldt, const int* trow,

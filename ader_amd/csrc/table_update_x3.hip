@@ -483,7 +483,7 @@ static int tab_update_x3(const void* rep_hi, const void* rep_lo, const void* rep
 extern "C" {
 
 // LDS image of the x3 operand rows for ader_tab_update_x3[_kd]: img = ader_x3_rep_image_bytes(Bp) bytes, 16-byte aligned, built from
-// the two planes rep_hi / rep_lo [Bp,168] that ader_lx3_prep / ader_lx3_fwd[_kd] leave (Bp % 32 == 0).
+// the two planes rep_hi / rep_lo [Bp,168] that ader_lx3_prep / ader_lx3_fwd_{img,kd}_lnf leave (Bp % 32 == 0).
 int ader_x3_rep_image_bytes(int Bp) { return (Bp / X3_CH) * X3_IMG_B; }
 int ader_x3_rep_image(const void* rep_hi, const void* rep_lo, int Bp, void* img, void* stream) {
     if (Bp <= 0) return 0;

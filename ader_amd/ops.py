@@ -805,9 +805,9 @@ def logits_ce_x3(rep: torch.Tensor, emb: torch.Tensor, pos: torch.Tensor, ex_pos
     rep_hi, rep_lo, pm, pl, pO, lse, off, rowloss = _x3_fwd_scratch(N, Bp, dev)
     img = torch.zeros(call("ader_x3_rep_image_bytes", Bp), dtype=torch.uint8, device=dev)
     loss, drep = torch.zeros(1, device=dev), torch.empty(B, H, device=dev)
-    # (loss = NULL + ader_lbf_sum: the summation order Engine.train_step uses, so the two agree bit for bit)
-    call("ader_lx3_fwd_img", ptr(rep), ptr(emb), item_num, B, Bp, H, N, ptr(lab), ptr(wrow), ptr(rep_hi), ptr(rep_lo), ptr(pm), ptr(pl),
-         ptr(pO), ptr(lse), ptr(off), ptr(rowloss), None, ptr(drep), ptr(img), _st())
+    # (loss = NULL + ader_lbf_sum: the summation order Engine.train_step uses, so the two agree bit for bit; lnf = NULL: the plain merge)
+    call("ader_lx3_fwd_img_lnf", ptr(rep), ptr(emb), item_num, B, Bp, H, N, ptr(lab), ptr(wrow), ptr(rep_hi), ptr(rep_lo), ptr(pm), ptr(pl),
+         ptr(pO), ptr(lse), ptr(off), ptr(rowloss), None, ptr(drep), ptr(img), None, _st())
     call("ader_lbf_sum", ptr(rowloss), B, ptr(loss), _st())
     return loss, lse[:B].clone(), drep, rep_hi, rep_lo, off, lab, wrow, img
 
@@ -866,9 +866,9 @@ def logits_ce_x3_kd(rep: torch.Tensor, emb: torch.Tensor, pos: torch.Tensor, ex_
     rep_hi, rep_lo, pm, pl, pO, lse, off, rowloss = _x3_fwd_scratch(N, Bp, dev)
     pO2 = torch.empty(flash_sizes(0, Bp, call("ader_lx3_readout_ranges", Np, Bk), Bk).pO2, device=dev)
     loss, drep = torch.zeros(1, device=dev), torch.empty(B, H, device=dev)
-    call("ader_lx3_fwd_kd", ptr(rep), ptr(emb), item_num, n_train, n_ex, Bt, Bp, H, N, Np, ptr(pos), ptr(ex_trow), ptr(teacher),
+    call("ader_lx3_fwd_kd_lnf", ptr(rep), ptr(emb), item_num, n_train, n_ex, Bt, Bp, H, N, Np, ptr(pos), ptr(ex_trow), ptr(teacher),
          teacher.stride(0), ptr(tlse_all), float(w_train), float(w_ex), ptr(lab), ptr(wrow), ptr(trow), ptr(tlse2), ptr(rep_hi),
-         ptr(rep_lo), ptr(pm), ptr(pl), ptr(pO), ptr(pO2), ptr(lse), ptr(off), ptr(rowloss), ptr(loss), ptr(drep), _st())
+         ptr(rep_lo), ptr(pm), ptr(pl), ptr(pO), ptr(pO2), ptr(lse), ptr(off), ptr(rowloss), ptr(loss), ptr(drep), None, None, _st())
     lse_c = torch.cat([lse[:n_train], lse[Bt:Bt + n_ex]])
     return loss, lse_c, drep, rep_hi, rep_lo, off, lab, wrow, trow, tlse2
 

@@ -349,15 +349,10 @@ int ader_lbf_fwd_kd(const float* rep, const void* shadow, int item_num, int n_tr
                     float* pO, float* pO2, float* lse, float* off, float* rowloss, float* loss, float* drep, void* stream);
 int ader_lbf_ranges_kd(int N, int Bp, int kd_row0);
 int ader_lbf_readout_ranges(int N, int Bp, int kd_row0);
-/* the same forward at float32 grade (x3): the fp32 table instead of the shadow, two operand planes rep_hi / rep_lo.  Scratch:
- * pm / pl / pO with R = ader_lbf_ranges(N, Bp); pO2: ader_lx3_readout_ranges(Np, Bp - kd_row0) * (Bp - kd_row0) * 160 floats (the
- * teacher readout is a launch of its own here) */
+/* the same forward at float32 grade (x3) is ader_lx3_fwd_kd_lnf below: the fp32 table instead of the shadow, two operand planes
+ * rep_hi / rep_lo.  Scratch: pm / pl / pO with R = ader_lbf_ranges(N, Bp); pO2: ader_lx3_readout_ranges(Np, Bp - kd_row0) *
+ * (Bp - kd_row0) * 160 floats (the teacher readout is a launch of its own there) */
 int ader_lx3_readout_ranges(int Np, int Bk);
-int ader_lx3_fwd_kd(const float* rep, const float* emb, int item_num, int n_train, int n_ex, int kd_row0, int Bp, int H, int N,
-                    int Np, const int* pos, const int* ex_trow, const float* teacher, long ldt, const float* tlse_all,
-                    float w_train, float w_ex, int* lab, float* wrow, int* trow, float* tlse2, void* rep_hi, void* rep_lo,
-                    float* pm, float* pl, float* pO, float* pO2, float* lse, float* off, float* rowloss, float* loss, float* drep,
-                    void* stream);
 /* Pieces of ader_lbf_fwd for catalog-sharded data parallelism (each rank holds 1/W of the table rows and streams only
  * those; ADER.py:91-93 with the item axis split across ranks): ader_lbf_prep builds the bf16 operand rows [Bp,168] of the
  * (all-gathered) representations; ader_lbf_fwd_shard returns per batch row the softmax partials {max (log2 domain), sum,
@@ -391,19 +386,18 @@ int ader_lx3_merge_parts_kd(const float* parts_s, const float* parts_t, int worl
                             const float* wrow, float* lse, float* off, float* rowloss, float* drep, void* stream);
 int ader_lx3_merge_parts(const float* parts, int world, int Bp, int B, int H, const float* e_lab, const float* rep,
                          const float* wrow, float* lse, float* off, float* rowloss, float* loss, float* drep, void* stream);
-/* float32-grade variant of ader_lbf_fwd ("x3": every product as three bf16 MFMAs on hi/lo operand splits, fp32 accumulate;
- * ADER.py:91-93 is fp32 arithmetic).  Streams the fp32 table itself -- no bf16 shadow exists in this mode.  rep_hi/rep_lo:
- * Bp*168 bf16 each (written here: bf16(rep), bf16(rep - hi)); the other scratch and the outputs as in ader_lbf_fwd. */
+/* float32-grade variant of ader_lbf_fwd / ader_lbf_fwd_kd ("x3": every product as three bf16 MFMAs on hi/lo operand splits, fp32
+ * accumulate; ADER.py:91-93 is fp32 arithmetic).  Streams the fp32 table itself -- no bf16 shadow exists in this mode.  rep_hi/rep_lo:
+ * Bp*168 bf16 each (written here: bf16(rep), bf16(rep - hi)); the other scratch and the outputs as in ader_lbf_fwd[_kd].  loss may be
+ * NULL: ader_lbf_sum(rowloss, ...) later.
+ * rep_img != NULL: the launch that cuts the planes also writes the operand images of the fused update (ader_x3_rep_image_bytes(Bp)
+ * bytes, zero-initialised once, 16-byte aligned; distilled form: over the padded row layout, for ader_tab_update_x3_kd) --
+ * ader_x3_rep_image need not be launched for this batch.  NULL: ader_x3_rep_image later.
+ * lnf != NULL: the backward of the final LayerNorm fused into the merge launch: rep = LN_f(x) (ADER.py:83-85), so the workgroup that
+ * forms a row of dRep also forms dx = LN_f'(dRep) for it (bit-equal to ader_ln_bwd) and the row's gamma / beta partials.  x [B,H] the
+ * input of the final LayerNorm (compact rows, as rep), mean / std [B] its statistics, gamma [H]; dx [B,H] out; slab [B][2][H] out
+ * (reduce with ader_reduce_slabs(slab, 2 H, B, H, 1, H, dgamma, dbeta)).  NULL: the plain merge. */
 int ader_lx3_prep(const float* rep, void* rep_hi, void* rep_lo, int B, int Bp, int H, void* stream);
-int ader_lx3_fwd(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* lab,
-                 const float* wrow, void* rep_hi, void* rep_lo, float* pm, float* pl, float* pO, float* lse, float* off,
-                 float* rowloss, float* loss, float* drep, void* stream);
-/* ... with the backward of the final LayerNorm fused into the merge launch: rep = LN_f(x) (ADER.py:83-85), so the workgroup that forms a
- * row of dRep also forms dx = LN_f'(dRep) for it (bit-equal to ader_ln_bwd) and the row's gamma / beta partials.  x [B,H] the input of
- * the final LayerNorm (compact rows, as rep), mean / std [B] its statistics, gamma [H]; dx [B,H] out; slab [B][2][H] out (reduce with
- * ader_reduce_slabs(slab, 2 H, B, H, 1, H, dgamma, dbeta)).  lnf == NULL: exactly ader_lx3_fwd_img / ader_lx3_fwd_kd (loss may be NULL
- * in both: ader_lbf_sum(rowloss, ...) later).  rep_img of the distilled form: as in ader_lx3_fwd_img -- the operand images of
- * ader_tab_update_x3_kd over the padded row layout, cut by the launch that cuts the planes (NULL: ader_x3_rep_image later). */
 typedef struct { const float *x, *mean, *std, *gamma; float *dx, *slab; } AderLnfBwd;
 int ader_lx3_fwd_img_lnf(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* lab,
                          const float* wrow, void* rep_hi, void* rep_lo, float* pm, float* pl, float* pO, float* lse, float* off,
@@ -413,21 +407,16 @@ int ader_lx3_fwd_kd_lnf(const float* rep, const float* emb, int item_num, int n_
                         float w_train, float w_ex, int* lab, float* wrow, int* trow, float* tlse2, void* rep_hi, void* rep_lo,
                         float* pm, float* pl, float* pO, float* pO2, float* lse, float* off, float* rowloss, float* loss, float* drep,
                         void* rep_img, const AderLnfBwd* lnf, void* stream);
-/* loss = sum of rowloss[0..n) in a fixed order: the last launch of ader_lx3_fwd when that was given loss = NULL (reference
+/* loss = sum of rowloss[0..n) in a fixed order: the last launch of an x3 forward when that was given loss = NULL (reference
  * ADER.py:93: reduce_mean of the per-row cross entropies; the weights 1/B are already in rowloss). */
 int ader_lbf_sum(const float* rowloss, int n, float* loss, void* stream);
-/* ader_lx3_fwd that also writes the operand images of the fused update (rep_img: ader_x3_rep_image_bytes(Bp) bytes, zero-initialised
- * once, 16-byte aligned; NULL: exactly ader_lx3_fwd) -- ader_x3_rep_image need not be launched for this batch. */
-int ader_lx3_fwd_img(const float* rep, const float* emb, int item_num, int B, int Bp, int H, int N, const int* lab,
-                     const float* wrow, void* rep_hi, void* rep_lo, float* pm, float* pl, float* pO, float* lse, float* off,
-                     float* rowloss, float* loss, float* drep, void* rep_img, void* stream);
 /* Gradient of the one-hot softmax CE w.r.t. the item table (ADER.py:91-93 differentiated): demb rows 1..N overwritten
  * (each row written once, then the sparse one-hot term is added with float atomics).  The GEMM operand is cut from the
  * fp32 table `emb` inside the kernel (bf16, or hi/lo when rep_lo != NULL: x3 mode). */
 int ader_tab_grad(const void* rep_hi, const void* rep_lo, const float* emb, int item_num, int B, int Bp, int H, int N,
                   const int* lab, const float* wrow, const float* off, float* demb, void* stream);
 
-/* ... for a distilled step (padded layout of ader_lbf_fwd_kd / ader_lx3_fwd_kd; rows [kd_row0, Bp) carry the teacher term of
+/* ... for a distilled step (padded layout of ader_lbf_fwd_kd / ader_lx3_fwd_kd_lnf; rows [kd_row0, Bp) carry the teacher term of
  * ADER.py:132-137): the gradient-only form behind the dense data-parallel exchange. */
 int ader_tab_grad_kd(const void* rep_hi, const void* rep_lo, const float* emb, int item_num, int Bp, int kd_row0, int H, int N,
                      int Np, const int* lab, const float* wrow, const float* off, const float* teacher, long ldt, const int* trow,

@@ -786,6 +786,8 @@ CASES = (
     + [_case("kd_Np%d_ex%d" % (np_, ne), mode="kd", Np=np_, n_ex=ne, lam=0.7)
        for np_, ne in ((648, 70), (650, 70), (64, 70), (130, 70), (645, 70), (648, 1), (645, 129), (650, 129))]
     + [_case("H%d" % h, H=h) for h in (64, 158, 10)]
+    # H mod 8 = 2 has no block image: the generic forward k_lx3_fwd<false> with a distilled chunk (N = Np), and its readout form
+    + [_case("H10_kd_Np645_ex70", H=10, mode="kd", Np=645, n_ex=70, lam=0.7)]
 )
 CASE_IDS = [c["name"] for c in CASES]
 
@@ -941,7 +943,7 @@ SHARD_CASES = (
     + [_scase("W3_kd_Np%d_ex%d" % (np_, ne), 3, n_ex=ne, Np=np_, lam=0.7)
        for np_, ne in ((648, 24), (645, 24), (256, 24), (257, 24), (130, 24), (64, 24), (648, 1), (645, 129))]
     + [_scase("W2_kd_NpN_ex24", 2, n_ex=24, Np=650, lam=0.7)]
-    # H = 64: the shard forward takes k_lx3_fwd<false>, the readout k_lx3_fwd<true>
+    # H = 64: the shard forward takes the block-image kernel k_lx3g (lx3f_supports(64)); only the readout is the generic k_lx3_fwd<true>
     + [_scase("W2_H64", 2, H=64), _scase("W3_H64_kd_Np645_ex24", 3, H=64, n_ex=24, Np=645, lam=0.7)]
 )
 SHARD_CASE_IDS = [c["name"] for c in SHARD_CASES]

@@ -15,7 +15,7 @@ Shapes: the smallest at which each mechanism of table_update_x3.hip engages (64-
 Measured on an MI355X (device error / emulated error, worst over the cases; profiles/x3_rowwise_parity.txt has every case):
     lse 1.28x (kd_Np648_ex70)   rowloss 1.18x (N129)   drep 1.19x (H10)   g_dense 1.08x (B1153)   g_sparse 1.07x (N63)
     loss 5.69x (B1153: 5.6e-08, a 1153-term float32 sum in another order; under the 16-ulp floor of 9.5e-07)
-The bound is 8x: the unchanged kernels sit on the emulation.  Adam and the untouched rows hold their bounds in all 27 cases."""
+The bound is 8x: the unchanged kernels sit on the emulation.  Adam and the untouched rows hold their bounds in all 28 cases."""
 import os
 import sys
 
