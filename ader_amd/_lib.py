@@ -99,6 +99,7 @@ _SIGS = {
     "ader_topk_ranges": [I, I],
     "ader_topk_items": [P, P, I, I, I, I, P, P, I, I, P, P, P, P],
     "ader_topk_items_cand": [P, P, I, I, I, I, P, P, I, P, I, I, P, P, P, P, P],
+    "ader_rank_targets_cand": [P, P, I, I, I, I, P, P, P, I, P, I, P, P, P, P],
     "ader_topk_x3_kmax": [],
     "ader_topk_x3_ranges": [I, I],
     "ader_topk_items_x3": [P, P, I, I, I, I, I, P, P, I, I, I, P, P, P, P, P, P, P, P, P, P],

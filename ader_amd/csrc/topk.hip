@@ -5,6 +5,8 @@
 //   k_topk_tile + k_topk_merge               all items 1..N, k <= 64                      (Engine.recommend, ader_topk_items)
 //   k_topk_cand + k_topk_merge               the items of one ascending id list, k <= 64  (Engine.recommend_among, ader_topk_items_cand)
 //   k_topk_wide_tile + k_topk_wide_select    all items 1..N, k <= 1024, slab and select   (Engine.recommend_wide, ader_topk_items_wide)
+// and the evaluation-side twin of the second form, the rank of a row's target under the same order:
+//   k_rank_cand                              the items of one ascending id list           (Engine.rank_targets_among, ader_rank_targets_cand)
 // A candidate is one 64-bit key (topk_key.h): order-preserving float bits above, the complemented 1-based item id below, so ONE unsigned
 // compare is the total order and no two candidates of a row compare equal.  Key 0 = "no candidate".  (The MFMA chain starts from +0 and
 // rounds to nearest, so it never yields -0; topk_key still folds -0 onto +0, as == does.)
@@ -252,6 +254,139 @@ __global__ __launch_bounds__(512) void k_topk_cand(TopkCandArgs ca) {
     rowbuf_flush(a.part + ((size_t)range * a.Bp + bc * TB) * k, buf, ldb, cnt, k, tid);
 }
 
+// ============================================================================================= the rank of a target among a candidate list
+// ader_rank_targets_cand: k_logits_tile<MODE_RANK>'s count (logits.hip) over k_topk_cand's gathered tile stream.  rank[b] = the number
+// of live positions of the list whose id c is a column of row b, is not seen by it, is not its target t, and whose score beats the
+// target's: s(b,c) > tl[b], or == with c < t -- the order of the keys above, so rank_targets_cand(b, items[b, j]) == j for what
+// ader_topk_items_cand returns over the same list.  tl[b] is k_target_logit's float32 (the same chain on the target's own table row),
+// so the target may be absent from the list; listed, it is skipped by id.
+// The walk, the id slots two tiles ahead, the gather, the live rule, ADER_ST_BAD_CAND and the seen lookup are k_topk_cand's, restated
+// here: lifted into helpers that both call, they change the code emitted for k_topk_cand (tools/isa_digest.py).  What differs is what
+// happens to an accumulator: no key, no row buffer, no third barrier, no second launch.  A lane owns two batch rows (j = 0, 1) and 4 positions of every tile, and
+// keeps one integer count per row over all tiles of its range; after the last tile the counts of the four lanes that share a row are
+// added (__shfl_xor 16, 32) and the wave issues one integer atomicAdd per row with a non-zero count.  Integer adds commute: rank is a
+// pure function of the inputs, for any list (a list that is not strictly ascending is flagged, its dead positions count for nothing).
+struct RankCandArgs {
+    const float* rep;      // [B,H]
+    const float* emb1;     // table row 1 (item 1); N: the last item of the table that may be read
+    int B, Bp, H, N;
+    const int* target;     // [Bp] 1-based target item
+    const int* ncol;       // [Bp] N for real rows, 0 for padding rows
+    const int* seen;       // [B, seen_ld] 1-based ids never to be counted (0 = none), or NULL
+    int seen_ld, ranges;   // ranges: over the M positions
+    const int* cand;       // [M] strictly ascending 1-based item ids
+    int M;
+    const float* tlogit;   // [Bp] the target's logit (k_target_logit)
+    int* rank;             // [Bp] zeroed by the launcher
+    int* status;           // status word or NULL
+};
+
+__global__ __launch_bounds__(512) void k_rank_cand(RankCandArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* E_l = smem;                                       // [TI][LDE]
+    float* R_l = E_l + TI * LDE;                             // [TB][LDE]
+    u64* msk = (u64*)(R_l + TB * LDE);                       // [TB] bit i: the id at position i of the tile is in the row's seen list
+    u64* lm = msk + TB;                                      // [2] bit i: position i of the slot's tile is live
+    int* idl = (int*)(lm + 2);                               // [2][TI] the slot's ids
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int mw = wave & 3, nw = wave >> 2;
+    const int H = a.H, ksteps = (H + 3) >> 2;
+    const int r16 = lane & 15, q = lane >> 4;
+    int range, bc, s_begin, s_end;
+    if (!tile_walk(a.Bp / TB, a.ranges, (a.M + TI - 1) / TI, range, bc, s_begin, s_end)) return;
+    if (s_begin >= s_end) return;                            // an empty range counts nothing
+    int nid = 0;                                             // wave 0: the id at position `lane` of the tile fetched last, and that tile's
+    u64 nlm = 0;                                             // live mask
+    auto fetch_ids = [&](int s) {                            // wave 0 only
+        const int p = s * TI + lane;
+        int id = 0x7fffffff;
+        bool bad = false;
+        if (p < a.M) {
+            id = a.cand[p];
+            const int prev = p > 0 ? a.cand[p - 1] : 0;
+            bad = id < 1 || id <= prev;
+        }
+        const u64 anybad = __ballot(bad);
+        if (anybad && lane == 0 && a.status) atomicOr(a.status, ADER_ST_BAD_CAND);
+        nid = id;
+        nlm = __ballot(p < a.M && !bad && id <= a.N);
+    };
+    if (wave == 0) {
+        fetch_ids(s_begin);
+        idl[(s_begin & 1) * TI + lane] = nid;
+        if (lane == 0) lm[s_begin & 1] = nlm;
+    }
+    stage_tile(R_l, a.rep, bc * TB, a.B, H, tid, 512);
+    if (tid < TB) msk[tid] = 0;
+    int nc[2], tg[2], cnt[2];
+    float tl[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int b = bc * TB + nw * 32 + j * 16 + r16;      // b < Bp: ncol, target and tlogit hold Bp entries
+        nc[j] = a.ncol[b]; tg[j] = a.target[b]; tl[j] = a.tlogit[b]; cnt[j] = 0;
+    }
+    float pre[TILE_STAGE_REGS];
+    __syncthreads();                                         // the first tile's ids are in LDS
+    tile_load_ids(pre, a.emb1, idl + (s_begin & 1) * TI, lm[s_begin & 1], H, tid);
+    if (wave == 0 && s_begin + 1 < s_end) fetch_ids(s_begin + 1);
+    for (int s = s_begin; s < s_end; ++s) {
+        const int cur = s & 1;
+        const int* ids = idl + cur * TI;
+        __syncthreads();                                     // the previous tile's MFMA reads and its reads of msk, lm and the ids are done
+        tile_store(E_l, pre, tid);
+        if (wave == 0 && s + 1 < s_end) {                    // the other slot's last readers (tile s - 1) are behind the barrier above
+            idl[(cur ^ 1) * TI + lane] = nid;
+            if (lane == 0) lm[cur ^ 1] = nlm;
+        }
+        if (a.seen) {                                        // thread (row = tid / 8, part = tid % 8): the 8 lanes of a row are neighbours
+            const int row = tid >> 3, b = bc * TB + row;
+            const int lo = ids[0], hi = ids[TI - 1];
+            u64 m = 0;
+            if (b < a.B)
+                for (int t = tid & 7; t < a.seen_ld; t += 8) {
+                    const int sid = a.seen[(size_t)b * a.seen_ld + t];
+                    if (sid < lo || sid > hi) continue;
+                    int x = 0;                               // the first position whose id is >= sid: x + h - 1 <= 62, x <= 63
+#pragma unroll
+                    for (int h = TI / 2; h; h >>= 1)
+                        if (ids[x + h - 1] < sid) x += h;
+                    if (ids[x] == sid) m |= 1ull << x;
+                }
+            m |= __shfl_xor(m, 1, 64); m |= __shfl_xor(m, 2, 64); m |= __shfl_xor(m, 4, 64);
+            if ((tid & 7) == 0) msk[row] = m;
+        }
+        __syncthreads();
+        if (s + 1 < s_end) tile_load_ids(pre, a.emb1, idl + (cur ^ 1) * TI, lm[cur ^ 1], H, tid);
+        if (wave == 0 && s + 2 < s_end) fetch_ids(s + 2);
+        f32x4 acc[2];
+        acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        mma_tile<2>(E_l + mw * 16 * LDE, LDE, 1, R_l + nw * 32 * LDE, 1, LDE, ksteps, acc, lane);
+        const int il0 = mw * 16 + q * 4;                     // this lane's 4 consecutive positions of the tile
+        const u64 dead = ~lm[cur];
+        int id4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) id4[r] = ids[il0 + r];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int bl = nw * 32 + j * 16 + r16;           // batch row within the chunk
+            const unsigned sm = (unsigned)((msk[bl] | dead) >> il0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                // the target never counts itself, listed or not, seen or not (MODE_RANK's rule)
+                const bool in = !((sm >> r) & 1u) && id4[r] <= nc[j] && id4[r] != tg[j];
+                cnt[j] += in && ((acc[j][r] > tl[j]) || (acc[j][r] == tl[j] && id4[r] < tg[j]));
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        int c = cnt[j];
+        c += __shfl_xor(c, 16, 64);
+        c += __shfl_xor(c, 32, 64);
+        if (q == 0 && c) atomicAdd(a.rank + bc * TB + nw * 32 + j * 16 + r16, c);
+    }
+}
+
 // ============================================================================================= wide answers, k up to 1024: slab and select
 // k_topk_tile keeps k + 64 keys per row in LDS, which ends at k = 64; here no buffer in LDS grows with k.
 // Per row, in global memory: a list of cap 64-bit keys, a count, a threshold key (0 = none yet) and a status word.  The catalog is
@@ -443,6 +578,10 @@ static inline int wide_runs(int ntile, int nchunk) {
     return ntile < target ? ntile : target;
 }
 
+// in logits.hip: the exact-f32 logit of every row's target (k_target_logit), what ader_rank_targets compares against
+int rank_target_logit_launch(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
+                             float* tlogit, void* stream);
+
 extern "C" {
 
 // ader_topk_ranges: item ranges per 64-row chunk -- about one workgroup per CU over the Bp/64 chunks, a multiple of 8 (the block ->
@@ -497,6 +636,29 @@ int ader_topk_items_cand(const float* rep, const float* emb, int B, int Bp, int 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_topk_cand, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, ca);
     hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, st, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+// rank[b] = #{c in cand[0:M] : 1 <= c <= min(N, ncol[b]), c != t, c not in seen[b], s(b,c) > s(b,t) or (== and c < t)}, t = target[b]:
+// ader_rank_targets' count over ader_topk_items_cand's list (same cand, M, N, seen, status and -2 conditions).  tlogit: Bp floats of
+// scratch; rank: [Bp] (zeroed here).  M = 0: the clear of rank and nothing else.  Enqueue only.
+int ader_rank_targets_cand(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
+                           const int* cand, int M, const int* seen, int seen_ld, float* tlogit, int* rank, int* status, void* stream) {
+    if (topk_bad(B, Bp, H, N, seen, seen_ld, 1, 1) || M < 0 || (M > 0 && !cand)) return -2;
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(rank, 0, sizeof(int) * (size_t)Bp, st);
+    if (e != hipSuccess) return (int)e;
+    if (M == 0) return 0;
+    const size_t lds = tile_lds(TB * sizeof(u64) + 2 * sizeof(u64) + 2 * TI * sizeof(int));      // msk, lm, idl
+    int rc = ader_dyn_lds<k_rank_cand>(lds);
+    if (rc) return rc;
+    rc = rank_target_logit_launch(rep, emb, B, Bp, H, N, target, ncol, tlogit, stream);
+    if (rc) return rc;
+    RankCandArgs a;
+    a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.target = target; a.ncol = ncol; a.seen = seen;
+    a.seen_ld = seen_ld; a.ranges = ader_topk_ranges(M, Bp); a.cand = cand; a.M = M; a.tlogit = tlogit; a.rank = rank; a.status = status;
+    hipLaunchKernelGGL(k_rank_cand, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, a);
     HIP_LAUNCH_CHECK();
     return 0;
 }

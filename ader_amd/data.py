@@ -483,16 +483,26 @@ class Evaluator:
     """Evaluates the rank of the ground-truth next item among all `max_item` items
     (reference util.py:276-350).  `model.predict(sess, seq, item_idx)` must return the full rank
     matrix as in the reference; when the model offers `rank_targets(seq, pos, max_item)` (the HIP
-    count-greater kernel) that is used instead -- only pred[label-1] is ever read (util.py:325)."""
+    count-greater kernel) that is used instead -- only pred[label-1] is ever read (util.py:325).
+    candidates (item ids, as Engine.recommend_among takes them) and / or exclude_seen: beside `ranks`, which stay what they are, the
+    same pass fills `ranks_among` -- the target's rank among the listed items of 1..max_item (None: all of them), without the
+    session's own items under exclude_seen -- by one `model.rank_targets_among` call; results_among() / display_among() report it."""
 
     _packed = {}        # (id(data), len, maxlen, is_subseq) -> (data, (prepared_data, rows, valid)): see __init__
 
-    def __init__(self, data, is_subseq, maxlen, batch_size, max_item, mode, model, sess, shard=(0, 1)):
+    def __init__(self, data, is_subseq, maxlen, batch_size, max_item, mode, model, sess, shard=(0, 1), candidates=None,
+                 exclude_seen=False):
         self.shard = shard          # (rank, world): evaluation batches are independent units (SURVEY 8e)
         self.max_item = max_item
         self.model = model
         self.sess = sess
         self.ranks = []
+        self.candidates, self.exclude_seen = candidates, bool(exclude_seen)
+        self.among = candidates is not None or self.exclude_seen
+        self.ranks_among = []
+        if self.among and getattr(model, "rank_targets_among", None) is None:
+            raise RuntimeError("Evaluator(candidates=..., exclude_seen=...) needs a model with rank_targets_among(seq, pos, max_item, "
+                               "candidates, exclude_seen); %s has none" % type(model).__name__)
         self.mode = mode
         self.desc = 'Validating epoch ' if mode == 'valid' else 'Testing epoch '
         # (the packed rows of an unchanged session list are kept between evaluators -- one is built per epoch, main.py:264-266 -- and
@@ -519,10 +529,13 @@ class Evaluator:
         fast = getattr(self.model, "rank_targets", None)
         mine = []                    # [(batch index, ranks)] of the batches this rank evaluates
         todo = []                    # fast path: (batch index, seq, pos) of this rank's batches, ranked by ONE call below
+        rows = []                    # candidates / exclude_seen: the same, whichever path gives `ranks`
         for b in range(self.evaluate_sampler.batch_num()):
             seq, pos = self.evaluate_sampler.next_batch()       # every rank walks the same batch sequence
             if len(pos) == 0 or b % world != rank:
                 continue
+            if self.among:
+                rows.append((b, seq, pos))
             if fast is not None:
                 todo.append((b, seq, pos))
             else:
@@ -541,10 +554,46 @@ class Evaluator:
             from . import dist as _dist
             mine = sorted(x for part in _dist.gather_lists(mine, world) for x in part)
         self.ranks = [x for _, r in mine for x in r]
+        if self.among:
+            among = []
+            if rows:                 # one more call on the same concatenated rows
+                r = np.asarray(self.model.rank_targets_among(np.concatenate([s_ for _, s_, _ in rows]),
+                                                             np.concatenate([p_ for _, _, p_ in rows]), self.max_item,
+                                                             self.candidates, self.exclude_seen)).tolist()
+                o = 0
+                for b, _, pos in rows:
+                    among.append((b, r[o:o + len(pos)]))
+                    o += len(pos)
+            if world > 1:
+                from . import dist as _dist
+                among = sorted(x for part in _dist.gather_lists(among, world) for x in part)
+            self.ranks_among = [x for _, r in among for x in r]
         return self.display(epoch)
 
     def results(self):
         return recall_mrr(self.ranks)
+
+    def n_candidates(self):
+        """Distinct candidate ids within 1..max_item: what a target is ranked among by ranks_among (before exclude_seen)."""
+        if self.candidates is None:
+            return int(self.max_item)
+        c = self.candidates
+        c = c.detach().cpu().numpy() if hasattr(c, "detach") else np.asarray(c)
+        return int(np.unique(c[c <= self.max_item]).size)
+
+    def results_among(self):
+        """recall_mrr of ranks_among (an Evaluator built with candidates or exclude_seen, after evaluate())."""
+        if not self.among:
+            raise RuntimeError("results_among: this Evaluator was built without candidates / exclude_seen")
+        return recall_mrr(self.ranks_among)
+
+    def display_among(self, epoch):
+        r = self.results_among()
+        info = 'epoch:%d, %s among %d candidate items%s (MRR@20: %.4f, RECALL@20: %.4f, MRR@10: %.4f, RECALL@10: %.4f)' \
+               % (epoch, self.mode, self.n_candidates(), ', seen items excluded' if self.exclude_seen else '', r[0], r[1], r[2], r[3])
+        if self.shard[0] == 0:
+            print(info)
+        return info
 
     def display(self, epoch):
         r = self.results()

@@ -159,6 +159,42 @@ class _Infer:
             out[s:e] = rk[:B]
         return out.cpu().numpy()
 
+    def rank_targets_among(self, seq, pos, max_item, candidates=None, exclude_seen=False):
+        """rank_targets restricted to a candidate item list, what scores recommend_among: the 0-based rank of pos[b] among
+        set(candidates) within [1, max_item], minus the row's seen ids under exclude_seen -> int32 numpy [n].  candidates as
+        recommend_among's (candidate_ids: any order, duplicates allowed, every id in [1, item_num]); None: every item of 1..max_item,
+        which with exclude_seen=False is rank_targets(dtype="f32").  The target need not be listed and never counts itself, listed or
+        seen.  Scores, tie rule (score descending, id ascending) and list are recommend_among's, so for (items, _) =
+        recommend_among(seq, k, c, N, exclude_seen=e): rank_targets_among(seq_b, items[b, j], N, c, exclude_seen=e) == j wherever
+        items[b, j] > 0.  The list's table rows are gathered inside the kernel (ader_rank_targets_cand, k_rank_cand): the work follows
+        len(candidates), not max_item.  Exact-f32 chain whatever rank_dtype says (the x3 filter walks contiguous tiles only).  The list
+        is copied to the device once, chunks of MAX_ROWS rows, one device -> host copy."""
+        N = int(max_item)
+        _check(1 <= N <= self.item_num, "rank_targets_among: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        cand = np.arange(1, N + 1, dtype=np.int32) if candidates is None else candidate_ids(candidates, N, self.item_num)
+        self._refresh_stream()
+        self.sync_table()
+        seq = self._seq_in(seq)
+        pos = self._dev_i32(pos)
+        n, M = seq.shape[0], int(cand.shape[0])
+        cand_d = torch.from_numpy(cand).to(self.device) if M else None
+        out = torch.empty(n, dtype=torch.int32, device=self.device)
+        for s in range(0, n, self.MAX_ROWS):
+            e = min(n, s + self.MAX_ROWS)
+            B = e - s
+            Bp = (B + 63) // 64 * 64
+            rep = self.forward(seq[s:e], training=False)
+            tl = self.buf("rkc_tl", (Bp,))
+            rk = self.buf("rkc_rank", (Bp,), torch.int32)
+            tgt = self.buf("rkc_tgt", (Bp,), torch.int32)
+            tgt.zero_()
+            tgt[:B] = pos[s:e]
+            call("ader_rank_targets_cand", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(tgt), ptr(self._ncol_all(Bp, B, N)),
+                 ptr(cand_d), M, ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], ptr(tl), ptr(rk), ptr(self.status),
+                 self._stream())
+            out[s:e] = rk[:B]
+        return out.cpu().numpy()
+
     def _rank_targets_x3(self, seq, pos, max_item, cand_cap):
         """rank_targets on the bf16 matrix cores (ader_rank_targets_x3): per 128-row-padded chunk the x3 filter decides every (row, item)
         whose x3 logit is outside the band tl +- delta, the exact-f32 recheck decides the listed rest; a chunk whose list overflowed is

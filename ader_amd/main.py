@@ -7,7 +7,7 @@ Differences from the reference that do not change results: booleans are parsed w
 batches and teacher logits stay on the GPU (the reference feeds Python float lists every step, util.py:254);
 the best-epoch checkpoint is kept in memory and written to disk only with --save_ckpt.
 Extra flags: --logits_dtype, --max_periods, --data_root, --save_ckpt, --eval_batch (--test_batch is accepted and ignored:
-ranks do not depend on the evaluation batch size), --dist_backend, --device_feed, --teacher_form.
+ranks do not depend on the evaluation batch size), --dist_backend, --device_feed, --teacher_form, --eval_among.
 
 Data parallel: launched as `python -m torch.distributed.run --nproc-per-node W -m ader_amd.main ...` every
 rank builds the same batches from the same RNG streams, trains on its slice of the train rows and of the exemplar rows
@@ -52,6 +52,10 @@ _REFERENCE_FLAGS = (
 # Flags of this build only: (flag, default, type, help / choices)
 _BUILD_FLAGS = (
     ("logits_dtype", "x3", str, ("f32", "bf16", "x3")), ("rank_dtype", "f32", str, ("f32", "x3")), ("topk_dtype", "f32", str, ("f32", "x3")), ("max_periods", 0, int, None), ("data_root", None, str, None),
+    # what a period's TEST targets are ranked among, beside the whole catalog (which is always reported, unchanged): "period" adds a
+    # second line and the summary keys among_*, the rank among the items that occur in the period's own training sessions
+    # (Evaluator(candidates=...), Engine.rank_targets_among); "catalog": nothing more
+    ("eval_among", "catalog", str, ("catalog", "period")),
     ("results_root", "results", str, None), ("save_ckpt", False, bool, None),
     ("dist_backend", "nccl", str, "torch.distributed backend when WORLD_SIZE > 1"),
     ("device_feed", True, bool, "keep the packed training rows on the GPU and gather batches there"),
@@ -88,6 +92,13 @@ def build_parser():
 
 
 ITEM_NUM = {'DIGINETICA': 43136, 'YOOCHOOSE': 25958}     # main.py:133-138
+
+
+def period_items(sessions, max_item):
+    """The distinct item ids <= max_item of a session list, inputs and labels alike, ascending (--eval_among period: the candidate
+    list of the period's test evaluator)."""
+    ids = np.fromiter((i for s in sessions for i in s), dtype=np.int64)
+    return np.unique(ids[(ids >= 1) & (ids <= max_item)])
 
 
 class _NullLog:
@@ -164,6 +175,7 @@ def run(args, log=print):
         test_sess, info = dataloader.evaluate_loader(period)
         logs.write(info + '\n')
         max_item = dataloader.max_item()
+        among = period_items(train_sess, max_item) if getattr(args, "eval_among", "catalog") == "period" else None
         use_ex = period > 1 and not baseline
         if use_ex:
             # (the reference flattens {item: [[session, logits], ...]} into a list, main.py:54-65,176-190; the store holds the same
@@ -277,13 +289,19 @@ def run(args, log=print):
             if period_best is None:                                      # no epoch improved on 0: keep the last state
                 best_state = model.engine.state_dict()
             model.engine.load_state_dict(best_state)                    # saver.restore(best), main.py:283
-            test_evaluator = Evaluator(test_sess, False, args.maxlen, args.eval_batch, max_item, 'test', model, sess, shard)
+            test_evaluator = Evaluator(test_sess, False, args.maxlen, args.eval_batch, max_item, 'test', model, sess, shard,
+                                       candidates=among)
             info = test_evaluator.evaluate(best_epoch)
             logs.write(info + '\n')
             r = test_evaluator.results()
             MRR_20.append(r[0]); Recall_20.append(r[1]); MRR_10.append(r[2]); Recall_10.append(r[3])
             summary.append({"period": period, "best_epoch": best_epoch, "mrr20": r[0], "recall20": r[1], "mrr10": r[2],
                             "recall10": r[3], "max_item": max_item})
+            if among is not None:                                        # --eval_among period: the same targets among the period's items
+                logs.write(test_evaluator.display_among(best_epoch) + '\n')
+                ra = test_evaluator.results_among()
+                summary[-1].update({"among_mrr20": ra[0], "among_recall20": ra[1], "among_mrr10": ra[2], "among_recall10": ra[3],
+                                    "among_items": test_evaluator.n_candidates()})
             if not baseline:                                             # exemplar selection, main.py:294-313
                 exemplar_candidate = train_subseq
                 exemplar_candidate.extend(valid_subseq)

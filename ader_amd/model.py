@@ -77,6 +77,11 @@ class Ader:
     def rank_targets(self, seq, pos, max_item):
         return self.engine.rank_targets(seq, pos, max_item)
 
+    def rank_targets_among(self, seq, pos, max_item, candidates=None, exclude_seen=False):
+        """Rank of every row's target among a candidate item list and / or without the row's seen ids (Engine.rank_targets_among):
+        what scores recommend(candidates=..., exclude_seen=...)."""
+        return self.engine.rank_targets_among(seq, pos, max_item, candidates, exclude_seen)
+
     def recommend(self, seq, k, max_item=None, exclude_seen=False, dtype=None, candidates=None):
         """The k best items per session, (items int32 [n,k], scores float32 [n,k]): Engine.recommend (dtype None: --topk_dtype);
         candidates: item ids the answer may come from (Engine.recommend_among), None: the whole catalog.  k above ader_topk_kmax()

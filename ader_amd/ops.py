@@ -13,6 +13,8 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
   ader::rank_of_target(rep, emb, target, N)                    -> rank   ADER.py:99-103 + util.py:325
   ader::rank_of_target_x3(rep, emb, target, N)                 -> rank   the same ranks; products on the bf16 matrix cores (x3 filter
                                                                          + exact-f32 recheck of the undecided pairs)
+  ader::rank_of_target_cand(rep, emb, target, cand, seen, N)   -> rank   rank_of_target over the ids of one ascending candidate list,
+                                                                         minus the row's seen ids: what scores topk_items_cand
   ader::topk_items(rep, emb, seen, N, k)                       -> (items, scores)   the k best items per row, fused with the logits:
                                                                          order and bits of argsort(-logits) (ADER.py:92, 103)
   ader::topk_items_cand(rep, emb, cand, seen, N, k)            -> (items, scores)   topk_items over the ids of one ascending candidate
@@ -257,6 +259,41 @@ def topk_items_cand(rep: torch.Tensor, emb: torch.Tensor, cand: torch.Tensor, se
 
 
 topk_items_cand.register_fake(_topk_fake)
+
+
+@torch.library.custom_op("ader::rank_of_target_cand", mutates_args=())
+def rank_of_target_cand(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, cand: torch.Tensor, seen: Optional[torch.Tensor],
+                        N: int) -> torch.Tensor:
+    """rank_of_target over the items of cand only (cand, seen and N as topk_items_cand's): rank int32 [B] = the number of ids of cand
+    in [1, N], other than the row's target and its seen ids, that precede the target by (logit descending, id ascending) -- so the
+    rank of topk_items_cand's items[b, j] > 0 over the same arguments is j.  The target (in [1, N]) need not be in cand.  A list that
+    is not strictly ascending, or holds an id < 1, raises (one synchronisation to read the status)."""
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(target, "target", torch.int32, 1)
+    _chk(cand, "cand", torch.int32, 1)
+    B, H = rep.shape
+    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or target.shape[0] != B or B > 1024:
+        raise RuntimeError("ader::rank_of_target_cand: bad shapes")
+    if seen is not None:
+        _chk(seen, "seen", torch.int32, 2)
+        if seen.shape[0] != B or seen.shape[1] < 1:
+            raise RuntimeError("ader::rank_of_target_cand: seen must be [B, S] with S >= 1")
+    Bp = (B + 63) // 64 * 64
+    dev = rep.device
+    tgt, ncol = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, dtype=torch.int32, device=dev)
+    tgt[:B], ncol[:B] = target, N
+    tl, rk = torch.empty(Bp, device=dev), torch.empty(Bp, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    M = cand.shape[0]
+    call("ader_rank_targets_cand", ptr(rep), ptr(emb), B, Bp, H, N, ptr(tgt), ptr(ncol), ptr(cand) if M else None, M, ptr(seen),
+         seen.shape[1] if seen is not None else 0, ptr(tl), ptr(rk), ptr(status), _st())
+    if int(status.item()):
+        raise RuntimeError("ader::rank_of_target_cand: cand must be strictly ascending item ids >= 1")
+    return rk[:B].clone()
+
+
+@rank_of_target_cand.register_fake
+def _(rep, emb, target, cand, seen, N):
+    return target.new_empty(rep.shape[0])
 
 
 @torch.library.custom_op("ader::topk_items_x3", mutates_args=())

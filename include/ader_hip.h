@@ -269,6 +269,17 @@ int ader_topk_items(const float* rep, const float* emb, int B, int Bp, int H, in
 int ader_topk_items_cand(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* cand, int M,
                          const int* seen, int seen_ld, int k, unsigned long long* part, int* items, float* scores, int* status,
                          void* stream);
+/* ader_rank_targets over the same kind of candidate list, the evaluation-side twin of ader_topk_items_cand: for every real row b with
+ * t = target[b] in [1, N], rank[b] = the number of ids c of cand[0:M] with 1 <= c <= min(N, ncol[b]), c != t, c not among the non-zero
+ * ids of seen[b, 0:seen_ld] (if seen), and s(b,c) > s(b,t) or (s(b,c) == s(b,t) and c < t): the scores and the tie rule of
+ * ader_topk_items_cand, so that for its items[b, j] > 0 the rank over the same list, seen ids and N is j.  The target need not be in
+ * the list and never counts itself, listed or seen.  cand, M, N, seen, ncol and status as ader_topk_items_cand (ids above N ignored,
+ * bit 4 of status for a list that is not strictly ascending or holds an id < 1, nothing outside the table read for any list).
+ * tlogit: Bp floats of scratch (the target's logit, by ader_rank_targets' own kernel); rank: [Bp], zeroed here; padding rows get 0.
+ * M = 0: every rank is 0 and nothing but the clear of rank is enqueued.  Integer counts only: a pure function of the inputs.
+ * Enqueue only.  -2 when Bp % 64 != 0, Bp > 1024, B > Bp, H > 160, N < 1, M < 0, M > 0 with cand == NULL, or seen with seen_ld < 1. */
+int ader_rank_targets_cand(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
+                           const int* cand, int M, const int* seen, int seen_ld, float* tlogit, int* rank, int* status, void* stream);
 /* ader_topk_items with the [B,N] products on the bf16 matrix cores: k_lx3t keeps, per row and item range, every item whose x3 logit is
  * not provably below the row's k-th best by delta[b] = 2^-13 |rep_b| emax[0] (a superset of the exact top-k, at most k + band keys), and
  * k_topk3_finish merges the ranges, re-evaluates the kept pairs through the exact-f32 MFMA chain and selects: for every row with

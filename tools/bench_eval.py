@@ -2,6 +2,7 @@
 """Evaluation ranking, "x3" against the exact-f32 kernel (Engine.rank_targets dtype= / --rank_dtype): times, candidate shares, the bound.
 
     python tools/bench_eval.py [--check] [--reps 5] [--warmup 2] [--train_steps 200] [--out profiles/eval_x3.txt]
+    python tools/bench_eval.py --among [...]      the candidate-list rank instead (measure_among below), to profiles/rank_cand.txt
 
 Shapes: (a) the last test period of data/YOOCHOOSE.npz and data/DIGINETICA.npz -- the rows the product's DataLoader / Evaluator hand to
 model.rank_targets; (b) 4,096 synthetic rows at N = 10^6.  Per shape and dtype, device events around (1) the whole rank_targets call
@@ -124,6 +125,98 @@ def measure(name, eng, seq, pos, N, reps, warmup):
     return equal
 
 
+def among_launches(eng, rep, pos, seq, N, cand, exclude):
+    """The rank launches of Engine.rank_targets_among alone, on precomputed representations (no forward, no copy back)."""
+    st = torch.cuda.current_stream().cuda_stream
+    n, M = rep.shape[0], cand.shape[0]
+    for s in range(0, n, eng.MAX_ROWS):
+        e = min(n, s + eng.MAX_ROWS)
+        B = e - s
+        Bp = (B + 63) // 64 * 64
+        tgt = eng.buf("be_tgt", (Bp,), torch.int32)
+        tgt.zero_()
+        tgt[:B] = pos[s:e]
+        call("ader_rank_targets_cand", ptr(rep[s:e]), eng._pp["emb"], B, Bp, eng.H, N, ptr(tgt), ptr(eng._ncol_all(Bp, B, N)), ptr(cand), M,
+             ptr(seq[s:e]) if exclude else None, seq.shape[1], ptr(eng.buf("be_tl", (Bp,))), ptr(eng.buf("be_rk", (Bp,), torch.int32)),
+             ptr(eng.status), st)
+
+
+def torch_among(eng, seq, pos, N, cand, exclude):
+    """What a user composes without the kernel: dense Engine.logits, the list, the seen ids and the target's column masked out, the
+    count of (lg > tl) | (lg == tl and id < t) -- in row groups whose logits stay near 1 GB."""
+    dev, n = eng.device, seq.shape[0]
+    listed = torch.zeros(N + 1, dtype=torch.bool, device=dev)
+    listed[cand.long()] = True
+    ids = torch.arange(1, N + 1, device=dev)
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    group = max(1, 256_000_000 // N)
+    for s in range(0, n, group):
+        e = min(n, s + group)
+        lg = eng.logits(seq[s:e], N)
+        t = pos[s:e].long()
+        tl = lg.gather(1, (t - 1)[:, None])
+        ahead = ((lg > tl) | ((lg == tl) & (ids[None, :] < t[:, None]))) & listed[None, 1:]
+        ahead.scatter_(1, (t - 1)[:, None], False)
+        if exclude:
+            sid = seq[s:e].long()
+            sid = torch.where(sid <= N, sid, torch.zeros_like(sid))                  # column 0 = "no id" (and ids above N)
+            ahead = torch.cat([torch.zeros((e - s, 1), dtype=torch.bool, device=dev), ahead], 1)
+            ahead.scatter_(1, sid, False)
+        out[s:e] = ahead.sum(1)
+    return out.cpu().numpy()
+
+
+def measure_among(name, eng, seq, pos, N, reps, warmup):
+    """--among: rank_targets_among over a random tenth of the ids and over all ids, against rank_targets (f32) and against the torch
+    composition for the tenth, alternating inside every repetition.  The work of k_rank_cand follows the list: the tenth should cost
+    well under the whole-catalog rank launches; what is printed is what was measured."""
+    n = len(pos)
+    seq_d, pos_d = torch.from_numpy(seq).to(eng.device), torch.from_numpy(pos).to(eng.device)
+    rep = eng.encode(seq_d)
+    rs = np.random.RandomState(0)
+    tenth = np.sort(rs.choice(N, size=max(N // 10, 1), replace=False)).astype(np.int32) + 1
+    lists = {"tenth": torch.from_numpy(tenth).to(eng.device), "all": torch.arange(1, N + 1, dtype=torch.int32, device=eng.device)}
+    calls = {"rank_targets f32": lambda: eng.rank_targets(seq_d, pos_d, N, dtype="f32"),
+             "among all ids": lambda: eng.rank_targets_among(seq_d, pos_d, N, lists["all"]),
+             "among N/10": lambda: eng.rank_targets_among(seq_d, pos_d, N, lists["tenth"]),
+             "among N/10, seen excluded": lambda: eng.rank_targets_among(seq_d, pos_d, N, lists["tenth"], exclude_seen=True),
+             "torch logits+mask+count N/10": lambda: torch_among(eng, seq_d, pos_d, N, lists["tenth"], False)}
+    launches = {"rank_targets f32": lambda: rank_launches(eng, rep, pos_d, N, "f32"),
+                "among all ids": lambda: among_launches(eng, rep, pos_d, seq_d, N, lists["all"], False),
+                "among N/10": lambda: among_launches(eng, rep, pos_d, seq_d, N, lists["tenth"], False),
+                "among N/10, seen excluded": lambda: among_launches(eng, rep, pos_d, seq_d, N, lists["tenth"], True)}
+    tw, tl, res = {k: [] for k in calls}, {k: [] for k in launches}, {}
+    for it in range(warmup + reps):
+        for k in calls:                                                # alternating inside every repetition
+            t, res[k] = ev_time(calls[k])
+            if it >= warmup:
+                tw[k].append(t)
+            if k in launches:
+                t, _ = ev_time(launches[k])
+                if it >= warmup:
+                    tl[k].append(t)
+    eng.check_status()
+    med = statistics.median
+    say("== %s: %d rows, N = %d, list of %d ids; %d repetitions after %d warm-up, medians [min .. max]" % (name, n, N, len(tenth), reps, warmup))
+    for k in calls:
+        w = tw[k]
+        line = "  %-30s whole call %9.2f ms [%.2f .. %.2f]" % (k, med(w) * 1e3, min(w) * 1e3, max(w) * 1e3)
+        if k in launches:
+            l = tl[k]
+            line += " | rank launches %9.3f ms [%.3f .. %.3f]" % (med(l) * 1e3, min(l) * 1e3, max(l) * 1e3)
+        say(line)
+    base = med(tl["rank_targets f32"])
+    say("  rank launches over rank_targets f32's: among all ids %.3f, among N/10 %.3f, among N/10 seen excluded %.3f; whole call, torch "
+        "composition over among N/10: %.1f" % (med(tl["among all ids"]) / base, med(tl["among N/10"]) / base,
+                                              med(tl["among N/10, seen excluded"]) / base,
+                                              med(tw["torch logits+mask+count N/10"]) / med(tw["among N/10"])))
+    ok = bool(np.array_equal(res["among all ids"], res["rank_targets f32"]))
+    ok &= bool(np.array_equal(res["among N/10"], res["torch logits+mask+count N/10"]))
+    ok &= bool(np.array_equal(res["among N/10, seen excluded"], torch_among(eng, seq_d, pos_d, N, lists["tenth"], True)))
+    say("  among all ids == rank_targets, among N/10 == the torch composition (with and without seen ids): %s" % ok)
+    return ok
+
+
 def dataset(name, args):
     """Measures the last test period; returns (ok, check) where check() compares the two dtypes on every earlier test period."""
     dl = DataLoader(name)
@@ -146,7 +239,7 @@ def dataset(name, args):
         if period == periods or args.check:
             rows.append((period, N) + evaluator_rows(test_sess, N, args.eval_batch))
     period, N, seq, pos = rows.pop()
-    ok = measure("%s, test period %d" % (name, period), eng, seq, pos, N, args.reps, args.warmup)
+    ok = (measure_among if args.among else measure)("%s, test period %d" % (name, period), eng, seq, pos, N, args.reps, args.warmup)
 
     def check():
         good = True
@@ -169,7 +262,7 @@ def synthetic(args):
         ln = int(rs.randint(1, T + 1))
         seq[b, T - ln:] = rs.randint(1, N + 1, size=ln)
     pos = rs.randint(1, N + 1, size=B).astype(np.int32)
-    return measure("synthetic", eng, seq, pos, N, max(args.reps // 2, 2), 1)
+    return (measure_among if args.among else measure)("synthetic", eng, seq, pos, N, max(args.reps // 2, 2), 1)
 
 
 def main():
@@ -181,13 +274,23 @@ def main():
     ap.add_argument("--eval_batch", type=int, default=1024)
     ap.add_argument("--synthetic_rows", type=int, default=4096)
     ap.add_argument("--datasets", default="YOOCHOOSE,DIGINETICA")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "eval_x3.txt"))
+    ap.add_argument("--among", action="store_true", help="measure Engine.rank_targets_among (k_rank_cand) over a list of N/10 and of all "
+                    "ids against rank_targets f32 and against Engine.logits + mask + count in torch; writes profiles/rank_cand.txt")
+    ap.add_argument("--out", default=None, help="profiles/eval_x3.txt, with --among profiles/rank_cand.txt")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_eval.py measures on the GPU: no device found")
-    _out.append(open(args.out, "w"))
-    say("# tools/bench_eval.py%s: Engine.rank_targets, dtype x3 (k_lx3k filter + exact recheck) against f32 (k_logits_tile<RANK>), same "
-        "process, alternating; %s" % (" --check" if args.check else "", torch.cuda.get_device_name(0)))
+    if args.among and args.check:
+        raise SystemExit("--check compares the two rank dtypes: not with --among")
+    _out.append(open(args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                              "rank_cand.txt" if args.among else "eval_x3.txt"), "w"))
+    if args.among:
+        say("# tools/bench_eval.py --among: Engine.rank_targets_among (k_rank_cand, gathered tiles) over a random tenth of the ids and over "
+            "all ids, against Engine.rank_targets f32 (k_logits_tile<RANK>) and dense logits + mask + count in torch, same process, "
+            "alternating; %s" % torch.cuda.get_device_name(0))
+    else:
+        say("# tools/bench_eval.py%s: Engine.rank_targets, dtype x3 (k_lx3k filter + exact recheck) against f32 (k_logits_tile<RANK>), "
+            "same process, alternating; %s" % (" --check" if args.check else "", torch.cuda.get_device_name(0)))
     ok, checks = True, []
     for name in [d for d in args.datasets.split(",") if d]:
         good, check = dataset(name, args)
@@ -198,6 +301,8 @@ def main():
     for check in checks:                                           # (the measurements first: the checks are the long part)
         ok &= check()
     say("# ranks equal everywhere: %s" % ok)
+    if args.among and not ok:
+        raise SystemExit("rank mismatch between rank_targets_among and its references")
     if args.check and not ok:
         raise SystemExit("rank mismatch between x3 and f32")
 
