@@ -100,6 +100,10 @@ _SIGS = {
     "ader_topk_items": [P, P, I, I, I, I, P, P, I, I, P, P, P, P],
     "ader_topk_items_cand": [P, P, I, I, I, I, P, P, I, P, I, I, P, P, P, P, P],
     "ader_rank_targets_cand": [P, P, I, I, I, I, P, P, P, I, P, I, P, P, P, P],
+    "ader_score_items": [P, P, I, I, I, P, P, I, I, P, I, P],
+    "ader_topk_rows_ranges": [I, I],
+    "ader_topk_items_rows": [P, P, I, I, I, I, P, P, I, I, P, I, I, P, P, P, P, P],
+    "ader_rank_targets_rows": [P, P, I, I, I, I, P, P, P, I, I, P, I, P, P, P, P],
     "ader_topk_x3_kmax": [],
     "ader_topk_x3_ranges": [I, I],
     "ader_topk_items_x3": [P, P, I, I, I, I, I, P, P, I, I, I, P, P, P, P, P, P, P, P, P, P],
@@ -204,7 +208,7 @@ class AderStepKey(ctypes.Structure):
     _fields_ = [("blob", c_int), ("site", c_int), ("offset", c_size_t)]
 
 
-_NO_CHECK = {"ader_step_fn_index", "ader_step_fn_args", "ader_step_plan_failed_op", "ader_ln_bwd_slabs", "ader_gemm_atb_batch_slabs", "ader_gemm_atb_slabs", "ader_logits_sub", "ader_logits_parts", "ader_logits_ranges", "ader_lbf_ranges", "ader_lbf_ranges_kd", "ader_lbf_readout_ranges", "ader_lx3_readout_ranges", "ader_wprep_elems", "ader_fused_bucket_gran", "ader_fused_bucket_id0", "ader_tab_meta_ints", "ader_x3_rep_image_bytes", "ader_sparse_lists_scratch_n", "ader_sparse_lists_starts", "ader_topk_kmax", "ader_topk_ranges", "ader_topk_x3_kmax", "ader_topk_x3_ranges", "ader_topk_wide_kmax", "ader_topk_wide_cap", "ader_topk_wide_slabs", "ader_teacher_ranges"}
+_NO_CHECK = {"ader_step_fn_index", "ader_step_fn_args", "ader_step_plan_failed_op", "ader_ln_bwd_slabs", "ader_gemm_atb_batch_slabs", "ader_gemm_atb_slabs", "ader_logits_sub", "ader_logits_parts", "ader_logits_ranges", "ader_lbf_ranges", "ader_lbf_ranges_kd", "ader_lbf_readout_ranges", "ader_lx3_readout_ranges", "ader_wprep_elems", "ader_fused_bucket_gran", "ader_fused_bucket_id0", "ader_tab_meta_ints", "ader_x3_rep_image_bytes", "ader_sparse_lists_scratch_n", "ader_sparse_lists_starts", "ader_topk_kmax", "ader_topk_ranges", "ader_topk_rows_ranges", "ader_topk_x3_kmax", "ader_topk_x3_ranges", "ader_topk_wide_kmax", "ader_topk_wide_cap", "ader_topk_wide_slabs", "ader_teacher_ranges"}
 
 
 class AderHipError(RuntimeError):

@@ -7,6 +7,10 @@
 //   k_topk_wide_tile + k_topk_wide_select    all items 1..N, k <= 1024, slab and select   (Engine.recommend_wide, ader_topk_items_wide)
 // and the evaluation-side twin of the second form, the rank of a row's target under the same order:
 //   k_rank_cand                              the items of one ascending id list           (Engine.rank_targets_among, ader_rank_targets_cand)
+// and the forms whose list differs from row to row, ids [B, ld]: one kernel, a tile = 64 positions of ONE row's list
+//   k_rowlist<STORE>                         the scores of the listed items, any ids      (Engine.score_items, ader_score_items)
+//   k_rowlist<KEYS> + k_topk_merge           the k <= 64 best of each row's own list      (Engine.recommend_per_row, ader_topk_items_rows)
+//   k_rowlist<RANK>                          the target's rank among each row's own list  (Engine.rank_targets_per_row, ader_rank_targets_rows)
 // A candidate is one 64-bit key (topk_key.h): order-preserving float bits above, the complemented 1-based item id below, so ONE unsigned
 // compare is the total order and no two candidates of a row compare equal.  Key 0 = "no candidate".  (The MFMA chain starts from +0 and
 // rounds to nearest, so it never yields -0; topk_key still folds -0 onto +0, as == does.)
@@ -387,6 +391,140 @@ __global__ __launch_bounds__(512) void k_rank_cand(RankCandArgs a) {
     }
 }
 
+// ============================================================================================= every row's own item list
+// ader_score_items / ader_topk_items_rows / ader_rank_targets_rows: the list differs from row to row -- ids [B, ld], C positions per row
+// (the input of a re-ranking stage, the sampled negatives of an evaluation, a per-user eligibility set) -- so nothing of a tile is
+// shared between rows and the work is n * C gathered table rows.  Workgroup = (row b, 64 positions of its list), 256 threads:
+//   wave 0      the tile's 64 ids -> idl, the mask of its live positions -> lm[0] (a dead position's id forms no address);
+//   all         the row's rep -> R_l [LDE] and its seen ids -> sl, then the 64 table rows gathered into E_l [64][LDE] as tile_load_ids
+//               does, a dead position's row zero; meanwhile wave 1 scans sl for the id of position `lane` -> lm[1];
+//   wave w      mma_tile<1> over positions 16w .. 16w + 15 with a column stride of 0: the one rep row is broadcast to all 16 MFMA columns,
+//               and the lanes with (lane & 15) == 0 hold acc[0][r] = the score of position 16w + 4 (lane >> 4) + r.
+// The matrix unit is 1/16 used: the kernel is a gather of 4H bytes per pair.  The operands of a pair, their k order and ksteps are the
+// tile kernels', and a pair's chain does not depend on what else its tile holds: a score is k_logits_tile<MODE_STORE>'s float32.
+//   ROWLIST_STORE   scores[b, p] = the score, -inf at a dead position: id <= 0, id > N or id > ncol[b].  Any order, duplicates allowed: a
+//                   position's result depends on that position alone.
+//   ROWLIST_KEYS    topk_key(score, id) of every live, unseen position p -> part[p / k][b][p % k], key 0 elsewhere up to ranges * k:
+//                   k_topk_merge's input, ranges = ceil(C / k), and its output is ader_topk_items_cand's over the row's own list.
+//   ROWLIST_RANK    k_rank_cand's count over the row's list against tl[b] = k_target_logit's float32, one integer atomicAdd per wave.
+// KEYS and RANK take every row's list as strictly ascending ids >= 1 followed by 0 padding (ragged lists share one ld): a position with
+// id < 0, or p > 0 and id > 0 and (ids[b, p-1] == 0 or id <= ids[b, p-1]), flags ADER_ST_BAD_CAND and is dead; the result is then
+// unspecified (two equal keys would break k_topk_merge's rank-by-count) but every access stays in bounds, whatever the list.
+enum { ROWLIST_STORE = 0, ROWLIST_KEYS = 1, ROWLIST_RANK = 2 };
+#define ROWLIST_STAGE_REGS ((TI * LDE + 255) / 256)
+struct RowlistArgs {
+    const float* rep;      // [B,H]
+    const float* emb1;     // table row 1 (item 1); N: the last item of the table that may be read
+    int B, Bp, H, N;
+    const int* ncol;       // [B] columns of the row, or NULL: N
+    const int* ids;        // [B, ld] 1-based item ids, C positions per row
+    int ld, C, ntile;      // ntile: 64-position tiles per row
+    const int* seen;       // [B, seen_ld] 1-based ids never to be returned or counted (0 = none), or NULL     (KEYS, RANK)
+    int seen_ld;
+    float* scores;         // [B, ld_scores]                                   (STORE)
+    int ld_scores;
+    u64* part;             // [ranges][Bp][k]                                  (KEYS)
+    int k, ranges;
+    const int* target;     // [Bp] 1-based target item                         (RANK)
+    const float* tlogit;   // [Bp] the target's logit (k_target_logit)
+    int* rank;             // [Bp] zeroed by the launcher
+    int* status;           // status word or NULL
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_rowlist(RowlistArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* E_l = smem;                                       // [TI][LDE]
+    float* R_l = E_l + TI * LDE;                             // [LDE]
+    u64* lm = (u64*)(R_l + LDE);                             // [0] bit i: position i of the tile is live, [1] its id is seen by the row
+    int* idl = (int*)(lm + 2);                               // [TI] the tile's ids
+    int* sl = idl + TI;                                      // [seen_ld] the row's seen ids
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H = a.H, ksteps = (H + 3) >> 2;
+    const int b = blockIdx.x / a.ntile, p0 = (blockIdx.x - b * a.ntile) * TI;      // b < B: the grid is B * ntile
+    const int* row = a.ids + (size_t)b * a.ld;
+    if (wave == 0) {
+        const int p = p0 + lane;
+        int id = 0, nc = a.N;
+        bool bad = false;
+        if (p < a.C) {
+            id = row[p];
+            if (a.ncol) nc = min(nc, a.ncol[b]);
+            if (MODE != ROWLIST_STORE) {
+                const int prev = p > 0 ? row[p - 1] : 0;
+                bad = id < 0 || (p > 0 && id > 0 && (prev == 0 || id <= prev));
+            }
+        }
+        if (MODE != ROWLIST_STORE) {
+            const u64 anybad = __ballot(bad);
+            if (anybad && lane == 0 && a.status) atomicOr(a.status, ADER_ST_BAD_CAND);
+        }
+        const u64 live = __ballot(id >= 1 && id <= nc && !bad);
+        idl[lane] = id;
+        if (lane == 0) { lm[0] = live; lm[1] = 0; }
+    }
+    for (int i = tid; i < LDE; i += 256) R_l[i] = i < H ? a.rep[(size_t)b * H + i] : 0.0f;
+    if (MODE != ROWLIST_STORE && a.seen)
+        for (int i = tid; i < a.seen_ld; i += 256) sl[i] = a.seen[(size_t)b * a.seen_ld + i];
+    __syncthreads();                                         // ids, live mask, rep row and seen ids are in LDS
+    const u64 live = lm[0];
+    float pre[ROWLIST_STAGE_REGS];                           // tile_load_ids for 256 threads: every load of the gather is in flight at once
+#pragma unroll
+    for (int n = 0; n < ROWLIST_STAGE_REGS; ++n) {
+        const int i = tid + n * 256, r = (i / LDE) & (TI - 1), c = i - (i / LDE) * LDE;
+        const bool ok = i < TI * LDE && c < H && ((live >> r) & 1ull);
+        pre[n] = ok ? a.emb1[(size_t)(idl[r] - 1) * H + c] : 0.0f;
+    }
+    if (MODE != ROWLIST_STORE && a.seen && wave == 1) {
+        const int id = idl[lane];
+        bool s = false;
+        for (int t = 0; t < a.seen_ld; ++t) s |= sl[t] == id;      // (id 0 matches a padding 0 of seq: the position is dead anyway)
+        const u64 sm = __ballot(s);
+        if (lane == 0) lm[1] = sm;
+    }
+#pragma unroll
+    for (int n = 0; n < ROWLIST_STAGE_REGS; ++n)
+        if (tid + n * 256 < TI * LDE) E_l[tid + n * 256] = pre[n];
+    __syncthreads();                                         // E_l and the seen mask are complete
+    f32x4 acc[1];
+    acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    mma_tile<1>(E_l + wave * 16 * LDE, LDE, 1, R_l, 1, 0, ksteps, acc, lane);
+    const int q = lane >> 4, il0 = wave * 16 + q * 4;        // the 4 positions of the tile a lane with (lane & 15) == 0 holds
+    const bool owner = (lane & 15) == 0;
+    if (MODE == ROWLIST_STORE) {
+        if (owner)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (p0 + il0 + r < a.C) a.scores[(size_t)b * a.ld_scores + p0 + il0 + r] = ((live >> (il0 + r)) & 1ull) ? acc[0][r] : -INFINITY;
+    } else if (MODE == ROWLIST_KEYS) {
+        const u64 in = live & ~lm[1];
+        if (owner)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int p = p0 + il0 + r;
+                if (p >= a.ranges * a.k) continue;
+                const int rg = p / a.k;
+                a.part[((size_t)rg * a.Bp + b) * a.k + (p - rg * a.k)] = ((in >> (il0 + r)) & 1ull) ? topk_key(acc[0][r], idl[il0 + r]) : 0;
+            }
+    } else {
+        const u64 in = live & ~lm[1];
+        const int tg = a.target[b];
+        const float tl = a.tlogit[b];
+        int c = 0;
+        if (owner)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int id = idl[il0 + r];
+                // the target never counts itself, listed or not, seen or not (MODE_RANK's rule)
+                const bool ok = ((in >> (il0 + r)) & 1ull) && id != tg;
+                c += ok && ((acc[0][r] > tl) || (acc[0][r] == tl && id < tg));
+            }
+        c += __shfl_xor(c, 16, 64);                          // (the other lanes hold 0)
+        c += __shfl_xor(c, 32, 64);
+        if (lane == 0 && c) atomicAdd(a.rank + b, c);
+    }
+}
+
 // ============================================================================================= wide answers, k up to 1024: slab and select
 // k_topk_tile keeps k + 64 keys per row in LDS, which ends at k = 64; here no buffer in LDS grows with k.
 // Per row, in global memory: a list of cap 64-bit keys, a count, a threshold key (0 = none yet) and a status word.  The catalog is
@@ -560,6 +698,14 @@ static void topk_fill(TopkCommon& a, const float* rep, const float* emb, int B, 
     a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ncol = ncol; a.seen = seen; a.seen_ld = seen_ld; a.k = k;
 }
 static size_t tile_lds(size_t tail) { return (size_t)(2 * 64 * LDE) * sizeof(float) + tail; }
+#define ROWLIST_SEEN_MAX 4096     // seen ids per row that k_rowlist stages in LDS (a session's length)
+#define ROWLIST_CMAX 65536        // list positions per row
+static size_t rowlist_lds(int seen_ld) {      // E_l, R_l, lm, idl, sl
+    return (size_t)(TI * LDE + LDE) * sizeof(float) + 2 * sizeof(u64) + (size_t)(TI + seen_ld) * sizeof(int);
+}
+static bool rowlist_bad(const int* ids, int ld, int C, const int* seen, int seen_ld) {
+    return C < 0 || C > ROWLIST_CMAX || ld < C || (C > 0 && !ids) || (seen && seen_ld > ROWLIST_SEEN_MAX);
+}
 static size_t rowbuf_lds(int k) { return (size_t)TB * (k + TI) * sizeof(u64) + TB * (2 * sizeof(u64) + sizeof(int)); }      // buf, thr, msk, cnt
 
 // Items of the slab that follows `seen` items: max(64, 64 floor(seen min(1, (cap - k) / (WIDE_GROWTH k)) / 64)), in integers.
@@ -659,6 +805,76 @@ int ader_rank_targets_cand(const float* rep, const float* emb, int B, int Bp, in
     a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.target = target; a.ncol = ncol; a.seen = seen;
     a.seen_ld = seen_ld; a.ranges = ader_topk_ranges(M, Bp); a.cand = cand; a.M = M; a.tlogit = tlogit; a.rank = rank; a.status = status;
     hipLaunchKernelGGL(k_rank_cand, dim3(a.ranges * (Bp / TB)), dim3(512), lds, st, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// scores[b, p] (row stride ld_scores >= C) = the logit of item ids[b, p] (row stride ld >= C) for row b, the float32 of
+// ader_logits_store; -inf where the id is outside [1, min(N, ncol[b])].  ncol: [B], or NULL: N for every row.  Any ids, in any order.
+// C = 0 or B <= 0: nothing is launched.  Enqueue only.
+int ader_score_items(const float* rep, const float* emb, int B, int H, int N, const int* ncol, const int* ids, int ld, int C,
+                     float* scores, int ld_scores, void* stream) {
+    if (H > HP || H < 1 || N < 1 || C < 0 || ld < C || ld_scores < C || (C > 0 && !ids)) return -2;
+    if (B <= 0 || C == 0) return 0;
+    RowlistArgs a = {};
+    a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = B; a.H = H; a.N = N; a.ncol = ncol; a.ids = ids; a.ld = ld; a.C = C;
+    a.ntile = (C + TI - 1) / TI; a.scores = scores; a.ld_scores = ld_scores;
+    if ((long)B * a.ntile > 0x7fffffffL) return -2;
+    const size_t lds = rowlist_lds(0);
+    const int rc = ader_dyn_lds<k_rowlist<ROWLIST_STORE>>(lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_rowlist<ROWLIST_STORE>, dim3(B * a.ntile), dim3(256), lds, (hipStream_t)stream, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+// ader_topk_items_cand with a list per row: ids [B, ld], C positions per row, every row strictly ascending ids >= 1 followed by 0
+// padding; ids above N (or ncol[b]) are ignored.  part: ader_topk_rows_ranges(C,k) * Bp * k keys of scratch.  C = 0: every row is
+// padding (ids may be NULL).  status (NULL: none): ADER_ST_BAD_CAND is OR-ed in for a row that is not in that form; the result is then
+// unspecified, and nothing outside the table or the buffers is touched.  seen_ld <= ROWLIST_SEEN_MAX.  Enqueue only.
+int ader_topk_rows_ranges(int C, int k) { return (C > 0 && k > 0) ? (C + k - 1) / k : 1; }
+int ader_topk_items_rows(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* ids, int ld, int C,
+                         const int* seen, int seen_ld, int k, unsigned long long* part, int* items, float* scores, int* status,
+                         void* stream) {
+    if (topk_bad(B, Bp, H, N, seen, seen_ld, k, TOPK_KMAX) || rowlist_bad(ids, ld, C, seen, seen_ld)) return -2;
+    if (B <= 0) return 0;
+    TopkArgs t;
+    topk_fill(t, rep, emb, B, Bp, H, N, ncol, seen, seen_ld, k);
+    t.ranges = ader_topk_rows_ranges(C, k); t.part = part; t.items = items; t.scores = scores;
+    RowlistArgs a = {};
+    a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ncol = ncol; a.ids = ids; a.ld = ld; a.C = C;
+    a.ntile = (t.ranges * k + TI - 1) / TI;                  // every slot of part is written: ranges * k >= C
+    a.seen = seen; a.seen_ld = seen_ld; a.part = part; a.k = k; a.ranges = t.ranges; a.status = status;
+    const size_t lds = rowlist_lds(seen ? seen_ld : 0);
+    const int rc = ader_dyn_lds<k_rowlist<ROWLIST_KEYS>>(lds);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_rowlist<ROWLIST_KEYS>, dim3(B * a.ntile), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, st, t);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
+// ader_rank_targets_cand with a list per row (ids, ld, C, seen, status and -2 as ader_topk_items_rows): rank[b] = the number of
+// positions of row b's list whose id c is live, not seen, != t = target[b], and s(b,c) > s(b,t) or (== and c < t) -- so the rank of
+// ader_topk_items_rows' items[b, j] > 0 over the same arguments is j.  tlogit: Bp floats of scratch; rank: [Bp] (zeroed here).
+// C = 0: the clear of rank and nothing else.  Enqueue only.
+int ader_rank_targets_rows(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
+                           const int* ids, int ld, int C, const int* seen, int seen_ld, float* tlogit, int* rank, int* status,
+                           void* stream) {
+    if (topk_bad(B, Bp, H, N, seen, seen_ld, 1, 1) || rowlist_bad(ids, ld, C, seen, seen_ld)) return -2;
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(rank, 0, sizeof(int) * (size_t)Bp, st);
+    if (e != hipSuccess) return (int)e;
+    if (C == 0) return 0;
+    const size_t lds = rowlist_lds(seen ? seen_ld : 0);
+    int rc = ader_dyn_lds<k_rowlist<ROWLIST_RANK>>(lds);
+    if (rc) return rc;
+    rc = rank_target_logit_launch(rep, emb, B, Bp, H, N, target, ncol, tlogit, stream);
+    if (rc) return rc;
+    RowlistArgs a = {};
+    a.rep = rep; a.emb1 = emb + H; a.B = B; a.Bp = Bp; a.H = H; a.N = N; a.ncol = ncol; a.ids = ids; a.ld = ld; a.C = C;
+    a.ntile = (C + TI - 1) / TI; a.seen = seen; a.seen_ld = seen_ld; a.target = target; a.tlogit = tlogit; a.rank = rank; a.status = status;
+    hipLaunchKernelGGL(k_rowlist<ROWLIST_RANK>, dim3(B * a.ntile), dim3(256), lds, st, a);
     HIP_LAUNCH_CHECK();
     return 0;
 }

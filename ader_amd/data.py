@@ -479,6 +479,29 @@ def recall_mrr(ranks):
     return tuple(out)
 
 
+def sample_negatives(seq, pos, max_item, n_neg, seed):
+    """The sampled-negative protocol of the SASRec / BERT4Rec evaluations: for every row n_neg distinct item ids, uniform over
+    1..max_item minus the row's target pos[b] and the non-zero ids of seq[b] -> int32 [n, n_neg], every row ascending.  Draws from its
+    own np.random.Generator(seed): `random` and the global numpy stream, which the reference's shuffles consume, are left alone.
+    RuntimeError when a row has fewer than n_neg eligible ids."""
+    seq = np.asarray(seq.cpu() if hasattr(seq, "cpu") else seq, dtype=np.int64)
+    pos = np.asarray(pos.cpu() if hasattr(pos, "cpu") else pos, dtype=np.int64).reshape(-1)
+    if seq.ndim != 2 or seq.shape[0] != pos.shape[0]:
+        raise RuntimeError("sample_negatives: seq must be [n, T] and pos [n]")
+    N, m = int(max_item), int(n_neg)
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    out = np.zeros((seq.shape[0], m), dtype=np.int32)
+    for b in range(seq.shape[0]):
+        ex = np.unique(np.append(seq[b], pos[b]))
+        ex = ex[(ex >= 1) & (ex <= N)] - 1                   # 0-based, ascending
+        free = N - len(ex)
+        if free < m:
+            raise RuntimeError("sample_negatives: row %d has %d eligible items of 1..%d, fewer than n_neg = %d" % (b, free, N, m))
+        x = np.sort(rng.choice(free, size=m, replace=False))                      # indices into the row's eligible ids, ascending
+        out[b] = x + np.searchsorted(ex - np.arange(len(ex)), x, side="right") + 1      # the x-th id that is not excluded
+    return out
+
+
 class Evaluator:
     """Evaluates the rank of the ground-truth next item among all `max_item` items
     (reference util.py:276-350).  `model.predict(sess, seq, item_idx)` must return the full rank
@@ -486,12 +509,15 @@ class Evaluator:
     count-greater kernel) that is used instead -- only pred[label-1] is ever read (util.py:325).
     candidates (item ids, as Engine.recommend_among takes them) and / or exclude_seen: beside `ranks`, which stay what they are, the
     same pass fills `ranks_among` -- the target's rank among the listed items of 1..max_item (None: all of them), without the
-    session's own items under exclude_seen -- by one `model.rank_targets_among` call; results_among() / display_among() report it."""
+    session's own items under exclude_seen -- by one `model.rank_targets_among` call; results_among() / display_among() report it.
+    negatives > 0: the same pass also fills `ranks_sampled` -- the target's rank among itself plus `negatives` sampled items the session
+    has not seen (sample_negatives with neg_seed: the protocol the SASRec and BERT4Rec papers report), by one
+    `model.rank_targets_per_row` call; results_sampled() / display_sampled() report it, beside the whole-catalog ranks."""
 
     _packed = {}        # (id(data), len, maxlen, is_subseq) -> (data, (prepared_data, rows, valid)): see __init__
 
     def __init__(self, data, is_subseq, maxlen, batch_size, max_item, mode, model, sess, shard=(0, 1), candidates=None,
-                 exclude_seen=False):
+                 exclude_seen=False, negatives=0, neg_seed=0):
         self.shard = shard          # (rank, world): evaluation batches are independent units (SURVEY 8e)
         self.max_item = max_item
         self.model = model
@@ -503,6 +529,13 @@ class Evaluator:
         if self.among and getattr(model, "rank_targets_among", None) is None:
             raise RuntimeError("Evaluator(candidates=..., exclude_seen=...) needs a model with rank_targets_among(seq, pos, max_item, "
                                "candidates, exclude_seen); %s has none" % type(model).__name__)
+        self.negatives, self.neg_seed = int(negatives), int(neg_seed)
+        self.ranks_sampled = []
+        if self.negatives < 0:
+            raise RuntimeError("Evaluator(negatives=...) must be >= 0 (got %d)" % self.negatives)
+        if self.negatives and getattr(model, "rank_targets_per_row", None) is None:
+            raise RuntimeError("Evaluator(negatives=...) needs a model with rank_targets_per_row(seq, pos, max_item, lists, "
+                               "exclude_seen); %s has none" % type(model).__name__)
         self.mode = mode
         self.desc = 'Validating epoch ' if mode == 'valid' else 'Testing epoch '
         # (the packed rows of an unchanged session list are kept between evaluators -- one is built per epoch, main.py:264-266 -- and
@@ -534,7 +567,7 @@ class Evaluator:
             seq, pos = self.evaluate_sampler.next_batch()       # every rank walks the same batch sequence
             if len(pos) == 0 or b % world != rank:
                 continue
-            if self.among:
+            if self.among or self.negatives:
                 rows.append((b, seq, pos))
             if fast is not None:
                 todo.append((b, seq, pos))
@@ -568,6 +601,20 @@ class Evaluator:
                 from . import dist as _dist
                 among = sorted(x for part in _dist.gather_lists(among, world) for x in part)
             self.ranks_among = [x for _, r in among for x in r]
+        if self.negatives:
+            sampled = []
+            if rows:                 # one call on the same concatenated rows: the target joins its negatives by the rank's own contract
+                seq_all, pos_all = np.concatenate([s_ for _, s_, _ in rows]), np.concatenate([p_ for _, _, p_ in rows])
+                neg = sample_negatives(seq_all, pos_all, self.max_item, self.negatives, self.neg_seed)
+                r = np.asarray(self.model.rank_targets_per_row(seq_all, pos_all, self.max_item, neg, False)).tolist()
+                o = 0
+                for b, _, pos in rows:
+                    sampled.append((b, r[o:o + len(pos)]))
+                    o += len(pos)
+            if world > 1:
+                from . import dist as _dist
+                sampled = sorted(x for part in _dist.gather_lists(sampled, world) for x in part)
+            self.ranks_sampled = [x for _, r in sampled for x in r]
         return self.display(epoch)
 
     def results(self):
@@ -591,6 +638,20 @@ class Evaluator:
         r = self.results_among()
         info = 'epoch:%d, %s among %d candidate items%s (MRR@20: %.4f, RECALL@20: %.4f, MRR@10: %.4f, RECALL@10: %.4f)' \
                % (epoch, self.mode, self.n_candidates(), ', seen items excluded' if self.exclude_seen else '', r[0], r[1], r[2], r[3])
+        if self.shard[0] == 0:
+            print(info)
+        return info
+
+    def results_sampled(self):
+        """recall_mrr of ranks_sampled (an Evaluator built with negatives > 0, after evaluate())."""
+        if not self.negatives:
+            raise RuntimeError("results_sampled: this Evaluator was built without negatives")
+        return recall_mrr(self.ranks_sampled)
+
+    def display_sampled(self, epoch):
+        r = self.results_sampled()
+        info = 'epoch:%d, %s among the target and %d sampled unseen items (MRR@20: %.4f, RECALL@20: %.4f, MRR@10: %.4f, RECALL@10: %.4f)' \
+               % (epoch, self.mode, self.negatives, r[0], r[1], r[2], r[3])
         if self.shard[0] == 0:
             print(info)
         return info

@@ -46,6 +46,50 @@ def candidate_ids(candidates, N, item_num):
     return np.ascontiguousarray(a[a <= N], dtype=np.int32)
 
 
+def row_candidate_ids(lists, N, item_num):
+    """The per-row lists of Engine.recommend_per_row / rank_targets_per_row in the form ader_topk_items_rows takes: a 2-D integer array
+    or tensor (0 entries are padding), or a sequence of 1-D integer sequences -> int32 [n, C'] numpy, every row sorted, unique and
+    ascending, then zero-padded; C' = the longest row (0 if every row is empty).  Ids in (N, item_num] are dropped silently; a
+    non-integer dtype, a wrong rank or an id outside [0, item_num] raise RuntimeError.  A row already in form is not sorted again."""
+    if isinstance(lists, torch.Tensor):
+        lists = lists.detach().cpu().numpy()
+    if isinstance(lists, np.ndarray):
+        _check(np.issubdtype(lists.dtype, np.integer), "lists must hold integers (got dtype %s)" % (lists.dtype,))
+        _check(lists.ndim == 2, "lists must be 2-D, or a sequence of 1-D sequences (got %d dimensions)" % lists.ndim)
+        if lists.size:                                       # a matrix already in form, no id above N: one pass, no loop over rows
+            lo, hi = int(lists.min()), int(lists.max())
+            _check(0 <= lo and hi <= item_num, "lists must hold item ids in [0, item_num = %d] (got %d .. %d)" % (item_num, lo, hi))
+            nxt, prv = lists[:, 1:], lists[:, :-1]
+            if hi <= N and bool(np.all((nxt == 0) | ((prv > 0) & (nxt > prv)))):
+                C = int(np.count_nonzero(lists, axis=1).max())
+                return np.ascontiguousarray(lists[:, :C], dtype=np.int32)
+        rows = list(lists)
+    else:
+        rows = []
+        for r in lists:
+            a = r.detach().cpu().numpy() if isinstance(r, torch.Tensor) else np.asarray(r)
+            if a.size == 0 and a.ndim == 1 and not isinstance(r, (np.ndarray, torch.Tensor)):
+                a = a.astype(np.int32)                       # (an empty list has no dtype of its own)
+            _check(np.issubdtype(a.dtype, np.integer), "lists must hold integers (got dtype %s)" % (a.dtype,))
+            _check(a.ndim == 1, "every row of lists must be 1-D (got %d dimensions)" % a.ndim)
+            rows.append(a)
+    out = []
+    for a in rows:
+        if a.size:
+            lo, hi = int(a.min()), int(a.max())
+            _check(0 <= lo and hi <= item_num, "lists must hold item ids in [0, item_num = %d] (got %d .. %d)" % (item_num, lo, hi))
+        nz = int(np.count_nonzero(a))
+        head = a[:nz]
+        if not (bool(np.all(head > 0)) and (nz < 2 or bool(np.all(head[1:] > head[:-1])))):      # (not: ascending ids, then the zeros)
+            head = np.unique(a[a > 0])
+        out.append(head[head <= N])
+    C = max((len(r) for r in out), default=0)
+    res = np.zeros((len(out), C), dtype=np.int32)
+    for i, r in enumerate(out):
+        res[i, :len(r)] = r
+    return res
+
+
 def rank_x3_supports(H):
     """Hidden sizes of k_lx3k (lx3f_supports of csrc/logits_x3.hip)."""
     return H % 2 == 0 and 8 <= H <= 160 and H % 8 in (0, 4, 6)
@@ -328,6 +372,106 @@ class _Infer:
                  ptr(self.status), self._stream())
         host = res.cpu().numpy()
         return host[0], host[1].view(np.float32)
+
+    def score_items(self, seq, items, max_item=None):
+        """The logits of the listed items, row by row: items is an integer [n, C] array or tensor of item ids (any order, duplicates
+        allowed) -> float32 [n, C] numpy aligned with it, the bits of logits(seq, N)[b, items[b, c] - 1]; -inf where items[b, c] <= 0
+        or > N = max_item (None: the whole catalog).  What a re-ranking stage asks of the model: the table rows are gathered inside
+        the kernel (ader_score_items, k_rowlist), so the work follows n * C and no [n, N] logits are written.  Chunks of MAX_ROWS
+        rows, one device -> host copy."""
+        N = self.item_num if max_item is None else int(max_item)
+        _check(1 <= N <= self.item_num, "score_items: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        if not isinstance(items, torch.Tensor):
+            items = np.asarray(items)
+        _check(items.ndim == 2, "score_items: items must be [n, C] (got %d dimensions)" % items.ndim)
+        dt = items.dtype
+        _check(dt in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) if isinstance(items, torch.Tensor)
+               else np.issubdtype(dt, np.integer), "score_items: items must hold integers (got dtype %s)" % (dt,))
+        self._refresh_stream()
+        self.sync_table()
+        seq = self._seq_in(seq)
+        n, C = seq.shape[0], int(items.shape[1])
+        _check(items.shape[0] == n, "score_items: items must have one row per session (got %d for %d)" % (items.shape[0], n))
+        out = torch.empty((n, C), dtype=torch.float32, device=self.device)
+        if C:
+            ids = self._dev_i32(items)
+            for s in range(0, n, self.MAX_ROWS):
+                e = min(n, s + self.MAX_ROWS)
+                rep = self.forward(seq[s:e], training=False)
+                call("ader_score_items", ptr(rep), self._pp["emb"], e - s, self.H, N, None, ptr(ids[s:e]), C, C, ptr(out[s:e]), C,
+                     self._stream())
+        return out.cpu().numpy()
+
+    def recommend_per_row(self, seq, k, lists, max_item=None, exclude_seen=False):
+        """recommend_among with a candidate list of its own for every row: lists as row_candidate_ids takes them (a 2-D integer array
+        or tensor with 0 as padding, or a sequence of 1-D integer sequences; any order, duplicates allowed, every id in
+        [0, item_num]).  Row b's candidates are set(lists[b]) within [1, max_item], minus its seen ids under exclude_seen; scores,
+        order, ties and padding are recommend's, so with all of 1..max_item in every row the bytes are recommend's, and with the same
+        list in every row recommend_among's.  The lists' table rows are gathered inside the kernel (ader_topk_items_rows, k_rowlist):
+        the work follows the lists' length, not max_item.  Exact-f32 chain; last_topk_stats is left None.  The lists are copied to
+        the device once, chunks of MAX_ROWS rows, one device -> host copy."""
+        kmax = call("ader_topk_kmax")
+        k = int(k)
+        N = self.item_num if max_item is None else int(max_item)
+        _check(1 <= k <= kmax, "recommend_per_row: k must be in 1..%d (got %d)" % (kmax, k))
+        _check(1 <= N <= self.item_num, "recommend_per_row: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        ids = row_candidate_ids(lists, N, self.item_num)
+        self._refresh_stream()
+        self.sync_table()
+        self.last_topk_stats = None
+        seq = self._seq_in(seq)
+        n, C = seq.shape[0], int(ids.shape[1])
+        _check(ids.shape[0] == n, "recommend_per_row: lists must have one row per session (got %d for %d)" % (ids.shape[0], n))
+        ids_d = self._dev_i32(ids) if C else None
+        res = torch.empty((2, n, k), dtype=torch.int32, device=self.device)      # items | score bits: one copy back
+        scores = res[1].view(torch.float32)
+        ranges = call("ader_topk_rows_ranges", C, k)
+        for s in range(0, n, self.MAX_ROWS):
+            e = min(n, s + self.MAX_ROWS)
+            rep = self.forward(seq[s:e], training=False)
+            B = e - s
+            Bp = (B + 63) // 64 * 64
+            part = self.buf("tkr_part", (ranges * Bp * k,), torch.int64)
+            call("ader_topk_items_rows", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
+                 ptr(ids_d[s:e]) if C else None, C, C, ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, ptr(part),
+                 ptr(res[0, s:e]), ptr(scores[s:e]), ptr(self.status), self._stream())
+        host = res.cpu().numpy()
+        return host[0], host[1].view(np.float32)
+
+    def rank_targets_per_row(self, seq, pos, max_item, lists, exclude_seen=False):
+        """rank_targets_among with a candidate list of its own for every row (lists as recommend_per_row's): the 0-based rank of pos[b]
+        among set(lists[b]) within [1, max_item], minus the row's seen ids under exclude_seen -> int32 numpy [n].  The target need not
+        be listed and never counts itself, listed or seen; scores and the tie rule (score descending, id ascending) are
+        recommend_per_row's, so for (items, _) = recommend_per_row(seq, k, lists, N, e): rank_targets_per_row(seq_b, items[b, j], N,
+        lists, e) == j wherever items[b, j] > 0.  With the target plus sampled unseen items as a row's list this is the
+        sampled-negative protocol of the SASRec evaluation (data.sample_negatives, Evaluator(negatives=...)).  ader_rank_targets_rows,
+        k_rowlist: the work follows the lists' length.  Chunks of MAX_ROWS rows, one device -> host copy."""
+        N = int(max_item)
+        _check(1 <= N <= self.item_num, "rank_targets_per_row: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        ids = row_candidate_ids(lists, N, self.item_num)
+        self._refresh_stream()
+        self.sync_table()
+        seq = self._seq_in(seq)
+        pos = self._dev_i32(pos)
+        n, C = seq.shape[0], int(ids.shape[1])
+        _check(ids.shape[0] == n, "rank_targets_per_row: lists must have one row per session (got %d for %d)" % (ids.shape[0], n))
+        ids_d = self._dev_i32(ids) if C else None
+        out = torch.empty(n, dtype=torch.int32, device=self.device)
+        for s in range(0, n, self.MAX_ROWS):
+            e = min(n, s + self.MAX_ROWS)
+            B = e - s
+            Bp = (B + 63) // 64 * 64
+            rep = self.forward(seq[s:e], training=False)
+            tl = self.buf("rkr_tl", (Bp,))
+            rk = self.buf("rkr_rank", (Bp,), torch.int32)
+            tgt = self.buf("rkr_tgt", (Bp,), torch.int32)
+            tgt.zero_()
+            tgt[:B] = pos[s:e]
+            call("ader_rank_targets_rows", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(tgt), ptr(self._ncol_all(Bp, B, N)),
+                 ptr(ids_d[s:e]) if C else None, C, C, ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], ptr(tl), ptr(rk),
+                 ptr(self.status), self._stream())
+            out[s:e] = rk[:B]
+        return out.cpu().numpy()
 
     def _recommend_x3(self, seq, k, N, exclude_seen, band):
         """recommend on the bf16 matrix cores (ader_topk_items_x3): per 128-row-padded chunk k_lx3t keeps every item whose x3 logit is not

@@ -7,7 +7,7 @@ Differences from the reference that do not change results: booleans are parsed w
 batches and teacher logits stay on the GPU (the reference feeds Python float lists every step, util.py:254);
 the best-epoch checkpoint is kept in memory and written to disk only with --save_ckpt.
 Extra flags: --logits_dtype, --max_periods, --data_root, --save_ckpt, --eval_batch (--test_batch is accepted and ignored:
-ranks do not depend on the evaluation batch size), --dist_backend, --device_feed, --teacher_form, --eval_among.
+ranks do not depend on the evaluation batch size), --dist_backend, --device_feed, --teacher_form, --eval_among, --eval_negatives.
 
 Data parallel: launched as `python -m torch.distributed.run --nproc-per-node W -m ader_amd.main ...` every
 rank builds the same batches from the same RNG streams, trains on its slice of the train rows and of the exemplar rows
@@ -56,6 +56,9 @@ _BUILD_FLAGS = (
     # second line and the summary keys among_*, the rank among the items that occur in the period's own training sessions
     # (Evaluator(candidates=...), Engine.rank_targets_among); "catalog": nothing more
     ("eval_among", "catalog", str, ("catalog", "period")),
+    # N > 0: a third line and the summary keys *_sampled -- the rank among the target plus N sampled items the session has not seen, the
+    # protocol of the SASRec / BERT4Rec papers (Evaluator(negatives=N), Engine.rank_targets_per_row); 0: nothing more
+    ("eval_negatives", 0, int, None),
     ("results_root", "results", str, None), ("save_ckpt", False, bool, None),
     ("dist_backend", "nccl", str, "torch.distributed backend when WORLD_SIZE > 1"),
     ("device_feed", True, bool, "keep the packed training rows on the GPU and gather batches there"),
@@ -176,6 +179,7 @@ def run(args, log=print):
         logs.write(info + '\n')
         max_item = dataloader.max_item()
         among = period_items(train_sess, max_item) if getattr(args, "eval_among", "catalog") == "period" else None
+        neg = max(0, int(getattr(args, "eval_negatives", 0)))
         use_ex = period > 1 and not baseline
         if use_ex:
             # (the reference flattens {item: [[session, logits], ...]} into a list, main.py:54-65,176-190; the store holds the same
@@ -290,7 +294,7 @@ def run(args, log=print):
                 best_state = model.engine.state_dict()
             model.engine.load_state_dict(best_state)                    # saver.restore(best), main.py:283
             test_evaluator = Evaluator(test_sess, False, args.maxlen, args.eval_batch, max_item, 'test', model, sess, shard,
-                                       candidates=among)
+                                       candidates=among, negatives=neg, neg_seed=args.random_seed)
             info = test_evaluator.evaluate(best_epoch)
             logs.write(info + '\n')
             r = test_evaluator.results()
@@ -302,6 +306,11 @@ def run(args, log=print):
                 ra = test_evaluator.results_among()
                 summary[-1].update({"among_mrr20": ra[0], "among_recall20": ra[1], "among_mrr10": ra[2], "among_recall10": ra[3],
                                     "among_items": test_evaluator.n_candidates()})
+            if neg:                                                      # --eval_negatives: the same targets among sampled unseen items
+                logs.write(test_evaluator.display_sampled(best_epoch) + '\n')
+                rs = test_evaluator.results_sampled()
+                summary[-1].update({"sampled_negatives": neg, "mrr20_sampled": rs[0], "recall20_sampled": rs[1], "mrr10_sampled": rs[2],
+                                    "recall10_sampled": rs[3]})
             if not baseline:                                             # exemplar selection, main.py:294-313
                 exemplar_candidate = train_subseq
                 exemplar_candidate.extend(valid_subseq)

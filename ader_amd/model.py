@@ -94,6 +94,20 @@ class Ader:
             return self.engine.recommend_wide(seq, k, max_item, exclude_seen)
         return self.engine.recommend(seq, k, max_item, exclude_seen, dtype=dtype)
 
+    def score_items(self, seq, items, max_item=None):
+        """The logits of items[b, c] for session b, float32 [n, C] aligned with items (Engine.score_items): what a re-ranking stage
+        takes from the model."""
+        return self.engine.score_items(seq, items, max_item)
+
+    def recommend_per_row(self, seq, k, lists, max_item=None, exclude_seen=False):
+        """recommend(candidates=...) with a list of its own per session (Engine.recommend_per_row)."""
+        return self.engine.recommend_per_row(seq, k, lists, max_item, exclude_seen)
+
+    def rank_targets_per_row(self, seq, pos, max_item, lists, exclude_seen=False):
+        """rank_targets_among with a list of its own per session (Engine.rank_targets_per_row): what scores recommend_per_row, and the
+        sampled-negative protocol of the Evaluator."""
+        return self.engine.rank_targets_per_row(seq, pos, max_item, lists, exclude_seen)
+
     def predict(self, sess, seq, item_idx):
         """Rank of every candidate item (ADER.py:140-150).  Kept for API parity; the Evaluator uses rank_targets."""
         return sess.run(self.pred_last, {self.input_seq: seq, self.test_item: item_idx, self.is_training: False,

@@ -19,6 +19,12 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
                                                                          order and bits of argsort(-logits) (ADER.py:92, 103)
   ader::topk_items_cand(rep, emb, cand, seen, N, k)            -> (items, scores)   topk_items over the ids of one ascending candidate
                                                                          list, its table rows gathered in the kernel: work follows the list
+  ader::score_items(rep, emb, ids, N)                          -> scores   the logits of the items ids[b, :] lists for row b, any ids in
+                                                                         any order: what a re-ranking stage reads; work follows B * C
+  ader::topk_items_rows(rep, emb, ids, seen, N, k)             -> (items, scores)   topk_items_cand with an ascending, 0-padded list of
+                                                                         its own per row
+  ader::rank_of_target_rows(rep, emb, target, ids, seen, N)    -> rank   rank_of_target_cand over each row's own list: what scores
+                                                                         topk_items_rows, and the sampled-negative evaluation
   ader::topk_items_x3(rep, emb, seen, N, k)                    -> (items, scores)   the same bytes; products on the bf16 matrix cores (x3
                                                                          filter keeping a superset of the top-k + exact-f32 recheck)
   ader::topk_items_wide(rep, emb, seen, N, k, cap)             -> (items, scores, overflowed)   topk_items for k up to 1024 by slab
@@ -293,6 +299,90 @@ def rank_of_target_cand(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tens
 
 @rank_of_target_cand.register_fake
 def _(rep, emb, target, cand, seen, N):
+    return target.new_empty(rep.shape[0])
+
+
+def _rows_ids(op, ids, B):
+    _chk(ids, "ids", torch.int32, 2)
+    if ids.shape[0] != B:
+        raise RuntimeError("ader::%s: ids must be [B, C]" % op)
+    return ids.shape[1]
+
+
+_ROWS_MSG = "ader::%s: every row of ids must be strictly ascending item ids >= 1 followed by 0 padding"
+
+
+@torch.library.custom_op("ader::score_items", mutates_args=())
+def score_items(rep: torch.Tensor, emb: torch.Tensor, ids: torch.Tensor, N: int) -> torch.Tensor:
+    """rep [B,H] (any B), emb [V,H] (row 0 = padding item), ids int32 [B,C] item ids in any order, duplicates allowed -> scores float32
+    [B,C]: the logit of item ids[b, c] for row b, the bits of ader_logits_store; -inf where ids[b, c] <= 0 or > N.  The table rows are
+    gathered in the kernel: work follows B * C, not N."""
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
+    B, H = rep.shape
+    if emb.shape[1] != H or H > HP or not (1 <= N <= emb.shape[0] - 1):
+        raise RuntimeError("ader::score_items: bad shapes")
+    C = _rows_ids("score_items", ids, B)
+    scores = torch.empty(B, C, device=rep.device)
+    call("ader_score_items", ptr(rep), ptr(emb), B, H, N, None, ptr(ids) if C else None, C, C, ptr(scores), C, _st())
+    return scores
+
+
+@score_items.register_fake
+def _(rep, emb, ids, N):
+    return rep.new_empty(ids.shape)
+
+
+@torch.library.custom_op("ader::topk_items_rows", mutates_args=())
+def topk_items_rows(rep: torch.Tensor, emb: torch.Tensor, ids: torch.Tensor, seen: Optional[torch.Tensor], N: int,
+                    k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """topk_items_cand with a list per row: ids int32 [B,C], every row strictly ascending 1-based ids followed by 0 padding (ids above N
+    are ignored; C = 0 returns padding) -> (items int32 [B,k], scores float32 [B,k]) with topk_items' scores, order, ties and padding.
+    The op does not sort for the caller: a row that is not in that form raises (one synchronisation to read the status)."""
+    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_rows", rep, emb, seen, N, k, call("ader_topk_kmax"))
+    C = _rows_ids("topk_items_rows", ids, B)
+    part = torch.empty(call("ader_topk_rows_ranges", C, k) * Bp * k, dtype=torch.int64, device=rep.device)
+    status = torch.zeros(1, dtype=torch.int32, device=rep.device)
+    call("ader_topk_items_rows", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(ids) if C else None, C, C, ptr(seen), seen_ld, k,
+         ptr(part), ptr(items), ptr(scores), ptr(status), _st())
+    if int(status.item()):
+        raise RuntimeError(_ROWS_MSG % "topk_items_rows")
+    return items, scores
+
+
+topk_items_rows.register_fake(_topk_fake)
+
+
+@torch.library.custom_op("ader::rank_of_target_rows", mutates_args=())
+def rank_of_target_rows(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, ids: torch.Tensor, seen: Optional[torch.Tensor],
+                        N: int) -> torch.Tensor:
+    """rank_of_target_cand with a list per row (ids, seen and N as topk_items_rows'): rank int32 [B] = the number of ids of row b's list
+    in [1, N], other than the row's target and its seen ids, that precede the target by (logit descending, id ascending) -- so the rank
+    of topk_items_rows' items[b, j] > 0 over the same arguments is j.  The target (in [1, N]) need not be listed.  A row that is not
+    strictly ascending ids >= 1 followed by 0 padding raises (one synchronisation to read the status)."""
+    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(target, "target", torch.int32, 1)
+    B, H = rep.shape
+    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or target.shape[0] != B or B > 1024:
+        raise RuntimeError("ader::rank_of_target_rows: bad shapes")
+    C = _rows_ids("rank_of_target_rows", ids, B)
+    if seen is not None:
+        _chk(seen, "seen", torch.int32, 2)
+        if seen.shape[0] != B or seen.shape[1] < 1:
+            raise RuntimeError("ader::rank_of_target_rows: seen must be [B, S] with S >= 1")
+    Bp = (B + 63) // 64 * 64
+    dev = rep.device
+    tgt, ncol = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, dtype=torch.int32, device=dev)
+    tgt[:B], ncol[:B] = target, N
+    tl, rk = torch.empty(Bp, device=dev), torch.empty(Bp, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    call("ader_rank_targets_rows", ptr(rep), ptr(emb), B, Bp, H, N, ptr(tgt), ptr(ncol), ptr(ids) if C else None, C, C, ptr(seen),
+         seen.shape[1] if seen is not None else 0, ptr(tl), ptr(rk), ptr(status), _st())
+    if int(status.item()):
+        raise RuntimeError(_ROWS_MSG % "rank_of_target_rows")
+    return rk[:B].clone()
+
+
+@rank_of_target_rows.register_fake
+def _(rep, emb, target, ids, seen, N):
     return target.new_empty(rep.shape[0])
 
 

@@ -280,6 +280,29 @@ int ader_topk_items_cand(const float* rep, const float* emb, int B, int Bp, int 
  * Enqueue only.  -2 when Bp % 64 != 0, Bp > 1024, B > Bp, H > 160, N < 1, M < 0, M > 0 with cand == NULL, or seen with seen_ld < 1. */
 int ader_rank_targets_cand(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
                            const int* cand, int M, const int* seen, int seen_ld, float* tlogit, int* rank, int* status, void* stream);
+/* The three list forms above for a list that differs from row to row (the input of a re-ranking stage, the sampled negatives of an
+ * evaluation, a per-user eligibility set): ids [B, ld] int32, C <= ld positions per row (C <= 65536).  A workgroup of k_rowlist
+ * (csrc/topk.hip) gathers the table rows of 64 positions of one row's list: the work follows B * C, not N, and no id outside [1, N]
+ * forms an address.  A score is the float32 of ader_logits_store.
+ * ader_score_items: scores[b, p] (row stride ld_scores >= C) = the logit of item ids[b, p] for row b; -inf where the id is <= 0, above N
+ * or above ncol[b] (ncol: [B], or NULL = N).  Any ids in any order, duplicates allowed; any B.  C = 0 launches nothing.
+ * ader_topk_items_rows / ader_rank_targets_rows: ader_topk_items_cand's / ader_rank_targets_cand's contract with row b's list in place
+ * of the shared one.  Every row is strictly ascending ids >= 1 followed by 0 padding, so ragged lists share one ld; bit 4 of status is
+ * OR-ed in for a row that holds an id < 0, an id after a 0, or a pair that does not ascend -- the result is then unspecified, but every
+ * access stays in bounds.  seen: [B, seen_ld] or NULL, seen_ld <= 4096.  part: ader_topk_rows_ranges(C,k) * Bp * k 64-bit keys of scratch,
+ * ader_topk_rows_ranges = ceil(C / k), at least 1.  The rank of ader_topk_items_rows' items[b, j] > 0 over the same arguments is j; the
+ * target need not be listed and never counts itself, listed or seen.  C = 0 is legal (ids may be NULL): every row is padding, every
+ * rank 0.  tlogit: Bp floats of scratch; rank: [Bp], zeroed here.  Enqueue only.  -2 as the _cand launchers (ader_score_items: H, N),
+ * and when C < 0, ld < C (ld_scores < C), C > 0 with ids == NULL, C > 65536 or seen_ld > 4096. */
+int ader_score_items(const float* rep, const float* emb, int B, int H, int N, const int* ncol, const int* ids, int ld, int C,
+                     float* scores, int ld_scores, void* stream);
+int ader_topk_rows_ranges(int C, int k);
+int ader_topk_items_rows(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* ids, int ld, int C,
+                         const int* seen, int seen_ld, int k, unsigned long long* part, int* items, float* scores, int* status,
+                         void* stream);
+int ader_rank_targets_rows(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
+                           const int* ids, int ld, int C, const int* seen, int seen_ld, float* tlogit, int* rank, int* status,
+                           void* stream);
 /* ader_topk_items with the [B,N] products on the bf16 matrix cores: k_lx3t keeps, per row and item range, every item whose x3 logit is
  * not provably below the row's k-th best by delta[b] = 2^-13 |rep_b| emax[0] (a superset of the exact top-k, at most k + band keys), and
  * k_topk3_finish merges the ranges, re-evaluates the kept pairs through the exact-f32 MFMA chain and selects: for every row with

@@ -2,7 +2,7 @@
 """Top-K recommendation, fused (Engine.recommend) against the composition a caller had to write before it existed.
 
     python tools/bench_topk.py [--check] [--reps 3] [--warmup 1] [--rows 1024] [--k 20] [--datasets YOOCHOOSE,DIGINETICA]
-                               [--train_steps 200] [--cand | --wide] [--out profiles/topk.txt]
+                               [--train_steps 200] [--cand | --wide | --lists] [--out profiles/topk.txt]
 
 (A) Engine.recommend(seq, k, N): ader_topk_items -- k_topk_tile (logit tiles + per-row selection in LDS) and k_topk_merge;
 (B) Engine.logits(seq, N) followed by torch.topk(.., k): dense [n, N] logits in HBM, then torch's selection.  (B) is the yardstick.
@@ -36,7 +36,17 @@ asserts that the items and score bits of (D) equal those of (B') on every row wh
     the yardsticks, alternating with (W) inside every repetition.
 The two wide kernels are timed by torch.profiler over one more call, beside k_topk_tile at the same N in the same run; --check asserts
 that the items and score bits of (W) equal those of (B) on every row whose k-th and (k+1)-th scores of (B) differ, and that (W) at
-k = 64 equals (A) bytewise."""
+k = 64 equals (A) bytewise.
+
+--lists measures the forms whose list differs from row to row instead (default --out profiles/topk_lists.txt), per catalog size and
+for C = 101 (a target and 100 sampled negatives) and C = 1,024 distinct random ids per row:
+(P) Engine.score_items(seq, ids, N): ader_score_items -- k_rowlist<STORE>, 64 positions of one row's list per workgroup, its table
+    rows gathered;
+(Q) Engine.recommend_per_row(seq, k, ids, N): ader_topk_items_rows -- k_rowlist<KEYS> and k_topk_merge;
+(A) Engine.logits + torch.gather, the composition a caller writes without (P), over as many rows as keep its [n, N] logits under
+    0.8 GB; every leg is reported per row.  The three alternate inside every repetition.
+k_rowlist<STORE> is timed by torch.profiler over one more call and its gathered bytes per second set against the HBM probe of
+profiles/; --check asserts that the scores of (P) equal those of (A) bitwise."""
 import argparse
 import os
 import statistics
@@ -217,6 +227,63 @@ def measure_wide(name, eng, seq, N, args):
     return ok
 
 
+def composed_gather(eng, seq, N, ids_d):
+    """(A) of --lists: what a caller writes without Engine.score_items -- dense [n, N] logits, torch.gather at the listed ids, the copy
+    back.  (ids in [1, N] only: the composition has no rule for the others.)"""
+    lg = eng.logits(seq, N)
+    return torch.gather(lg, 1, ids_d.long() - 1).cpu().numpy()
+
+
+def measure_lists(name, eng, seq, N, args):
+    n, k = seq.shape[0], args.k
+    med = statistics.median
+    ldo = (N + 3) // 4 * 4
+    nA = max(1, min(n, 200_000_000 // ldo))              # rows whose dense logits stay under 0.8 GB
+    seq_d = torch.from_numpy(np.ascontiguousarray(seq)).to(eng.device)
+    say("== %s: %d rows ((A): %d rows, 0.8 GB of logits at most, reported per row), k = %d, H = %d; %d repetitions after %d warm-up, "
+        "medians [min .. max]" % (name, n, nA, k, H, args.reps, args.warmup))
+    ok = True
+    rs = np.random.default_rng(1)
+    for C in (101, 1024):
+        # every row its own list: C distinct random ids, ascending (recommend_per_row's form; score_items takes them as they are)
+        ids = np.stack([np.sort(rs.choice(N, size=C, replace=False)) + 1 for _ in range(n)]).astype(np.int32)
+        ids_d = torch.from_numpy(ids).to(eng.device)
+        tP, tQ, tA, p, a = [], [], [], None, None
+        for it in range(args.warmup + args.reps):
+            tp, p = ev_time(lambda: eng.score_items(seq_d, ids_d, N))
+            tq, _ = ev_time(lambda: eng.recommend_per_row(seq_d, k, ids, N))
+            ta, a = ev_time(lambda: composed_gather(eng, seq_d[:nA], N, ids_d[:nA]))
+            if it >= args.warmup:
+                tP.append(tp)
+                tQ.append(tq)
+                tA.append(ta)
+        us = lambda ts, rows: (med(ts) / rows * 1e6, min(ts) / rows * 1e6, max(ts) / rows * 1e6)
+        say("  C = %d ids per row" % C)
+        say("    (P) score_items              %9.2f ms  %9.3f us/row [%.3f .. %.3f]" % ((med(tP) * 1e3,) + us(tP, n)))
+        say("    (Q) recommend_per_row        %9.2f ms  %9.3f us/row [%.3f .. %.3f]   (the host's check of the lists' form is inside the call)"
+            % ((med(tQ) * 1e3,) + us(tQ, n)))
+        say("    (A) logits + torch.gather    %9.2f ms  %9.3f us/row [%.3f .. %.3f]   over %d rows; scratch %d B (the [n, N] float32 logits)"
+            % ((med(tA) * 1e3,) + us(tA, nA) + (nA, nA * ldo * 4)))
+        say("    per row: (P) / (A) = %.4f, (Q) / (A) = %.4f  (< 1: the gathered walk is faster)" %
+            (med(tP) / n / (med(tA) / nA), med(tQ) / n / (med(tA) / nA)))
+        kt = kernel_times(lambda: eng.score_items(seq_d, ids_d, N))
+        row = sum(t for nm, t in kt.items() if "k_rowlist" in nm)
+        if row:
+            say("    k_rowlist<STORE> %.3f ms (torch.profiler, one call): %d x %d table rows of %d B gathered = %.2f TB/s "
+                "(streaming reads of the HBM probe, profiles/bw_probe2_r2z.txt: 5.7 - 6.2 TB/s)" %
+                (row * 1e3, n, C, H * 4, n * C * H * 4.0 / row / 1e12))
+        else:
+            say("    torch.profiler reported no k_rowlist rows (kernels seen: %d): kernel time NOT measured" % len(kt))
+        if args.check:
+            same = np.array_equal(np.ascontiguousarray(p[:nA]).view(np.int32), np.ascontiguousarray(a).view(np.int32))
+            ok &= bool(same)
+            say("    check: the scores of (P) equal those of (A) bitwise on its %d rows: %s" % (nA, same))
+        del ids_d
+    del eng
+    torch.cuda.empty_cache()
+    return ok
+
+
 def kernel_times(fn):
     """Device time per kernel name over one call of fn (torch.profiler); {} if the profiler reports no kernels."""
     from torch.profiler import ProfilerActivity, profile
@@ -242,7 +309,8 @@ def synthetic(N, args):
     for b in range(n):
         ln = int(rs.randint(1, T + 1))
         seq[b, T - ln:] = rs.randint(1, N + 1, size=ln)
-    return (measure_cand if args.cand else measure_wide if args.wide else measure)("N = %d" % N, eng, seq, N, args)
+    return (measure_cand if args.cand else measure_wide if args.wide else measure_lists if args.lists else measure)("N = %d" % N, eng, seq, N,
+                                                                                                                   args)
 
 
 def dataset(name, args):
@@ -356,13 +424,17 @@ def main():
     ap.add_argument("--train_steps", type=int, default=200)
     ap.add_argument("--cand", action="store_true", help="measure the candidate-list form: legs (D), (A) and (B') at M = N/100, N/10 and N")
     ap.add_argument("--wide", action="store_true", help="measure the wide form: legs (W) at k = 64, 256, 1024, (B) and (A)")
-    ap.add_argument("--out", default=None, help="default: profiles/topk.txt, profiles/topk_cand.txt with --cand, profiles/topk_wide.txt with --wide")
+    ap.add_argument("--lists", action="store_true", help="measure the per-row list form: legs (P) score_items and (Q) recommend_per_row at "
+                                                       "C = 101 and 1,024 ids per row against (A) logits + torch.gather")
+    ap.add_argument("--out", default=None, help="default: profiles/topk.txt, profiles/topk_cand.txt with --cand, profiles/topk_wide.txt with "
+                                                "--wide, profiles/topk_lists.txt with --lists")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                "topk_cand.txt" if args.cand else "topk_wide.txt" if args.wide else "topk.txt")
-    if args.cand and args.wide:
-        raise SystemExit("--cand and --wide are two measurements: run them one at a time")
+                                "topk_cand.txt" if args.cand else "topk_wide.txt" if args.wide else "topk_lists.txt" if args.lists
+                                else "topk.txt")
+    if args.cand + args.wide + args.lists > 1:
+        raise SystemExit("--cand, --wide and --lists are three measurements: run them one at a time")
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_topk.py measures on the GPU: no device found")
     _out.append(open(args.out, "w"))
@@ -378,6 +450,19 @@ def main():
         say("# (D) equal to (B') wherever the yardstick's order is decided: %s" % (ok if args.check else "not checked"))
         if args.check and not ok:
             raise SystemExit("top-K mismatch between (D) and (B')")
+        return
+    if args.lists:
+        if args.datasets:
+            raise SystemExit("--lists measures the synthetic catalogs only")
+        say("# tools/bench_topk.py --lists%s: (P) Engine.score_items and (Q) Engine.recommend_per_row (k_rowlist, + k_topk_merge) over random "
+            "lists of C ids per row against (A) Engine.logits + torch.gather, same process, alternating; %s" %
+            (" --check" if args.check else "", torch.cuda.get_device_name(0)))
+        ok = True
+        for N in [int(x) for x in args.catalogs.split(",") if x]:
+            ok &= synthetic(N, args)
+        say("# (P) equal to (A) bitwise: %s" % (ok if args.check else "not checked"))
+        if args.check and not ok:
+            raise SystemExit("score mismatch between (P) and (A)")
         return
     if args.wide:
         say("# tools/bench_topk.py --wide%s: (W) Engine.recommend_wide (k_topk_wide_tile + k_topk_wide_select) at k = 64, 256, 1024 against "
