@@ -111,6 +111,9 @@ _SIGS = {
     "ader_topk_wide_cap": [],
     "ader_topk_wide_slabs": [I, I, I, P, I],
     "ader_topk_items_wide": [P, P, I, I, I, I, P, P, I, I, I, P, P, P, P, P, P, P, P],
+    "ader_row_stats_floats": [I, I],
+    "ader_row_stats": [P, P, I, I, I, I, P, P, P, P, P],
+    "ader_topk_items_stats": [P, P, I, I, I, I, P, P, I, I, P, P, P, P, P, P, P],
     "ader_teacher_ranges": [I, I],
     "ader_teacher_rows": [P, P, P, I, I, I, I, I, P, L, P, P, P, P],
     "ader_teacher_rows_shard": [P, P, P, I, I, I, I, I, I, I, P, L, P, P, P],
@@ -208,7 +211,7 @@ class AderStepKey(ctypes.Structure):
     _fields_ = [("blob", c_int), ("site", c_int), ("offset", c_size_t)]
 
 
-_NO_CHECK = {"ader_step_fn_index", "ader_step_fn_args", "ader_step_plan_failed_op", "ader_ln_bwd_slabs", "ader_gemm_atb_batch_slabs", "ader_gemm_atb_slabs", "ader_logits_sub", "ader_logits_parts", "ader_logits_ranges", "ader_lbf_ranges", "ader_lbf_ranges_kd", "ader_lbf_readout_ranges", "ader_lx3_readout_ranges", "ader_wprep_elems", "ader_fused_bucket_gran", "ader_fused_bucket_id0", "ader_tab_meta_ints", "ader_x3_rep_image_bytes", "ader_sparse_lists_scratch_n", "ader_sparse_lists_starts", "ader_topk_kmax", "ader_topk_ranges", "ader_topk_rows_ranges", "ader_topk_x3_kmax", "ader_topk_x3_ranges", "ader_topk_wide_kmax", "ader_topk_wide_cap", "ader_topk_wide_slabs", "ader_teacher_ranges"}
+_NO_CHECK = {"ader_step_fn_index", "ader_step_fn_args", "ader_step_plan_failed_op", "ader_ln_bwd_slabs", "ader_gemm_atb_batch_slabs", "ader_gemm_atb_slabs", "ader_logits_sub", "ader_logits_parts", "ader_logits_ranges", "ader_lbf_ranges", "ader_lbf_ranges_kd", "ader_lbf_readout_ranges", "ader_lx3_readout_ranges", "ader_wprep_elems", "ader_fused_bucket_gran", "ader_fused_bucket_id0", "ader_tab_meta_ints", "ader_x3_rep_image_bytes", "ader_sparse_lists_scratch_n", "ader_sparse_lists_starts", "ader_topk_kmax", "ader_topk_ranges", "ader_topk_rows_ranges", "ader_topk_x3_kmax", "ader_topk_x3_ranges", "ader_topk_wide_kmax", "ader_topk_wide_cap", "ader_topk_wide_slabs", "ader_row_stats_floats", "ader_teacher_ranges"}
 
 
 class AderHipError(RuntimeError):

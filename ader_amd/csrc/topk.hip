@@ -11,6 +11,8 @@
 //   k_rowlist<STORE>                         the scores of the listed items, any ids      (Engine.score_items, ader_score_items)
 //   k_rowlist<KEYS> + k_topk_merge           the k <= 64 best of each row's own list      (Engine.recommend_per_row, ader_topk_items_rows)
 //   k_rowlist<RANK>                          the target's rank among each row's own list  (Engine.rank_targets_per_row, ader_rank_targets_rows)
+// (The first form with every row's log-sum-exp and entropy out of the same walk is topk_stats.hip, a translation unit of its own for the
+// reason given below; it reaches k_topk_merge through topk_merge_launch.)
 // A candidate is one 64-bit key (topk_key.h): order-preserving float bits above, the complemented 1-based item id below, so ONE unsigned
 // compare is the total order and no two candidates of a row compare equal.  Key 0 = "no candidate".  (The MFMA chain starts from +0 and
 // rounds to nearest, so it never yields -0; topk_key still folds -0 onto +0, as == does.)
@@ -727,6 +729,18 @@ static inline int wide_runs(int ntile, int nchunk) {
 // in logits.hip: the exact-f32 logit of every row's target (k_target_logit), what ader_rank_targets compares against
 int rank_target_logit_launch(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* target, const int* ncol,
                              float* tlogit, void* stream);
+
+// for topk_stats.hip, whose tile kernel fills `part` as k_topk_tile does: k_topk_merge over part [ranges][Bp][k] -> items / scores
+// [B,k], the second launch of ader_topk_items (host code only: the kernels of this file are as they were, tools/isa_digest.py)
+int topk_merge_launch(int B, int Bp, int k, int ranges, unsigned long long* part, int* items, float* scores, void* stream) {
+    if (k < 1 || k > TOPK_KMAX || ranges < 1 || B > Bp) return -2;
+    if (B <= 0) return 0;
+    TopkArgs a = {};
+    a.B = B; a.Bp = Bp; a.k = k; a.ranges = ranges; a.part = part; a.items = items; a.scores = scores;
+    hipLaunchKernelGGL(k_topk_merge, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" {
 

@@ -90,6 +90,22 @@ def row_candidate_ids(lists, N, item_num):
     return res
 
 
+def log_probs(scores, lse):
+    """The log-probabilities of an answer: scores float32 [n,k] (any top-K call's, or score_items') and lse float32 [n] (row_stats',
+    recommend_stats') -> scores - lse[:, None], one float32 subtraction per entry; a padding score (-inf) stays -inf.  The
+    distribution is the softmax over all of 1..max_item: items a call excluded keep their mass."""
+    s, z = np.asarray(scores, dtype=np.float32), np.asarray(lse, dtype=np.float32)
+    _check(s.ndim == 2 and z.ndim == 1 and z.shape[0] == s.shape[0],
+           "log_probs: scores must be [n, k] and lse [n] (got %s and %s)" % (s.shape, z.shape))
+    return s - z[:, None]
+
+
+def probs(scores, lse):
+    """exp(log_probs(scores, lse)) in float32: the model's probability of every returned item, 0 for padding.  They need not sum to 1
+    over an answer (the items left out, excluded ones included, hold the rest)."""
+    return np.exp(log_probs(scores, lse))
+
+
 def rank_x3_supports(H):
     """Hidden sizes of k_lx3k (lx3f_supports of csrc/logits_x3.hip)."""
     return H % 2 == 0 and 8 <= H <= 160 and H % 8 in (0, 4, 6)
@@ -332,6 +348,66 @@ class _Infer:
         part = self.buf("tk_part", (call("ader_topk_ranges", N, Bp) * Bp * k,), torch.int64)
         call("ader_topk_items", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
              ptr(seen), seen.shape[1] if seen is not None else 0, k, ptr(part), ptr(items), ptr(scores), self._stream())
+
+    def row_stats(self, seq, max_item=None):
+        """The model's distribution per row, without the [n, max_item] matrix: (lse, entropy), float32 [n] numpy.  With s = the float32
+        logits(seq, max_item)[b]: lse[b] = log sum exp(s) and entropy[b] = -sum p log p in nats, p = exp(s - lse[b]) -- the softmax
+        the loss trains, over ALL of 1..max_item (None: the whole catalog).  One catalog walk (ader_row_stats, k_row_stats): per-lane
+        (max, sum, weighted sum) states merged in a fixed order, no float atomics, so two calls give the same bits, and they are the
+        bits recommend_stats returns for the same rows in the same chunking.  A batch of another size partitions the catalog
+        differently (ader_topk_ranges) and may differ in the last bits.  Chunks of MAX_ROWS rows, one device -> host copy."""
+        N = self.item_num if max_item is None else int(max_item)
+        _check(1 <= N <= self.item_num, "row_stats: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        self._refresh_stream()
+        self.sync_table()
+        seq = self._seq_in(seq)
+        n = seq.shape[0]
+        res = torch.empty((2, n), dtype=torch.float32, device=self.device)       # lse | entropy: one copy back
+        for s in range(0, n, self.MAX_ROWS):
+            e = min(n, s + self.MAX_ROWS)
+            rep = self.forward(seq[s:e], training=False)
+            B = e - s
+            Bp = (B + 63) // 64 * 64
+            spart = self.buf("ts_spart", (call("ader_row_stats_floats", N, Bp),))
+            call("ader_row_stats", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)), ptr(spart),
+                 ptr(res[0, s:e]), ptr(res[1, s:e]), self._stream())
+        host = res.cpu().numpy()
+        return host[0], host[1]
+
+    def recommend_stats(self, seq, k, max_item=None, exclude_seen=False):
+        """recommend(dtype="f32") with the row's normaliser out of the same catalog walk (ader_topk_items_stats, k_topk_tile_stats):
+        (items int32 [n,k], scores float32 [n,k], lse float32 [n], entropy float32 [n]) as numpy.  items / scores are
+        recommend(dtype="f32")'s, byte for byte (order, ties, exclude_seen, item 0 / -inf padding); lse / entropy are row_stats',
+        bit for bit for the same rows in the same chunking.  They run over ALL of 1..max_item whatever exclude_seen removes from the
+        answer: an excluded item keeps its mass, so probs(scores, lse) of an answer need not sum to 1, and a probability means the
+        same thing in every call.  k in 1..ader_topk_kmax() (= 64); exact-f32 chain only, whatever topk_dtype says.  Chunks of
+        MAX_ROWS rows, one device -> host copy.  (A method of its own: recommend's parameter list is pinned by the tests.)"""
+        kmax = call("ader_topk_kmax")
+        k = int(k)
+        N = self.item_num if max_item is None else int(max_item)
+        _check(1 <= k <= kmax, "recommend_stats: k must be in 1..%d (got %d)" % (kmax, k))
+        _check(1 <= N <= self.item_num, "recommend_stats: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        self._refresh_stream()
+        self.sync_table()
+        self.last_topk_stats = None
+        seq = self._seq_in(seq)
+        n = seq.shape[0]
+        res = torch.empty(2 * n * k + 2 * n, dtype=torch.int32, device=self.device)      # items | score bits | lse bits | entropy bits
+        items, scores = res[:n * k].view(n, k), res[n * k:2 * n * k].view(n, k).view(torch.float32)
+        stats = res[2 * n * k:].view(2, n).view(torch.float32)
+        for s in range(0, n, self.MAX_ROWS):
+            e = min(n, s + self.MAX_ROWS)
+            rep = self.forward(seq[s:e], training=False)
+            B = e - s
+            Bp = (B + 63) // 64 * 64
+            part = self.buf("tk_part", (call("ader_topk_ranges", N, Bp) * Bp * k,), torch.int64)
+            spart = self.buf("ts_spart", (call("ader_row_stats_floats", N, Bp),))
+            call("ader_topk_items_stats", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
+                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, ptr(part), ptr(spart), ptr(items[s:e]), ptr(scores[s:e]),
+                 ptr(stats[0, s:e]), ptr(stats[1, s:e]), self._stream())
+        host = res.cpu().numpy()
+        st = host[2 * n * k:].reshape(2, n).view(np.float32)
+        return host[:n * k].reshape(n, k), host[n * k:2 * n * k].reshape(n, k).view(np.float32), st[0], st[1]
 
     def recommend_among(self, seq, k, candidates, max_item=None, exclude_seen=False, dtype=None):
         """recommend restricted to a candidate item list: candidates is a 1-D integer array / tensor of item ids, shared by all rows

@@ -12,8 +12,8 @@ import numpy as np
 import torch
 
 from ._lib import call
-from .engine import Engine
-from .engine.infer import _check_topk_dtype
+from .engine import Engine, _check
+from .engine.infer import _check_topk_dtype, log_probs, probs
 
 
 class _Handle:
@@ -93,6 +93,31 @@ class Ader:
             _check_topk_dtype(self.engine.topk_dtype if dtype is None else dtype)
             return self.engine.recommend_wide(seq, k, max_item, exclude_seen)
         return self.engine.recommend(seq, k, max_item, exclude_seen, dtype=dtype)
+
+    def row_stats(self, seq, max_item=None):
+        """(lse, entropy), float32 [n]: the log-sum-exp and the entropy (nats) of every session's softmax over items 1..max_item, in
+        one catalog walk and without the [n, max_item] logits (Engine.row_stats)."""
+        return self.engine.row_stats(seq, max_item)
+
+    def recommend_probs(self, seq, k, max_item=None, exclude_seen=False, candidates=None, form="prob"):
+        """recommend with the model's probabilities in place of raw scores: (items int32 [n,k], values float32 [n,k]), values = the
+        softmax probability of every returned item (form="prob") or its logarithm (form="logprob"); padding (item 0) gets 0 / -inf.
+        The distribution is always the softmax over ALL of 1..max_item, the one the loss trains: an item left out by exclude_seen or
+        by candidates keeps its mass, so the values of an answer need not sum to 1, and a probability means the same thing in every
+        call.  Exact-f32 chain.  Whole catalog, k <= ader_topk_kmax() (= 64): one catalog walk (Engine.recommend_stats).  With
+        candidates (Engine.recommend_among), or k up to 1024 (Engine.recommend_wide), the normaliser comes from Engine.row_stats: a
+        second catalog walk."""
+        e = self.engine
+        _check(form in ("prob", "logprob"), "recommend_probs: form must be 'prob' or 'logprob' (got %r)" % (form,))
+        if candidates is not None:
+            items, scores = e.recommend_among(seq, k, candidates, max_item, exclude_seen, dtype="f32")
+            lse, _ = e.row_stats(seq, max_item)
+        elif int(k) > call("ader_topk_kmax"):
+            items, scores = e.recommend_wide(seq, k, max_item, exclude_seen)
+            lse, _ = e.row_stats(seq, max_item)
+        else:
+            items, scores, lse, _ = e.recommend_stats(seq, k, max_item, exclude_seen)
+        return items, (probs if form == "prob" else log_probs)(scores, lse)
 
     def score_items(self, seq, items, max_item=None):
         """The logits of items[b, c] for session b, float32 [n, C] aligned with items (Engine.score_items): what a re-ranking stage

@@ -29,6 +29,9 @@ violation (never clamps ids, never falls back to the CPU).  `import ader_amd.ops
                                                                          filter keeping a superset of the top-k + exact-f32 recheck)
   ader::topk_items_wide(rep, emb, seen, N, k, cap)             -> (items, scores, overflowed)   topk_items for k up to 1024 by slab
                                                                          and select: per-row key lists in global memory, no [B, N] logits
+  ader::topk_items_stats(rep, emb, seen, N, k)                 -> (items, scores, lse, entropy)   topk_items' bytes plus the row's
+                                                                         log-sum-exp and entropy over all of 1..N, from the same walk
+  ader::row_stats(rep, emb, N)                                 -> (lse, entropy)   the two statistics alone: log p = score - lse
   ader::teacher_rows(trep, temb, ex_trow, Np)                  -> (rows, trow_local)   teacher logits of a step's exemplar rows from
                                                                          stored representations + a table snapshot: the bits of
                                                                          ader_logits_store (util.py:433, ADER.py:134-135)
@@ -436,6 +439,48 @@ def topk_items_wide(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.T
 def _(rep, emb, seen, N, k, cap):
     B = rep.shape[0]
     return rep.new_empty((B, k), dtype=torch.int32), rep.new_empty((B, k)), rep.new_empty((B,), dtype=torch.int32)
+
+
+@torch.library.custom_op("ader::topk_items_stats", mutates_args=())
+def topk_items_stats(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor], N: int,
+                     k: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """topk_items (its arguments, its checks, the same bytes of items / scores) with the row's normaliser out of the same catalog walk
+    (ader_topk_items_stats) -> (items int32 [B,k], scores float32 [B,k], lse float32 [B], entropy float32 [B]): lse = log sum exp and
+    entropy = -sum p log p (nats) of softmax over the logits of ALL items 1..N -- seen removes items from the answer, not from the
+    sums, so exp(scores - lse) need not sum to 1.  lse / entropy are row_stats' bits for the same rep."""
+    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_stats", rep, emb, seen, N, k, call("ader_topk_kmax"))
+    dev = rep.device
+    part = torch.empty(call("ader_topk_ranges", N, Bp) * Bp * k, dtype=torch.int64, device=dev)
+    spart = torch.empty(call("ader_row_stats_floats", N, Bp), device=dev)
+    lse, entropy = torch.empty(B, device=dev), torch.empty(B, device=dev)
+    call("ader_topk_items_stats", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen_ld, k, ptr(part), ptr(spart), ptr(items),
+         ptr(scores), ptr(lse), ptr(entropy), _st())
+    return items, scores, lse, entropy
+
+
+@topk_items_stats.register_fake
+def _(rep, emb, seen, N, k):
+    B = rep.shape[0]
+    return rep.new_empty((B, k), dtype=torch.int32), rep.new_empty((B, k)), rep.new_empty((B,)), rep.new_empty((B,))
+
+
+@torch.library.custom_op("ader::row_stats", mutates_args=())
+def row_stats(rep: torch.Tensor, emb: torch.Tensor, N: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """rep [B,H], emb [V,H] (row 0 = padding item) -> (lse float32 [B], entropy float32 [B]) of softmax over the logits of items 1..N
+    (the float32 of ader_logits_store), in one catalog walk and without the [B,N] matrix (ader_row_stats).  The same rep, emb and N
+    give the same bits on every call; another B may differ in the last bits (the catalog is partitioned by the padded batch)."""
+    B, Bp, H, _, ncol, _, _ = _topk_prologue("row_stats", rep, emb, None, N, 1, 1)
+    dev = rep.device
+    spart = torch.empty(call("ader_row_stats_floats", N, Bp), device=dev)
+    lse, entropy = torch.empty(B, device=dev), torch.empty(B, device=dev)
+    call("ader_row_stats", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(spart), ptr(lse), ptr(entropy), _st())
+    return lse, entropy
+
+
+@row_stats.register_fake
+def _(rep, emb, N):
+    B = rep.shape[0]
+    return rep.new_empty((B,)), rep.new_empty((B,))
 
 
 @torch.library.custom_op("ader::teacher_rows", mutates_args=())

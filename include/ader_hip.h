@@ -336,6 +336,24 @@ int ader_topk_wide_slabs(int N, int k, int cap, int* begin, int max);
 int ader_topk_items_wide(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
                          int k, int cap, unsigned long long* list, int* cnt, unsigned long long* thr, int* row_status, int* diag,
                          int* items, float* scores, void* stream);
+/* The model's distribution beside its order (csrc/topk_stats.hip): for every real row b, over the float32 logits s(b,i) of ALL items
+ * i = 1..N (the float32 of ader_logits_store), lse[b] = log sum_i exp(s(b,i)) and entropy[b] = -sum_i p_i log p_i in nats, p_i =
+ * exp(s(b,i) - lse[b]): the softmax the loss trains.  logprob = score - lse is then one subtraction, and no [B,N] matrix is written.
+ * ader_row_stats: the two statistics alone, one catalog walk.  ader_topk_items_stats: ader_topk_items -- its arguments, its -2 conditions
+ * and the same bytes of items / scores -- with the statistics out of the same walk.  seen removes items from the answer, never from the
+ * sums: an excluded item keeps its mass, so the probabilities of an answer need not sum to 1, and lse / entropy do not depend on seen.
+ * Per-lane (max, sum exp, sum exp * (s - max)) states merged in a fixed order, no float atomics: the same inputs with the same (N, Bp)
+ * give the same bits on every run, and the two launchers give the same bits of lse / entropy for the same (rows, N, Bp).  Another Bp
+ * partitions the catalog differently (ader_topk_ranges) and may differ in the last bits.
+ * ncol: [Bp] = N for real rows, 0 for padding.  part: ader_topk_ranges(N,Bp)*Bp*k 64-bit keys of scratch; spart:
+ * ader_row_stats_floats(N,Bp) = ader_topk_ranges(N,Bp)*Bp*4 floats of scratch.  lse, entropy: [B]; nothing is written for padding
+ * rows.  Enqueue only.  -2 as ader_topk_items (ader_row_stats: Bp % 64 != 0, Bp > 1024, B > Bp, H > 160, N < 1). */
+int ader_row_stats_floats(int N, int Bp);
+int ader_row_stats(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, float* spart, float* lse,
+                   float* entropy, void* stream);
+int ader_topk_items_stats(const float* rep, const float* emb, int B, int Bp, int H, int N, const int* ncol, const int* seen, int seen_ld,
+                          int k, unsigned long long* part, float* spart, int* items, float* scores, float* lse, float* entropy,
+                          void* stream);
 
 /* Teacher logits of a step's exemplar rows, regenerated from stored teacher representations (util.py:433 computes them, ADER.py:134-135
  * consumes them as softmax(exemplar_logits)): trep [E,H] = the teacher's representations, temb = the item table as it stood when the

@@ -2,7 +2,7 @@
 """Top-K recommendation, fused (Engine.recommend) against the composition a caller had to write before it existed.
 
     python tools/bench_topk.py [--check] [--reps 3] [--warmup 1] [--rows 1024] [--k 20] [--datasets YOOCHOOSE,DIGINETICA]
-                               [--train_steps 200] [--cand | --wide | --lists] [--out profiles/topk.txt]
+                               [--train_steps 200] [--cand | --wide | --lists | --stats] [--out profiles/topk.txt]
 
 (A) Engine.recommend(seq, k, N): ader_topk_items -- k_topk_tile (logit tiles + per-row selection in LDS) and k_topk_merge;
 (B) Engine.logits(seq, N) followed by torch.topk(.., k): dense [n, N] logits in HBM, then torch's selection.  (B) is the yardstick.
@@ -46,7 +46,17 @@ for C = 101 (a target and 100 sampled negatives) and C = 1,024 distinct random i
 (A) Engine.logits + torch.gather, the composition a caller writes without (P), over as many rows as keep its [n, N] logits under
     0.8 GB; every leg is reported per row.  The three alternate inside every repetition.
 k_rowlist<STORE> is timed by torch.profiler over one more call and its gathered bytes per second set against the HBM probe of
-profiles/; --check asserts that the scores of (P) equal those of (A) bitwise."""
+profiles/; --check asserts that the scores of (P) equal those of (A) bitwise.
+
+--stats measures top-K with the row's normaliser instead (default --out profiles/topk_stats.txt), per catalog size:
+(S) Engine.recommend_stats(seq, k, N): ader_topk_items_stats -- k_topk_tile_stats (k_topk_tile's walk with the per-lane log-sum-exp and
+    entropy states), k_topk_merge and k_stats_merge;
+(R) Engine.row_stats(seq, N): ader_row_stats -- k_row_stats (the same walk without the row buffer) and k_stats_merge;
+(A) Engine.recommend(dtype="f32") and (L) Engine.row_losses on the same rows, the only matrix-free route to a log-sum-exp without (S):
+    the yardsticks.  The legs alternate inside every repetition, (A) runs twice per repetition and the spread of its runs is what
+    (A) + (L) - (S), the time the fusion saves, is set against.  The kernels are timed by torch.profiler over one more call each.
+--check asserts that items / scores of (S) equal (A) bytewise, that lse / entropy of (S) equal (R) bitwise, and that row_losses agrees
+with lse - score_items to 1e-4."""
 import argparse
 import os
 import statistics
@@ -284,6 +294,70 @@ def measure_lists(name, eng, seq, N, args):
     return ok
 
 
+def measure_stats(name, eng, seq, N, args):
+    n, k = seq.shape[0], args.k
+    seq_d = torch.from_numpy(np.ascontiguousarray(seq)).to(eng.device)
+    pos_d = torch.from_numpy(np.random.RandomState(1).randint(1, N + 1, size=n).astype(np.int32)).to(eng.device)
+    med = statistics.median
+    rows = min(n, eng.MAX_ROWS)
+    Bp = (rows + 63) // 64 * 64
+    ranges = call("ader_topk_ranges", N, Bp)
+    tA, tA2, tL, tS, tR, a, s, r = [], [], [], [], [], None, None, None
+    for it in range(args.warmup + args.reps):
+        ta, a = ev_time(lambda: eng.recommend(seq_d, k, N, dtype="f32"))
+        tl, _ = ev_time(lambda: eng.row_losses(seq_d, pos_d, N).cpu())
+        ts, s = ev_time(lambda: eng.recommend_stats(seq_d, k, N))
+        tr, r = ev_time(lambda: eng.row_stats(seq_d, N))
+        ta2, _ = ev_time(lambda: eng.recommend(seq_d, k, N, dtype="f32"))
+        if it >= args.warmup:
+            tA.append(ta)
+            tA2.append(ta2)
+            tL.append(tl)
+            tS.append(ts)
+            tR.append(tr)
+    allA = tA + tA2
+    spread = max(allA) - min(allA)
+    say("== %s: %d rows, k = %d, H = %d; %d repetitions after %d warm-up, medians [min .. max]" % (name, n, k, H, args.reps, args.warmup))
+    say("  (A) recommend                %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   twice per repetition: spread (max - min) of its %d runs %.3f ms"
+        % (med(allA) * 1e3, min(allA) * 1e3, max(allA) * 1e3, n / med(allA), len(allA), spread * 1e3))
+    say("  (L) row_losses               %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   the parent's matrix-free route to a log-sum-exp" %
+        (med(tL) * 1e3, min(tL) * 1e3, max(tL) * 1e3, n / med(tL)))
+    say("  (S) recommend_stats          %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B (%d ranges x %d rows x (k keys of 8 B + 16 B))" %
+        (med(tS) * 1e3, min(tS) * 1e3, max(tS) * 1e3, n / med(tS), ranges * Bp * (k * 8 + 16), ranges, Bp))
+    say("  (R) row_stats                %9.2f ms [%.2f .. %.2f]  %9.0f rows/s   scratch %12d B" %
+        (med(tR) * 1e3, min(tR) * 1e3, max(tR) * 1e3, n / med(tR), ranges * Bp * 16))
+    gain = med(allA) + med(tL) - med(tS)
+    say("  (S) / (A) whole call %.3f; (A) + (L) - (S) = %.3f ms = %.1f x the spread of (A): the fusion %s; (R) / (A) %.3f" %
+        (med(tS) / med(allA), gain * 1e3, gain / spread if spread > 0 else float("inf"),
+         "pays" if gain > spread else "does NOT pay beyond the spread", med(tR) / med(allA)))
+    kts = kernel_times(lambda: eng.recommend_stats(seq_d, k, N))
+    kta = kernel_times(lambda: eng.recommend(seq_d, k, N, dtype="f32"))
+    ktr = kernel_times(lambda: eng.row_stats(seq_d, N))
+    pick = lambda kt, key: sum(t for nm, t in kt.items() if key in nm and (key != "k_topk_tile" or "k_topk_tile_stats" not in nm))
+    if pick(kts, "k_topk_tile_stats") and pick(kta, "k_topk_tile"):
+        say("  kernels (torch.profiler, one call each): k_topk_tile_stats %.3f ms + k_topk_merge %.3f ms + k_stats_merge %.3f ms; k_topk_tile of "
+            "(A) %.3f ms: tile_stats / tile = %.3f; k_row_stats %.3f ms + k_stats_merge %.3f ms" %
+            (pick(kts, "k_topk_tile_stats") * 1e3, pick(kts, "k_topk_merge") * 1e3, pick(kts, "k_stats_merge") * 1e3,
+             pick(kta, "k_topk_tile") * 1e3, pick(kts, "k_topk_tile_stats") / pick(kta, "k_topk_tile"), pick(ktr, "k_row_stats") * 1e3,
+             pick(ktr, "k_stats_merge") * 1e3))
+    else:
+        say("  torch.profiler reported no k_topk_tile_stats / k_topk_tile rows (kernels seen: %d, %d): kernel time NOT measured" %
+            (len(kts), len(kta)))
+    ok = True
+    if args.check:
+        same = (np.array_equal(a[0], s[0]) and np.array_equal(np.ascontiguousarray(a[1]).view(np.int32), np.ascontiguousarray(s[1]).view(np.int32)))
+        same_r = (np.array_equal(s[2].view(np.int32), r[0].view(np.int32)) and np.array_equal(s[3].view(np.int32), r[1].view(np.int32)))
+        loss = eng.row_losses(seq_d, pos_d, N).cpu().numpy()
+        mine = s[2] - eng.score_items(seq_d, pos_d[:, None].contiguous(), N)[:, 0]
+        err = float(np.abs(loss - mine).max())
+        ok = bool(same and same_r and err < 1e-4)
+        say("  check: items / scores of (S) equal (A) bytewise: %s; lse / entropy of (S) equal (R) bitwise: %s; max |row_losses - (lse - "
+            "score)| = %.3g; entropy in [%.4f, %.4f] nats of log N = %.4f" % (same, same_r, err, s[3].min(), s[3].max(), np.log(N)))
+    del eng
+    torch.cuda.empty_cache()
+    return ok
+
+
 def kernel_times(fn):
     """Device time per kernel name over one call of fn (torch.profiler); {} if the profiler reports no kernels."""
     from torch.profiler import ProfilerActivity, profile
@@ -309,8 +383,8 @@ def synthetic(N, args):
     for b in range(n):
         ln = int(rs.randint(1, T + 1))
         seq[b, T - ln:] = rs.randint(1, N + 1, size=ln)
-    return (measure_cand if args.cand else measure_wide if args.wide else measure_lists if args.lists else measure)("N = %d" % N, eng, seq, N,
-                                                                                                                   args)
+    return (measure_cand if args.cand else measure_wide if args.wide else measure_lists if args.lists else measure_stats if args.stats
+            else measure)("N = %d" % N, eng, seq, N, args)
 
 
 def dataset(name, args):
@@ -426,15 +500,17 @@ def main():
     ap.add_argument("--wide", action="store_true", help="measure the wide form: legs (W) at k = 64, 256, 1024, (B) and (A)")
     ap.add_argument("--lists", action="store_true", help="measure the per-row list form: legs (P) score_items and (Q) recommend_per_row at "
                                                        "C = 101 and 1,024 ids per row against (A) logits + torch.gather")
+    ap.add_argument("--stats", action="store_true", help="measure top-K with the row's log-sum-exp and entropy: legs (S) recommend_stats and "
+                                                       "(R) row_stats against (A) recommend and (L) row_losses")
     ap.add_argument("--out", default=None, help="default: profiles/topk.txt, profiles/topk_cand.txt with --cand, profiles/topk_wide.txt with "
-                                                "--wide, profiles/topk_lists.txt with --lists")
+                                                "--wide, profiles/topk_lists.txt with --lists, profiles/topk_stats.txt with --stats")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "topk_cand.txt" if args.cand else "topk_wide.txt" if args.wide else "topk_lists.txt" if args.lists
-                                else "topk.txt")
-    if args.cand + args.wide + args.lists > 1:
-        raise SystemExit("--cand, --wide and --lists are three measurements: run them one at a time")
+                                else "topk_stats.txt" if args.stats else "topk.txt")
+    if args.cand + args.wide + args.lists + args.stats > 1:
+        raise SystemExit("--cand, --wide, --lists and --stats are four measurements: run them one at a time")
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_topk.py measures on the GPU: no device found")
     _out.append(open(args.out, "w"))
@@ -450,6 +526,19 @@ def main():
         say("# (D) equal to (B') wherever the yardstick's order is decided: %s" % (ok if args.check else "not checked"))
         if args.check and not ok:
             raise SystemExit("top-K mismatch between (D) and (B')")
+        return
+    if args.stats:
+        if args.datasets:
+            raise SystemExit("--stats measures the synthetic catalogs only")
+        say("# tools/bench_topk.py --stats%s: (S) Engine.recommend_stats (k_topk_tile_stats + k_topk_merge + k_stats_merge) and (R) "
+            "Engine.row_stats (k_row_stats + k_stats_merge) against (A) Engine.recommend and (L) Engine.row_losses, same process, "
+            "alternating; %s" % (" --check" if args.check else "", torch.cuda.get_device_name(0)))
+        ok = True
+        for N in [int(x) for x in args.catalogs.split(",") if x]:
+            ok &= synthetic(N, args)
+        say("# items / scores of (S) equal to (A) bytewise, lse / entropy of (S) equal to (R) bitwise: %s" % (ok if args.check else "not checked"))
+        if args.check and not ok:
+            raise SystemExit("mismatch between (S) and its yardsticks")
         return
     if args.lists:
         if args.datasets:
