@@ -2,6 +2,7 @@
 import numpy as np
 import torch
 
+from . import infer_launch as L
 from .._lib import call, ptr
 from .common import TeacherRep, _check
 
@@ -111,28 +112,75 @@ def rank_x3_supports(H):
     return H % 2 == 0 and 8 <= H <= 160 and H % 8 in (0, 4, 6)
 
 
+class _Packed:
+    """The answer of a top-K call as ONE int32 device tensor, items [n,k] | score bits [n,k] | extras ..., so that it comes back in one
+    copy.  rows(s, e) gives the device views items[s:e] (int32) / scores[s:e] (float32) for a launch to write into, extra[i] the
+    i-th extra as an int32 vector; cpu() returns the same views of the host copy.  (Built from as few tensor operations as the layout
+    allows: each costs the host 1 - 2 us, and the calls on short batches are host-bound.)"""
+
+    def __init__(self, dev, n, k, extras=(), zero=False):
+        self.shape, self.extras = (2, n, k), extras
+        self.dev = (torch.zeros if zero else torch.empty)(2 * n * k + sum(extras), dtype=torch.int32, device=dev)
+        self.both, self.extra = self._split(self.dev)
+        self.scores = self.both[1].view(torch.float32)
+
+    def _split(self, t):
+        if not self.extras:
+            return t.reshape(self.shape), ()
+        o = 2 * self.shape[1] * self.shape[2]
+        cuts = [o]
+        for m in self.extras:
+            cuts.append(cuts[-1] + m)
+        return t[:o].reshape(self.shape), [t[a:b] for a, b in zip(cuts, cuts[1:])]
+
+    def rows(self, s, e):
+        return self.both[0, s:e], self.scores[s:e]
+
+    def cpu(self):
+        both, extra = self._split(self.dev.cpu().numpy())
+        return (both[0], both[1].view(np.float32), *extra)
+
+
 class _Infer:
     last_topk_stats = None     # Engine.recommend(dtype="x3"): kept_pairs, rows, overflowed_rows, fallback_chunks, max_err_over_delta of the last call
     last_rank_stats = None     # Engine.rank_targets(dtype="x3"): candidates, pairs, overflowed_chunks, max_err_over_delta of the last call
 
+    # ---------------------------------------------------------------------------------------- what every entry point shares
+    def _enter(self, seq):
+        """The prelude of a public inference call, after its host checks: this call's stream, a whole table, seq on the device."""
+        self._refresh_stream()
+        self.sync_table()
+        return self._seq_in(seq)
+
+    def _chunks(self, seq, rep_all=None):
+        """(s, e, B, rep) over chunks of MAX_ROWS rows: rep = the eval-mode forward of seq[s:e].  rep_all [n, H], if given, keeps every
+        chunk's rep (rep is then its slice): what a fallback after the copy back works on."""
+        n = seq.shape[0]
+        for s in range(0, n, self.MAX_ROWS):
+            e = min(n, s + self.MAX_ROWS)
+            rep = self.forward(seq[s:e], training=False)
+            if rep_all is not None:
+                rep_all[s:e] = rep
+                rep = rep_all[s:e]
+            yield s, e, e - s, rep
+
+    def _check_kN(self, name, max_item, k=None, kmax=None):
+        """max_item (None: the whole catalog) and, if given, k against kmax, under the calling method's name -> N or (k, N)."""
+        N = self.item_num if max_item is None else int(max_item)
+        if k is not None:
+            k = int(k)
+            _check(1 <= k <= kmax, "%s: k must be in 1..%d (got %d)" % (name, kmax, k))
+        _check(1 <= N <= self.item_num, "%s: max_item must be in 1..%d (got %d)" % (name, self.item_num, N))
+        return N if k is None else (k, N)
+
     # ---------------------------------------------------------------------------------------- inference paths
     def encode(self, seq):
         """Eval-mode representation (is_training=False): rep [n,H] for any n (chunks of MAX_ROWS)."""
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        n = seq.shape[0]
-        out = torch.empty((n, self.H), dtype=torch.float32, device=self.device)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            out[s:e] = self.forward(seq[s:e], training=False)
+        seq = self._enter(seq)
+        out = torch.empty((seq.shape[0], self.H), dtype=torch.float32, device=self.device)
+        for s, e, _, rep in self._chunks(seq):
+            out[s:e] = rep
         return out
-
-    def _ncol_all(self, Bp, B, N):
-        t = self.buf("ncol_all", (Bp,), torch.int32)
-        t.zero_()
-        t[:B] = N
-        return t
 
     def logits_from_rep(self, rep, max_item, out=None):
         """Dense logits [n, N] = rep . E[1..N]^T  (ADER.py:92)."""
@@ -145,11 +193,7 @@ class _Infer:
             out = torch.empty((n, (N + 3) // 4 * 4), dtype=torch.float32, device=self.device)[:, :N]
         for s in range(0, n, self.MAX_ROWS):
             e = min(n, s + self.MAX_ROWS)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            r = rep[s:e].contiguous()
-            call("ader_logits_store", ptr(r), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
-                 ptr(out[s:e]), out.stride(0), self._stream())
+            L.logits_store(self.buf, self._stream(), rep[s:e].contiguous(), self._pp["emb"], self.H, N, out[s:e])
         return out
 
     def logits(self, seq, max_item):
@@ -198,25 +242,10 @@ class _Infer:
         dtype = _check_rank_dtype(self.rank_dtype if dtype is None else dtype)
         if dtype == "x3" and rank_x3_supports(self.H):       # (other hidden sizes: the exact kernel, as the flash forward does)
             return self._rank_targets_x3(seq, pos, max_item, cand_cap)
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        pos = self._dev_i32(pos)
-        n, N = seq.shape[0], int(max_item)
-        out = torch.empty(n, dtype=torch.int32, device=self.device)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            rep = self.forward(seq[s:e], training=False)
-            tl = self.buf("rk_tl", (Bp,))
-            rk = self.buf("rk_rank", (Bp,), torch.int32)
-            tgt = self.buf("rk_tgt", (Bp,), torch.int32)
-            tgt.zero_()
-            tgt[:B] = pos[s:e]
-            call("ader_rank_targets", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(tgt), ptr(self._ncol_all(Bp, B, N)),
-                 ptr(tl), ptr(rk), self._stream())
-            out[s:e] = rk[:B]
+        seq, pos, N = self._enter(seq), self._dev_i32(pos), int(max_item)
+        out = torch.empty(seq.shape[0], dtype=torch.int32, device=self.device)
+        for s, e, B, rep in self._chunks(seq):
+            out[s:e] = L.rank_targets(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, pos[s:e])[:B]
         return out.cpu().numpy()
 
     def rank_targets_among(self, seq, pos, max_item, candidates=None, exclude_seen=False):
@@ -229,64 +258,30 @@ class _Infer:
         items[b, j] > 0.  The list's table rows are gathered inside the kernel (ader_rank_targets_cand, k_rank_cand): the work follows
         len(candidates), not max_item.  Exact-f32 chain whatever rank_dtype says (the x3 filter walks contiguous tiles only).  The list
         is copied to the device once, chunks of MAX_ROWS rows, one device -> host copy."""
-        N = int(max_item)
-        _check(1 <= N <= self.item_num, "rank_targets_among: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        N = self._check_kN("rank_targets_among", int(max_item))
         cand = np.arange(1, N + 1, dtype=np.int32) if candidates is None else candidate_ids(candidates, N, self.item_num)
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        pos = self._dev_i32(pos)
-        n, M = seq.shape[0], int(cand.shape[0])
-        cand_d = torch.from_numpy(cand).to(self.device) if M else None
-        out = torch.empty(n, dtype=torch.int32, device=self.device)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            rep = self.forward(seq[s:e], training=False)
-            tl = self.buf("rkc_tl", (Bp,))
-            rk = self.buf("rkc_rank", (Bp,), torch.int32)
-            tgt = self.buf("rkc_tgt", (Bp,), torch.int32)
-            tgt.zero_()
-            tgt[:B] = pos[s:e]
-            call("ader_rank_targets_cand", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(tgt), ptr(self._ncol_all(Bp, B, N)),
-                 ptr(cand_d), M, ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], ptr(tl), ptr(rk), ptr(self.status),
-                 self._stream())
-            out[s:e] = rk[:B]
+        seq, pos = self._enter(seq), self._dev_i32(pos)
+        cand_d = torch.from_numpy(cand).to(self.device) if cand.shape[0] else None
+        out = torch.empty(seq.shape[0], dtype=torch.int32, device=self.device)
+        for s, e, B, rep in self._chunks(seq):
+            out[s:e] = L.rank_targets_cand(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, pos[s:e], cand_d,
+                                           seq[s:e] if exclude_seen else None, self.status)[:B]
         return out.cpu().numpy()
 
     def _rank_targets_x3(self, seq, pos, max_item, cand_cap):
         """rank_targets on the bf16 matrix cores (ader_rank_targets_x3): per 128-row-padded chunk the x3 filter decides every (row, item)
         whose x3 logit is outside the band tl +- delta, the exact-f32 recheck decides the listed rest; a chunk whose list overflowed is
         ranked again by the exact kernel.  One device -> host copy: ranks + per-chunk (count, max err / delta)."""
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        pos = self._dev_i32(pos)
-        n, N = seq.shape[0], int(max_item)
-        st = self._stream()
+        seq, pos = self._enter(seq), self._dev_i32(pos)
+        n, N, st, emb = seq.shape[0], int(max_item), self._stream(), self._pp["emb"]
         chunks = [(s, min(n, s + self.MAX_ROWS)) for s in range(0, n, self.MAX_ROWS)]
-        res = torch.zeros(n + 2 * len(chunks), dtype=torch.int32, device=self.device)
-        emax = self.buf("rkx_emax", (1,))
-        if chunks:
-            call("ader_rank_emax", self._pp["emb"], self.item_num, self.H, N, ptr(emax), st)      # once per call, not per chunk
+        res = torch.zeros(n + 2 * len(chunks), dtype=torch.int32, device=self.device)      # ranks | (count, max err / delta) per chunk
+        emax = L.rank_emax(self.buf, st, emb, self.item_num, self.H, N) if chunks else None      # once per call, not per chunk
         caps = []
-        for c, (s, e) in enumerate(chunks):
-            B = e - s
-            Bp = (B + 127) // 128 * 128
-            cap = int(cand_cap) if cand_cap is not None else RANK_X3_CAND_PER_ROW * Bp
-            caps.append(cap)
-            rep = self.forward(seq[s:e], training=False)
-            rep_hi, rep_lo = self.buf("rkx_hi", (Bp * 168,), torch.bfloat16), self.buf("rkx_lo", (Bp * 168,), torch.bfloat16)
-            tl, delta = self.buf("rkx_tl", (Bp,)), self.buf("rkx_delta", (Bp,))
-            rk = self.buf("rkx_rank", (Bp,), torch.int32)
-            tgt = self.buf("rkx_tgt", (Bp,), torch.int32)
-            cand = self.buf("rkx_cand", (3 * max(cap, 1),), torch.int32)      # (one list: the chunks' launches are ordered on the stream)
-            tgt.zero_()
-            tgt[:B] = pos[s:e]
-            call("ader_rank_targets_x3", ptr(rep), self._pp["emb"], self.item_num, B, Bp, self.H, N, ptr(tgt),
-                 ptr(self._ncol_all(Bp, B, N)), ptr(rep_hi), ptr(rep_lo), ptr(tl), ptr(delta), ptr(emax), ptr(cand), cap,
-                 ptr(res[n + 2 * c:]), ptr(rk), st)
+        for c, (s, e, B, rep) in enumerate(self._chunks(seq)):
+            caps.append(int(cand_cap) if cand_cap is not None else RANK_X3_CAND_PER_ROW * L.pad_rows(B, 128))
+            # (one candidate list for all chunks: their launches are ordered on the stream)
+            rk, _ = L.rank_targets_x3(self.buf, st, rep, emb, self.item_num, self.H, N, pos[s:e], emax, caps[c], res[n + 2 * c:])
             res[s:e] = rk[:B]
         host = res.cpu().numpy()
         ranks, diag = host[:n].copy(), host[n:].reshape(-1, 2)
@@ -319,35 +314,17 @@ class _Infer:
         k a row's kept set may hold on the "x3" path before the row is handed to the f32 kernels (None: TOPK_X3_BAND).
         recommend_among: the same over a candidate item list."""
         dtype = _check_topk_dtype(self.topk_dtype if dtype is None else dtype)
-        kmax = call("ader_topk_kmax")
-        k = int(k)
-        N = self.item_num if max_item is None else int(max_item)
+        k, N = self._check_kN("recommend", max_item, k, call("ader_topk_kmax"))
         band = TOPK_X3_BAND if band is None else int(band)
-        _check(1 <= k <= kmax, "recommend: k must be in 1..%d (got %d)" % (kmax, k))
-        _check(1 <= N <= self.item_num, "recommend: max_item must be in 1..%d (got %d)" % (self.item_num, N))
         _check(0 <= band <= TOPK_X3_BAND, "recommend: band must be in 0..%d (got %d)" % (TOPK_X3_BAND, band))
         if dtype == "x3" and rank_x3_supports(self.H) and k <= call("ader_topk_x3_kmax") and self.item_num * self.H * 4 < 2 ** 31:
             return self._recommend_x3(seq, k, N, exclude_seen, band)
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        n = seq.shape[0]
-        res = torch.empty((2, n, k), dtype=torch.int32, device=self.device)      # items | score bits: one copy back
-        scores = res[1].view(torch.float32)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            rep = self.forward(seq[s:e], training=False)
-            self._topk_f32(rep, seq[s:e] if exclude_seen else None, N, k, res[0, s:e], scores[s:e])
-        host = res.cpu().numpy()
-        return host[0], host[1].view(np.float32)
-
-    def _topk_f32(self, rep, seen, N, k, items, scores):
-        """ader_topk_items of one chunk: rep [B,H], seen [B,T] or None -> items / scores [B,k] (device, written in place)."""
-        B = rep.shape[0]
-        Bp = (B + 63) // 64 * 64
-        part = self.buf("tk_part", (call("ader_topk_ranges", N, Bp) * Bp * k,), torch.int64)
-        call("ader_topk_items", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
-             ptr(seen), seen.shape[1] if seen is not None else 0, k, ptr(part), ptr(items), ptr(scores), self._stream())
+        seq = self._enter(seq)
+        res = _Packed(self.device, seq.shape[0], k)
+        for s, e, _, rep in self._chunks(seq):
+            L.topk_items(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, seq[s:e] if exclude_seen else None, k,
+                         *res.rows(s, e))
+        return res.cpu()
 
     def row_stats(self, seq, max_item=None):
         """The model's distribution per row, without the [n, max_item] matrix: (lse, entropy), float32 [n] numpy.  With s = the float32
@@ -356,21 +333,11 @@ class _Infer:
         (max, sum, weighted sum) states merged in a fixed order, no float atomics, so two calls give the same bits, and they are the
         bits recommend_stats returns for the same rows in the same chunking.  A batch of another size partitions the catalog
         differently (ader_topk_ranges) and may differ in the last bits.  Chunks of MAX_ROWS rows, one device -> host copy."""
-        N = self.item_num if max_item is None else int(max_item)
-        _check(1 <= N <= self.item_num, "row_stats: max_item must be in 1..%d (got %d)" % (self.item_num, N))
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        n = seq.shape[0]
-        res = torch.empty((2, n), dtype=torch.float32, device=self.device)       # lse | entropy: one copy back
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            rep = self.forward(seq[s:e], training=False)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            spart = self.buf("ts_spart", (call("ader_row_stats_floats", N, Bp),))
-            call("ader_row_stats", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)), ptr(spart),
-                 ptr(res[0, s:e]), ptr(res[1, s:e]), self._stream())
+        N = self._check_kN("row_stats", max_item)
+        seq = self._enter(seq)
+        res = torch.empty((2, seq.shape[0]), dtype=torch.float32, device=self.device)       # lse | entropy: one copy back
+        for s, e, _, rep in self._chunks(seq):
+            L.row_stats(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, res[0, s:e], res[1, s:e])
         host = res.cpu().numpy()
         return host[0], host[1]
 
@@ -382,32 +349,17 @@ class _Infer:
         answer: an excluded item keeps its mass, so probs(scores, lse) of an answer need not sum to 1, and a probability means the
         same thing in every call.  k in 1..ader_topk_kmax() (= 64); exact-f32 chain only, whatever topk_dtype says.  Chunks of
         MAX_ROWS rows, one device -> host copy.  (A method of its own: recommend's parameter list is pinned by the tests.)"""
-        kmax = call("ader_topk_kmax")
-        k = int(k)
-        N = self.item_num if max_item is None else int(max_item)
-        _check(1 <= k <= kmax, "recommend_stats: k must be in 1..%d (got %d)" % (kmax, k))
-        _check(1 <= N <= self.item_num, "recommend_stats: max_item must be in 1..%d (got %d)" % (self.item_num, N))
-        self._refresh_stream()
-        self.sync_table()
+        k, N = self._check_kN("recommend_stats", max_item, k, call("ader_topk_kmax"))
+        seq = self._enter(seq)
         self.last_topk_stats = None
-        seq = self._seq_in(seq)
         n = seq.shape[0]
-        res = torch.empty(2 * n * k + 2 * n, dtype=torch.int32, device=self.device)      # items | score bits | lse bits | entropy bits
-        items, scores = res[:n * k].view(n, k), res[n * k:2 * n * k].view(n, k).view(torch.float32)
-        stats = res[2 * n * k:].view(2, n).view(torch.float32)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            rep = self.forward(seq[s:e], training=False)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            part = self.buf("tk_part", (call("ader_topk_ranges", N, Bp) * Bp * k,), torch.int64)
-            spart = self.buf("ts_spart", (call("ader_row_stats_floats", N, Bp),))
-            call("ader_topk_items_stats", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
-                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, ptr(part), ptr(spart), ptr(items[s:e]), ptr(scores[s:e]),
-                 ptr(stats[0, s:e]), ptr(stats[1, s:e]), self._stream())
-        host = res.cpu().numpy()
-        st = host[2 * n * k:].reshape(2, n).view(np.float32)
-        return host[:n * k].reshape(n, k), host[n * k:2 * n * k].reshape(n, k).view(np.float32), st[0], st[1]
+        res = _Packed(self.device, n, k, (n, n))                                         # ... | lse bits | entropy bits
+        lse, entropy = (x.view(torch.float32) for x in res.extra)
+        for s, e, _, rep in self._chunks(seq):
+            L.topk_items_stats(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, seq[s:e] if exclude_seen else None, k,
+                               *res.rows(s, e), lse[s:e], entropy[s:e])
+        items, scores, lse, entropy = res.cpu()
+        return items, scores, lse.view(np.float32), entropy.view(np.float32)
 
     def recommend_among(self, seq, k, candidates, max_item=None, exclude_seen=False, dtype=None):
         """recommend restricted to a candidate item list: candidates is a 1-D integer array / tensor of item ids, shared by all rows
@@ -419,35 +371,20 @@ class _Infer:
         walks contiguous tiles only), next to recommend's own cases that fall to f32; last_topk_stats is left None.  (A method of its
         own: recommend's parameter list is pinned by tests/test_topk_x3_host.py; Ader.recommend takes candidates=.)"""
         _check_topk_dtype(self.topk_dtype if dtype is None else dtype)
-        kmax = call("ader_topk_kmax")
-        k = int(k)
-        N = self.item_num if max_item is None else int(max_item)
-        _check(1 <= k <= kmax, "recommend_among: k must be in 1..%d (got %d)" % (kmax, k))
-        _check(1 <= N <= self.item_num, "recommend_among: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        k, N = self._check_kN("recommend_among", max_item, k, call("ader_topk_kmax"))
         return self._recommend_cand(seq, k, N, exclude_seen, candidate_ids(candidates, N, self.item_num))
 
     def _recommend_cand(self, seq, k, N, exclude_seen, cand):
         """recommend over cand, candidate_ids' list: copied to the device once, ader_topk_items_cand per chunk of MAX_ROWS rows, one
         device -> host copy."""
-        self._refresh_stream()
-        self.sync_table()
+        seq = self._enter(seq)
         self.last_topk_stats = None
-        seq = self._seq_in(seq)
-        n, M = seq.shape[0], int(cand.shape[0])
-        cand_d = torch.from_numpy(cand).to(self.device) if M else None
-        res = torch.empty((2, n, k), dtype=torch.int32, device=self.device)      # items | score bits: one copy back
-        scores = res[1].view(torch.float32)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            rep = self.forward(seq[s:e], training=False)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            part = self.buf("tkc_part", (call("ader_topk_ranges", M, Bp) * Bp * k,), torch.int64)
-            call("ader_topk_items_cand", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)), ptr(cand_d), M,
-                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, ptr(part), ptr(res[0, s:e]), ptr(scores[s:e]),
-                 ptr(self.status), self._stream())
-        host = res.cpu().numpy()
-        return host[0], host[1].view(np.float32)
+        cand_d = torch.from_numpy(cand).to(self.device) if cand.shape[0] else None
+        res = _Packed(self.device, seq.shape[0], k)
+        for s, e, _, rep in self._chunks(seq):
+            L.topk_items_cand(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, cand_d, seq[s:e] if exclude_seen else None, k,
+                              *res.rows(s, e), self.status)
+        return res.cpu()
 
     def score_items(self, seq, items, max_item=None):
         """The logits of the listed items, row by row: items is an integer [n, C] array or tensor of item ids (any order, duplicates
@@ -455,27 +392,21 @@ class _Infer:
         or > N = max_item (None: the whole catalog).  What a re-ranking stage asks of the model: the table rows are gathered inside
         the kernel (ader_score_items, k_rowlist), so the work follows n * C and no [n, N] logits are written.  Chunks of MAX_ROWS
         rows, one device -> host copy."""
-        N = self.item_num if max_item is None else int(max_item)
-        _check(1 <= N <= self.item_num, "score_items: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        N = self._check_kN("score_items", max_item)
         if not isinstance(items, torch.Tensor):
             items = np.asarray(items)
         _check(items.ndim == 2, "score_items: items must be [n, C] (got %d dimensions)" % items.ndim)
         dt = items.dtype
         _check(dt in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) if isinstance(items, torch.Tensor)
                else np.issubdtype(dt, np.integer), "score_items: items must hold integers (got dtype %s)" % (dt,))
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
+        seq = self._enter(seq)
         n, C = seq.shape[0], int(items.shape[1])
         _check(items.shape[0] == n, "score_items: items must have one row per session (got %d for %d)" % (items.shape[0], n))
         out = torch.empty((n, C), dtype=torch.float32, device=self.device)
         if C:
             ids = self._dev_i32(items)
-            for s in range(0, n, self.MAX_ROWS):
-                e = min(n, s + self.MAX_ROWS)
-                rep = self.forward(seq[s:e], training=False)
-                call("ader_score_items", ptr(rep), self._pp["emb"], e - s, self.H, N, None, ptr(ids[s:e]), C, C, ptr(out[s:e]), C,
-                     self._stream())
+            for s, e, _, rep in self._chunks(seq):
+                L.score_items(self._stream(), rep, self._pp["emb"], self.H, N, ids[s:e], out[s:e])
         return out.cpu().numpy()
 
     def recommend_per_row(self, seq, k, lists, max_item=None, exclude_seen=False):
@@ -486,33 +417,18 @@ class _Infer:
         list in every row recommend_among's.  The lists' table rows are gathered inside the kernel (ader_topk_items_rows, k_rowlist):
         the work follows the lists' length, not max_item.  Exact-f32 chain; last_topk_stats is left None.  The lists are copied to
         the device once, chunks of MAX_ROWS rows, one device -> host copy."""
-        kmax = call("ader_topk_kmax")
-        k = int(k)
-        N = self.item_num if max_item is None else int(max_item)
-        _check(1 <= k <= kmax, "recommend_per_row: k must be in 1..%d (got %d)" % (kmax, k))
-        _check(1 <= N <= self.item_num, "recommend_per_row: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        k, N = self._check_kN("recommend_per_row", max_item, k, call("ader_topk_kmax"))
         ids = row_candidate_ids(lists, N, self.item_num)
-        self._refresh_stream()
-        self.sync_table()
+        seq = self._enter(seq)
         self.last_topk_stats = None
-        seq = self._seq_in(seq)
-        n, C = seq.shape[0], int(ids.shape[1])
+        n = seq.shape[0]
         _check(ids.shape[0] == n, "recommend_per_row: lists must have one row per session (got %d for %d)" % (ids.shape[0], n))
-        ids_d = self._dev_i32(ids) if C else None
-        res = torch.empty((2, n, k), dtype=torch.int32, device=self.device)      # items | score bits: one copy back
-        scores = res[1].view(torch.float32)
-        ranges = call("ader_topk_rows_ranges", C, k)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            rep = self.forward(seq[s:e], training=False)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            part = self.buf("tkr_part", (ranges * Bp * k,), torch.int64)
-            call("ader_topk_items_rows", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
-                 ptr(ids_d[s:e]) if C else None, C, C, ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, ptr(part),
-                 ptr(res[0, s:e]), ptr(scores[s:e]), ptr(self.status), self._stream())
-        host = res.cpu().numpy()
-        return host[0], host[1].view(np.float32)
+        ids_d = self._dev_i32(ids) if ids.shape[1] else None
+        res = _Packed(self.device, n, k)
+        for s, e, _, rep in self._chunks(seq):
+            L.topk_items_rows(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, ids_d[s:e] if ids.shape[1] else None,
+                              seq[s:e] if exclude_seen else None, k, *res.rows(s, e), self.status)
+        return res.cpu()
 
     def rank_targets_per_row(self, seq, pos, max_item, lists, exclude_seen=False):
         """rank_targets_among with a candidate list of its own for every row (lists as recommend_per_row's): the 0-based rank of pos[b]
@@ -522,31 +438,16 @@ class _Infer:
         lists, e) == j wherever items[b, j] > 0.  With the target plus sampled unseen items as a row's list this is the
         sampled-negative protocol of the SASRec evaluation (data.sample_negatives, Evaluator(negatives=...)).  ader_rank_targets_rows,
         k_rowlist: the work follows the lists' length.  Chunks of MAX_ROWS rows, one device -> host copy."""
-        N = int(max_item)
-        _check(1 <= N <= self.item_num, "rank_targets_per_row: max_item must be in 1..%d (got %d)" % (self.item_num, N))
+        N = self._check_kN("rank_targets_per_row", int(max_item))
         ids = row_candidate_ids(lists, N, self.item_num)
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        pos = self._dev_i32(pos)
-        n, C = seq.shape[0], int(ids.shape[1])
+        seq, pos = self._enter(seq), self._dev_i32(pos)
+        n = seq.shape[0]
         _check(ids.shape[0] == n, "rank_targets_per_row: lists must have one row per session (got %d for %d)" % (ids.shape[0], n))
-        ids_d = self._dev_i32(ids) if C else None
+        ids_d = self._dev_i32(ids) if ids.shape[1] else None
         out = torch.empty(n, dtype=torch.int32, device=self.device)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            rep = self.forward(seq[s:e], training=False)
-            tl = self.buf("rkr_tl", (Bp,))
-            rk = self.buf("rkr_rank", (Bp,), torch.int32)
-            tgt = self.buf("rkr_tgt", (Bp,), torch.int32)
-            tgt.zero_()
-            tgt[:B] = pos[s:e]
-            call("ader_rank_targets_rows", ptr(rep), self._pp["emb"], B, Bp, self.H, N, ptr(tgt), ptr(self._ncol_all(Bp, B, N)),
-                 ptr(ids_d[s:e]) if C else None, C, C, ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], ptr(tl), ptr(rk),
-                 ptr(self.status), self._stream())
-            out[s:e] = rk[:B]
+        for s, e, B, rep in self._chunks(seq):
+            out[s:e] = L.rank_targets_rows(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, pos[s:e],
+                                           ids_d[s:e] if ids.shape[1] else None, seq[s:e] if exclude_seen else None, self.status)[:B]
         return out.cpu().numpy()
 
     def _recommend_x3(self, seq, k, N, exclude_seen, band):
@@ -554,40 +455,27 @@ class _Infer:
         provably below the row's k-th best, k_topk3_finish rechecks the kept pairs on the exact chain and selects.  One device -> host
         copy of items, scores, status and diag; a chunk with a row whose kept set outgrew k + band keys goes through ader_topk_items on
         the representations kept from this call's forward, and those rows are replaced."""
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        n, st, dev = seq.shape[0], self._stream(), self.device
+        seq = self._enter(seq)
+        n, st, dev, emb = seq.shape[0], self._stream(), self.device, self._pp["emb"]
         chunks = [(s, min(n, s + self.MAX_ROWS)) for s in range(0, n, self.MAX_ROWS)]
-        res = torch.zeros(2 * n * k + n + 3 * len(chunks), dtype=torch.int32, device=dev)      # items | score bits | status | diag
-        items, scores = res[:n * k].view(n, k), res[n * k:2 * n * k].view(n, k).view(torch.float32)
-        status, diag = res[2 * n * k:2 * n * k + n], res[2 * n * k + n:]
+        res = _Packed(dev, n, k, (n, 3 * len(chunks)), zero=True)                        # ... | status | diag
+        status, diag = res.extra
         rep_all = torch.empty((n, self.H), dtype=torch.float32, device=dev)
-        emax = self.buf("tkx_emax", (1,))
-        if chunks:
-            call("ader_rank_emax", self._pp["emb"], self.item_num, self.H, N, ptr(emax), st)       # once per call, not per chunk
-        for c, (s, e) in enumerate(chunks):
-            B = e - s
-            Bp = (B + 127) // 128 * 128
-            rep_all[s:e] = self.forward(seq[s:e], training=False)
-            rep_hi, rep_lo = self.buf("tkx_hi", (Bp * 168,), torch.bfloat16), self.buf("tkx_lo", (Bp * 168,), torch.bfloat16)
-            delta, stat = self.buf("tkx_delta", (Bp,)), self.buf("tkx_status", (Bp,), torch.int32)
-            part3 = self.buf("tkx_part", (call("ader_topk_x3_ranges", N, Bp) * Bp * (k + band),), torch.int64)
-            call("ader_topk_items_x3", ptr(rep_all[s:e]), self._pp["emb"], self.item_num, B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
-                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, band, ptr(rep_hi), ptr(rep_lo), ptr(delta), ptr(emax),
-                 ptr(part3), ptr(stat), ptr(diag[3 * c:]), ptr(items[s:e]), ptr(scores[s:e]), st)
+        emax = L.rank_emax(self.buf, st, emb, self.item_num, self.H, N) if chunks else None       # once per call, not per chunk
+        for c, (s, e, B, rep) in enumerate(self._chunks(seq, rep_all)):
+            stat, _ = L.topk_items_x3(self.buf, st, rep, emb, self.item_num, self.H, N, seq[s:e] if exclude_seen else None, k, band,
+                                      emax, *res.rows(s, e), diag[3 * c:])
             status[s:e] = stat[:B]
-        host = res.cpu().numpy()
-        h_items, h_scores = host[:n * k].reshape(n, k).copy(), host[n * k:2 * n * k].reshape(n, k).view(np.float32).copy()
-        h_status, h_diag = host[2 * n * k:2 * n * k + n], host[2 * n * k + n:].reshape(-1, 3)
+        h_items, h_scores, h_status, h_diag = res.cpu()
+        h_items, h_scores, h_diag = h_items.copy(), h_scores.copy(), h_diag.reshape(-1, 3)
         over = [c for c, (s, e) in enumerate(chunks) if h_status[s:e].any()]
         for c in over:
             s, e = chunks[c]
-            fb = torch.empty((2, e - s, k), dtype=torch.int32, device=dev)
-            self._topk_f32(rep_all[s:e], seq[s:e] if exclude_seen else None, N, k, fb[0], fb[1].view(torch.float32))
-            fb = fb.cpu().numpy()
+            fb = _Packed(dev, e - s, k)
+            L.topk_items(self.buf, st, rep_all[s:e], emb, self.H, N, seq[s:e] if exclude_seen else None, k, *fb.rows(0, e - s))
+            fb_items, fb_scores = fb.cpu()
             rows = np.nonzero(h_status[s:e])[0]
-            h_items[s + rows], h_scores[s + rows] = fb[0][rows], fb[1].view(np.float32)[rows]
+            h_items[s + rows], h_scores[s + rows] = fb_items[rows], fb_scores[rows]
         self.last_topk_stats = {
             "kept_pairs": int(h_diag[:, 0].sum()), "rows": int(n), "overflowed_rows": int(np.count_nonzero(h_status)),
             "fallback_chunks": len(over),
@@ -605,36 +493,23 @@ class _Infer:
         logits of those rows in groups under 256 MB, the seen columns at -inf, a stable descending sort, the same padding.
         last_topk_stats: slabs (per chunk), rows, max_list (the largest list a select after slab 0 met), overflowed_rows,
         fallback_rows."""
-        kmax, capmax = call("ader_topk_wide_kmax"), call("ader_topk_wide_cap")
-        k = int(k)
-        N = self.item_num if max_item is None else int(max_item)
+        capmax = call("ader_topk_wide_cap")
+        k, N = self._check_kN("recommend_wide", max_item, k, call("ader_topk_wide_kmax"))
         cap = capmax if cap is None else int(cap)
-        _check(1 <= k <= kmax, "recommend_wide: k must be in 1..%d (got %d)" % (kmax, k))
-        _check(1 <= N <= self.item_num, "recommend_wide: max_item must be in 1..%d (got %d)" % (self.item_num, N))
         _check(cap % 64 == 0 and k + 64 <= cap <= capmax,
                "recommend_wide: cap must be a multiple of 64 in [k + 64 = %d, %d] (got %d)" % (k + 64, capmax, cap))
-        self._refresh_stream()
-        self.sync_table()
-        seq = self._seq_in(seq)
-        n, st, dev = seq.shape[0], self._stream(), self.device
-        chunks = [(s, min(n, s + self.MAX_ROWS)) for s in range(0, n, self.MAX_ROWS)]
-        res = torch.zeros(2 * n * k + n + 2 * len(chunks), dtype=torch.int32, device=dev)      # items | score bits | status | diag
-        items, scores = res[:n * k].view(n, k), res[n * k:2 * n * k].view(n, k).view(torch.float32)
-        status, diag = res[2 * n * k:2 * n * k + n], res[2 * n * k + n:]
+        seq = self._enter(seq)
+        n, dev = seq.shape[0], self.device
+        n_chunks = (n + self.MAX_ROWS - 1) // self.MAX_ROWS
+        res = _Packed(dev, n, k, (n, 2 * n_chunks), zero=True)                           # ... | status | diag
+        status, diag = res.extra
         rep_all = torch.empty((n, self.H), dtype=torch.float32, device=dev)
-        for c, (s, e) in enumerate(chunks):
-            B = e - s
-            Bp = (B + 63) // 64 * 64
-            rep_all[s:e] = self.forward(seq[s:e], training=False)
-            lst, thr = self.buf("tkw_list", (Bp * cap,), torch.int64), self.buf("tkw_thr", (Bp,), torch.int64)
-            cnt, stat = self.buf("tkw_cnt", (Bp,), torch.int32), self.buf("tkw_status", (Bp,), torch.int32)
-            call("ader_topk_items_wide", ptr(rep_all[s:e]), self._pp["emb"], B, Bp, self.H, N, ptr(self._ncol_all(Bp, B, N)),
-                 ptr(seq[s:e]) if exclude_seen else None, seq.shape[1], k, cap, ptr(lst), ptr(cnt), ptr(thr), ptr(stat),
-                 ptr(diag[2 * c:]), ptr(items[s:e]), ptr(scores[s:e]), st)
+        for c, (s, e, B, rep) in enumerate(self._chunks(seq, rep_all)):
+            stat, _ = L.topk_items_wide(self.buf, self._stream(), rep, self._pp["emb"], self.H, N, seq[s:e] if exclude_seen else None, k,
+                                        cap, *res.rows(s, e), diag[2 * c:])
             status[s:e] = stat[:B]
-        host = res.cpu().numpy()
-        h_items, h_scores = host[:n * k].reshape(n, k).copy(), host[n * k:2 * n * k].reshape(n, k).view(np.float32).copy()
-        h_status, h_diag = host[2 * n * k:2 * n * k + n], host[2 * n * k + n:].reshape(-1, 2)
+        h_items, h_scores, h_status, h_diag = res.cpu()
+        h_items, h_scores, h_diag = h_items.copy(), h_scores.copy(), h_diag.reshape(-1, 2)
         over = np.nonzero(h_status)[0]
         group = max(1, 64_000_000 // ((N + 3) // 4 * 4))          # rows whose dense logits stay under 256 MB
         m = min(k, N)
@@ -654,25 +529,19 @@ class _Infer:
             h_items[over[g:g + group], :m], h_scores[over[g:g + group], :m] = i, v
         self.last_topk_stats = {
             "slabs": int(call("ader_topk_wide_slabs", N, k, cap, None, 0)), "rows": int(n),
-            "max_list": int(h_diag[:, 0].max()) if len(chunks) else 0, "overflowed_rows": int(len(over)), "fallback_rows": int(len(over))}
+            "max_list": int(h_diag[:, 0].max()) if n_chunks else 0, "overflowed_rows": int(len(over)), "fallback_rows": int(len(over))}
         return h_items, h_scores
 
     def row_losses(self, seq, pos, max_item):
         """Per-row cross entropy -log softmax(logits)[label] in eval mode (the quantity the reference's `loss` exemplar selector
         means to rank by, util.py:463-495; its graph fetches the batch MEAN, see ExemplarGenerator.loss_selection) -> float32 [n]
         device tensor.  Exact-f32 logit kernels, chunks of MAX_ROWS rows."""
-        self._refresh_stream()
-        self.sync_table()
-        seq, pos = self._seq_in(seq), self._dev_i32(pos)
-        n, N = seq.shape[0], int(max_item)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        seq, pos, N = self._enter(seq), self._dev_i32(pos), int(max_item)
+        out = torch.empty(seq.shape[0], dtype=torch.float32, device=self.device)
         st = self._stream()
         parts = call("ader_logits_parts", N)
         scr = torch.empty(1, dtype=torch.float32, device=self.device)
-        for s in range(0, n, self.MAX_ROWS):
-            e = min(n, s + self.MAX_ROWS)
-            B = e - s
-            rep = self.forward(seq[s:e], training=False)
+        for s, e, B, rep in self._chunks(seq):
             Bp, ri = self._rowinfo(B, pos[s:e].contiguous(), B, None, None, N, 0, 1.0, 0.0, None, tag="rl_")
             part = self.buf("lg_part", (parts * Bp * 3,))
             lse, rowloss = self.buf("rl_lse", (Bp,)), self.buf("rl_rowloss", (Bp,))

@@ -55,6 +55,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
+from .engine import infer_launch as L
 from .engine.common import HP, LDR, X3_IMG_ROW_B, TableJob, flash_sizes, issue_table_job
 
 _lib.load()
@@ -155,19 +156,27 @@ def adam_step(p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor
     call("ader_adam_step", ptr(p), ptr(m), ptr(v), ptr(g), p.numel(), lr_t, beta1, beta2, eps, None, 0, 1, _st())
 
 
-@torch.library.custom_op("ader::rank_of_target", mutates_args=())
-def rank_of_target(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, N: int) -> torch.Tensor:
+def _seen_chk(op, seen, B):
+    if seen is not None:
+        _chk(seen, "seen", torch.int32, 2)
+        if seen.shape[0] != B or seen.shape[1] < 1:
+            raise RuntimeError("ader::%s: seen must be [B, S] with S >= 1" % op)
+
+
+def _rank_prologue(op, rep, emb, target, seen, N, pad=64):
+    """What the rank_of_target* operators check alike -> (B, Bp, H), Bp = B padded to `pad` rows."""
     _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(target, "target", torch.int32, 1)
     B, H = rep.shape
     if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or target.shape[0] != B or B > 1024:
-        raise RuntimeError("ader::rank_of_target: bad shapes")
-    Bp = (B + 63) // 64 * 64
-    dev = rep.device
-    tgt, ncol = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, dtype=torch.int32, device=dev)
-    tgt[:B], ncol[:B] = target, N
-    tl, rk = torch.empty(Bp, device=dev), torch.empty(Bp, dtype=torch.int32, device=dev)
-    call("ader_rank_targets", ptr(rep), ptr(emb), B, Bp, H, N, ptr(tgt), ptr(ncol), ptr(tl), ptr(rk), _st())
-    return rk[:B].clone()
+        raise RuntimeError("ader::%s: bad shapes" % op)
+    _seen_chk(op, seen, B)
+    return B, L.pad_rows(B, pad), H
+
+
+@torch.library.custom_op("ader::rank_of_target", mutates_args=())
+def rank_of_target(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, N: int) -> torch.Tensor:
+    B, _, H = _rank_prologue("rank_of_target", rep, emb, target, None, N)
+    return L.rank_targets(L.fresh(rep.device), _st(), rep, ptr(emb), H, N, target)[:B].clone()
 
 
 @rank_of_target.register_fake
@@ -180,24 +189,12 @@ def rank_of_target_x3(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tensor
     """rank_of_target's contract and result (ties included) through ader_rank_targets_x3.  Reads the candidate count back (one
     synchronisation): if the list overflowed, the rows are ranked by the exact kernel instead."""
     from .engine.infer import RANK_X3_CAND_PER_ROW, rank_x3_supports
-    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(target, "target", torch.int32, 1)
-    B, H = rep.shape
-    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or target.shape[0] != B or B > 1024:
-        raise RuntimeError("ader::rank_of_target_x3: bad shapes")
+    B, Bp, H = _rank_prologue("rank_of_target_x3", rep, emb, target, None, N, pad=128)
     if not rank_x3_supports(H):
         raise RuntimeError("ader::rank_of_target_x3: H must be even, 8 <= H <= 160, H mod 8 in {0, 4, 6} (got %d)" % H)
-    Bp = (B + 127) // 128 * 128
-    dev = rep.device
-    tgt, ncol = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, dtype=torch.int32, device=dev)
-    tgt[:B], ncol[:B] = target, N
-    tl, delta, emax = torch.empty(Bp, device=dev), torch.empty(Bp, device=dev), torch.empty(1, device=dev)
-    rep_hi, rep_lo = (torch.empty(Bp * LDR, dtype=torch.bfloat16, device=dev) for _ in range(2))
-    cap = RANK_X3_CAND_PER_ROW * Bp
-    cand, diag = torch.empty(3 * cap, dtype=torch.int32, device=dev), torch.empty(2, dtype=torch.int32, device=dev)
-    rk = torch.empty(Bp, dtype=torch.int32, device=dev)
-    call("ader_rank_emax", ptr(emb), emb.shape[0] - 1, H, N, ptr(emax), _st())
-    call("ader_rank_targets_x3", ptr(rep), ptr(emb), emb.shape[0] - 1, B, Bp, H, N, ptr(tgt), ptr(ncol), ptr(rep_hi), ptr(rep_lo),
-         ptr(tl), ptr(delta), ptr(emax), ptr(cand), cap, ptr(diag), ptr(rk), _st())
+    ws, st, item_num, cap = L.fresh(rep.device), _st(), emb.shape[0] - 1, RANK_X3_CAND_PER_ROW * Bp
+    emax = L.rank_emax(ws, st, ptr(emb), item_num, H, N)
+    rk, diag = L.rank_targets_x3(ws, st, rep, ptr(emb), item_num, H, N, target, emax, cap)
     if int(diag[0].item()) > cap:
         return rank_of_target(rep, emb, target, N)
     return rk[:B].clone()
@@ -208,25 +205,19 @@ def _(rep, emb, target, N):
     return target.new_empty(rep.shape[0])
 
 
-def _topk_prologue(op, rep, emb, seen, N, k, kmax, pad=64):
-    """What the topk_items* operators check and allocate alike -> (B, Bp, H, seen_ld, ncol, items, scores): Bp = B padded to `pad` rows,
-    ncol int32 [Bp] = N for real rows and 0 for padding rows, items int32 / scores float32 [B,k] uninitialised."""
+def _topk_prologue(op, rep, emb, seen, N, k, kmax):
+    """What the topk_items* operators check and allocate alike -> (B, H, ws, items, scores): ws the allocator of the launch's workspace,
+    items int32 / scores float32 [B,k] uninitialised."""
     _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2)
     B, H = rep.shape
     if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or B > 1024:
         raise RuntimeError("ader::%s: bad shapes" % op)
     if not (1 <= k <= kmax):
         raise RuntimeError("ader::%s: k must be in 1..%d (got %d)" % (op, kmax, k))
-    if seen is not None:
-        _chk(seen, "seen", torch.int32, 2)
-        if seen.shape[0] != B or seen.shape[1] < 1:
-            raise RuntimeError("ader::%s: seen must be [B, S] with S >= 1" % op)
-    Bp = (B + pad - 1) // pad * pad
+    _seen_chk(op, seen, B)
     dev = rep.device
-    ncol = torch.zeros(Bp, dtype=torch.int32, device=dev)
-    ncol[:B] = N
     items, scores = torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev)
-    return B, Bp, H, seen.shape[1] if seen is not None else 0, ncol, items, scores
+    return B, H, L.fresh(dev), items, scores
 
 
 def _topk_fake(rep, *rest):
@@ -239,9 +230,8 @@ def topk_items(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Tensor
     """rep [B,H], emb [V,H] (row 0 = padding item), seen int32 [B,S] ids to leave out (0 = none, ids above N ignored) or None ->
     (items int32 [B,k], scores float32 [B,k]): the first k of items 1..N by (logit descending, id ascending), the logits of
     ader_logits_store bit for bit; fewer than k candidates: item 0, score -inf."""
-    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items", rep, emb, seen, N, k, call("ader_topk_kmax"))
-    part = torch.empty(call("ader_topk_ranges", N, Bp) * Bp * k, dtype=torch.int64, device=rep.device)
-    call("ader_topk_items", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen_ld, k, ptr(part), ptr(items), ptr(scores), _st())
+    B, H, ws, items, scores = _topk_prologue("topk_items", rep, emb, seen, N, k, call("ader_topk_kmax"))
+    L.topk_items(ws, _st(), rep, ptr(emb), H, N, seen, k, items, scores)
     return items, scores
 
 
@@ -256,12 +246,9 @@ def topk_items_cand(rep: torch.Tensor, emb: torch.Tensor, cand: torch.Tensor, se
     list's table rows are gathered in the kernel: work follows M, not N.  The op does not sort for the caller: a list that is not
     strictly ascending, or holds an id < 1, raises (one synchronisation to read the status)."""
     _chk(cand, "cand", torch.int32, 1)
-    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_cand", rep, emb, seen, N, k, call("ader_topk_kmax"))
-    M = cand.shape[0]
-    part = torch.empty(call("ader_topk_ranges", M, Bp) * Bp * k, dtype=torch.int64, device=rep.device)
+    B, H, ws, items, scores = _topk_prologue("topk_items_cand", rep, emb, seen, N, k, call("ader_topk_kmax"))
     status = torch.zeros(1, dtype=torch.int32, device=rep.device)
-    call("ader_topk_items_cand", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(cand) if M else None, M, ptr(seen), seen_ld, k,
-         ptr(part), ptr(items), ptr(scores), ptr(status), _st())
+    L.topk_items_cand(ws, _st(), rep, ptr(emb), H, N, cand, seen, k, items, scores, status)
     if int(status.item()):
         raise RuntimeError("ader::topk_items_cand: cand must be strictly ascending item ids >= 1")
     return items, scores
@@ -277,24 +264,10 @@ def rank_of_target_cand(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tens
     in [1, N], other than the row's target and its seen ids, that precede the target by (logit descending, id ascending) -- so the
     rank of topk_items_cand's items[b, j] > 0 over the same arguments is j.  The target (in [1, N]) need not be in cand.  A list that
     is not strictly ascending, or holds an id < 1, raises (one synchronisation to read the status)."""
-    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(target, "target", torch.int32, 1)
     _chk(cand, "cand", torch.int32, 1)
-    B, H = rep.shape
-    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or target.shape[0] != B or B > 1024:
-        raise RuntimeError("ader::rank_of_target_cand: bad shapes")
-    if seen is not None:
-        _chk(seen, "seen", torch.int32, 2)
-        if seen.shape[0] != B or seen.shape[1] < 1:
-            raise RuntimeError("ader::rank_of_target_cand: seen must be [B, S] with S >= 1")
-    Bp = (B + 63) // 64 * 64
-    dev = rep.device
-    tgt, ncol = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, dtype=torch.int32, device=dev)
-    tgt[:B], ncol[:B] = target, N
-    tl, rk = torch.empty(Bp, device=dev), torch.empty(Bp, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    M = cand.shape[0]
-    call("ader_rank_targets_cand", ptr(rep), ptr(emb), B, Bp, H, N, ptr(tgt), ptr(ncol), ptr(cand) if M else None, M, ptr(seen),
-         seen.shape[1] if seen is not None else 0, ptr(tl), ptr(rk), ptr(status), _st())
+    B, _, H = _rank_prologue("rank_of_target_cand", rep, emb, target, seen, N)
+    status = torch.zeros(1, dtype=torch.int32, device=rep.device)
+    rk = L.rank_targets_cand(L.fresh(rep.device), _st(), rep, ptr(emb), H, N, target, cand, seen, status)
     if int(status.item()):
         raise RuntimeError("ader::rank_of_target_cand: cand must be strictly ascending item ids >= 1")
     return rk[:B].clone()
@@ -324,9 +297,8 @@ def score_items(rep: torch.Tensor, emb: torch.Tensor, ids: torch.Tensor, N: int)
     B, H = rep.shape
     if emb.shape[1] != H or H > HP or not (1 <= N <= emb.shape[0] - 1):
         raise RuntimeError("ader::score_items: bad shapes")
-    C = _rows_ids("score_items", ids, B)
-    scores = torch.empty(B, C, device=rep.device)
-    call("ader_score_items", ptr(rep), ptr(emb), B, H, N, None, ptr(ids) if C else None, C, C, ptr(scores), C, _st())
+    scores = torch.empty(B, _rows_ids("score_items", ids, B), device=rep.device)
+    L.score_items(_st(), rep, ptr(emb), H, N, ids, scores)
     return scores
 
 
@@ -341,12 +313,10 @@ def topk_items_rows(rep: torch.Tensor, emb: torch.Tensor, ids: torch.Tensor, see
     """topk_items_cand with a list per row: ids int32 [B,C], every row strictly ascending 1-based ids followed by 0 padding (ids above N
     are ignored; C = 0 returns padding) -> (items int32 [B,k], scores float32 [B,k]) with topk_items' scores, order, ties and padding.
     The op does not sort for the caller: a row that is not in that form raises (one synchronisation to read the status)."""
-    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_rows", rep, emb, seen, N, k, call("ader_topk_kmax"))
-    C = _rows_ids("topk_items_rows", ids, B)
-    part = torch.empty(call("ader_topk_rows_ranges", C, k) * Bp * k, dtype=torch.int64, device=rep.device)
+    B, H, ws, items, scores = _topk_prologue("topk_items_rows", rep, emb, seen, N, k, call("ader_topk_kmax"))
+    _rows_ids("topk_items_rows", ids, B)
     status = torch.zeros(1, dtype=torch.int32, device=rep.device)
-    call("ader_topk_items_rows", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(ids) if C else None, C, C, ptr(seen), seen_ld, k,
-         ptr(part), ptr(items), ptr(scores), ptr(status), _st())
+    L.topk_items_rows(ws, _st(), rep, ptr(emb), H, N, ids, seen, k, items, scores, status)
     if int(status.item()):
         raise RuntimeError(_ROWS_MSG % "topk_items_rows")
     return items, scores
@@ -362,23 +332,10 @@ def rank_of_target_rows(rep: torch.Tensor, emb: torch.Tensor, target: torch.Tens
     in [1, N], other than the row's target and its seen ids, that precede the target by (logit descending, id ascending) -- so the rank
     of topk_items_rows' items[b, j] > 0 over the same arguments is j.  The target (in [1, N]) need not be listed.  A row that is not
     strictly ascending ids >= 1 followed by 0 padding raises (one synchronisation to read the status)."""
-    _chk(rep, "rep", torch.float32, 2), _chk(emb, "emb", torch.float32, 2), _chk(target, "target", torch.int32, 1)
-    B, H = rep.shape
-    if emb.shape[1] != H or not (1 <= N <= emb.shape[0] - 1) or target.shape[0] != B or B > 1024:
-        raise RuntimeError("ader::rank_of_target_rows: bad shapes")
-    C = _rows_ids("rank_of_target_rows", ids, B)
-    if seen is not None:
-        _chk(seen, "seen", torch.int32, 2)
-        if seen.shape[0] != B or seen.shape[1] < 1:
-            raise RuntimeError("ader::rank_of_target_rows: seen must be [B, S] with S >= 1")
-    Bp = (B + 63) // 64 * 64
-    dev = rep.device
-    tgt, ncol = torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros(Bp, dtype=torch.int32, device=dev)
-    tgt[:B], ncol[:B] = target, N
-    tl, rk = torch.empty(Bp, device=dev), torch.empty(Bp, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    call("ader_rank_targets_rows", ptr(rep), ptr(emb), B, Bp, H, N, ptr(tgt), ptr(ncol), ptr(ids) if C else None, C, C, ptr(seen),
-         seen.shape[1] if seen is not None else 0, ptr(tl), ptr(rk), ptr(status), _st())
+    B, _, H = _rank_prologue("rank_of_target_rows", rep, emb, target, seen, N)
+    _rows_ids("rank_of_target_rows", ids, B)
+    status = torch.zeros(1, dtype=torch.int32, device=rep.device)
+    rk = L.rank_targets_rows(L.fresh(rep.device), _st(), rep, ptr(emb), H, N, target, ids, seen, status)
     if int(status.item()):
         raise RuntimeError(_ROWS_MSG % "rank_of_target_rows")
     return rk[:B].clone()
@@ -394,17 +351,12 @@ def topk_items_x3(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.Ten
     """topk_items' contract and result, byte for byte, through ader_topk_items_x3 (k <= ader_topk_x3_kmax(), H as rank_of_target_x3).
     Reads the row status back (one synchronisation): rows whose kept set outgrew k + TOPK_X3_BAND keys take topk_items' answer."""
     from .engine.infer import TOPK_X3_BAND, rank_x3_supports
-    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_x3", rep, emb, seen, N, k, call("ader_topk_x3_kmax"), pad=128)
+    B, H, ws, items, scores = _topk_prologue("topk_items_x3", rep, emb, seen, N, k, call("ader_topk_x3_kmax"))
     if not rank_x3_supports(H):
         raise RuntimeError("ader::topk_items_x3: H must be even, 8 <= H <= 160, H mod 8 in {0, 4, 6} (got %d)" % H)
-    dev = rep.device
-    delta, emax = torch.empty(Bp, device=dev), torch.empty(1, device=dev)
-    rep_hi, rep_lo = (torch.empty(Bp * LDR, dtype=torch.bfloat16, device=dev) for _ in range(2))
-    part3 = torch.empty(call("ader_topk_x3_ranges", N, Bp) * Bp * (k + TOPK_X3_BAND), dtype=torch.int64, device=dev)
-    status, diag = torch.empty(Bp, dtype=torch.int32, device=dev), torch.empty(3, dtype=torch.int32, device=dev)
-    call("ader_rank_emax", ptr(emb), emb.shape[0] - 1, H, N, ptr(emax), _st())
-    call("ader_topk_items_x3", ptr(rep), ptr(emb), emb.shape[0] - 1, B, Bp, H, N, ptr(ncol), ptr(seen), seen_ld, k, TOPK_X3_BAND,
-         ptr(rep_hi), ptr(rep_lo), ptr(delta), ptr(emax), ptr(part3), ptr(status), ptr(diag), ptr(items), ptr(scores), _st())
+    st, item_num = _st(), emb.shape[0] - 1
+    emax = L.rank_emax(ws, st, ptr(emb), item_num, H, N)
+    status, _ = L.topk_items_x3(ws, st, rep, ptr(emb), item_num, H, N, seen, k, TOPK_X3_BAND, emax, items, scores)
     over = status[:B] != 0
     if bool(over.any().item()):
         fi, fs = topk_items(rep, emb, seen, N, k)
@@ -422,16 +374,11 @@ def topk_items_wide(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.T
     list per row in global memory, a multiple of 64 in [k + 64, ader_topk_wide_cap() = 4096] -> (items int32 [B,k], scores float32
     [B,k], overflowed int32 [B]).  Rows with overflowed != 0 lost a key between two selects and are unspecified: the operator has no
     fallback and does not synchronise (Engine.recommend_wide recomputes such rows)."""
-    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_wide", rep, emb, seen, N, k, call("ader_topk_wide_kmax"))
+    B, H, ws, items, scores = _topk_prologue("topk_items_wide", rep, emb, seen, N, k, call("ader_topk_wide_kmax"))
     if cap % 64 != 0 or not (k + 64 <= cap <= call("ader_topk_wide_cap")):
         raise RuntimeError("ader::topk_items_wide: cap must be a multiple of 64 in [k + 64 = %d, %d] (got %d)" %
                            (k + 64, call("ader_topk_wide_cap"), cap))
-    dev = rep.device
-    lst, thr = torch.empty(Bp * cap, dtype=torch.int64, device=dev), torch.empty(Bp, dtype=torch.int64, device=dev)
-    cnt, status = torch.empty(Bp, dtype=torch.int32, device=dev), torch.empty(Bp, dtype=torch.int32, device=dev)
-    diag = torch.empty(2, dtype=torch.int32, device=dev)
-    call("ader_topk_items_wide", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen_ld, k, cap,
-         ptr(lst), ptr(cnt), ptr(thr), ptr(status), ptr(diag), ptr(items), ptr(scores), _st())
+    status, _ = L.topk_items_wide(ws, _st(), rep, ptr(emb), H, N, seen, k, cap, items, scores)
     return items, scores, status[:B].clone()
 
 
@@ -448,13 +395,9 @@ def topk_items_stats(rep: torch.Tensor, emb: torch.Tensor, seen: Optional[torch.
     (ader_topk_items_stats) -> (items int32 [B,k], scores float32 [B,k], lse float32 [B], entropy float32 [B]): lse = log sum exp and
     entropy = -sum p log p (nats) of softmax over the logits of ALL items 1..N -- seen removes items from the answer, not from the
     sums, so exp(scores - lse) need not sum to 1.  lse / entropy are row_stats' bits for the same rep."""
-    B, Bp, H, seen_ld, ncol, items, scores = _topk_prologue("topk_items_stats", rep, emb, seen, N, k, call("ader_topk_kmax"))
-    dev = rep.device
-    part = torch.empty(call("ader_topk_ranges", N, Bp) * Bp * k, dtype=torch.int64, device=dev)
-    spart = torch.empty(call("ader_row_stats_floats", N, Bp), device=dev)
-    lse, entropy = torch.empty(B, device=dev), torch.empty(B, device=dev)
-    call("ader_topk_items_stats", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(seen), seen_ld, k, ptr(part), ptr(spart), ptr(items),
-         ptr(scores), ptr(lse), ptr(entropy), _st())
+    B, H, ws, items, scores = _topk_prologue("topk_items_stats", rep, emb, seen, N, k, call("ader_topk_kmax"))
+    lse, entropy = torch.empty(B, device=rep.device), torch.empty(B, device=rep.device)
+    L.topk_items_stats(ws, _st(), rep, ptr(emb), H, N, seen, k, items, scores, lse, entropy)
     return items, scores, lse, entropy
 
 
@@ -469,11 +412,9 @@ def row_stats(rep: torch.Tensor, emb: torch.Tensor, N: int) -> tuple[torch.Tenso
     """rep [B,H], emb [V,H] (row 0 = padding item) -> (lse float32 [B], entropy float32 [B]) of softmax over the logits of items 1..N
     (the float32 of ader_logits_store), in one catalog walk and without the [B,N] matrix (ader_row_stats).  The same rep, emb and N
     give the same bits on every call; another B may differ in the last bits (the catalog is partitioned by the padded batch)."""
-    B, Bp, H, _, ncol, _, _ = _topk_prologue("row_stats", rep, emb, None, N, 1, 1)
-    dev = rep.device
-    spart = torch.empty(call("ader_row_stats_floats", N, Bp), device=dev)
-    lse, entropy = torch.empty(B, device=dev), torch.empty(B, device=dev)
-    call("ader_row_stats", ptr(rep), ptr(emb), B, Bp, H, N, ptr(ncol), ptr(spart), ptr(lse), ptr(entropy), _st())
+    B, H, ws, _, _ = _topk_prologue("row_stats", rep, emb, None, N, 1, 1)
+    lse, entropy = torch.empty(B, device=rep.device), torch.empty(B, device=rep.device)
+    L.row_stats(ws, _st(), rep, ptr(emb), H, N, lse, entropy)
     return lse, entropy
 
 

@@ -21,9 +21,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ader_amd._lib import call, ptr  # noqa: E402
+from ader_amd._lib import ptr  # noqa: E402
 from ader_amd.data import DataLoader, Evaluator, Sampler  # noqa: E402
 from ader_amd.engine import Engine  # noqa: E402
+from ader_amd.engine import infer_launch as L  # noqa: E402
+from ader_amd.engine.infer import RANK_X3_CAND_PER_ROW  # noqa: E402
 from ader_amd.main import ITEM_NUM  # noqa: E402
 
 PEAK_F32_MFMA, PEAK_BF16_MFMA = 157.3e12, 2.5e15
@@ -63,28 +65,18 @@ def ev_time(fn):
     return a.elapsed_time(b) * 1e-3, r
 
 
-def rank_launches(eng, rep, pos, N, dtype, emax=None):
+def rank_launches(eng, rep, pos, N, dtype):
     """The rank launches of Engine.rank_targets alone, on precomputed representations (no forward, no copy back)."""
-    st = torch.cuda.current_stream().cuda_stream
+    ws, st, emb = L.fresh(rep.device), torch.cuda.current_stream().cuda_stream, ptr(eng.param("emb"))
     n = rep.shape[0]
     if dtype == "x3":
-        call("ader_rank_emax", eng._pp["emb"], eng.item_num, eng.H, N, ptr(emax), st)
+        emax = L.rank_emax(ws, st, emb, eng.item_num, eng.H, N)
     for s in range(0, n, eng.MAX_ROWS):
         e = min(n, s + eng.MAX_ROWS)
-        B = e - s
-        Bp = (B + 127) // 128 * 128 if dtype == "x3" else (B + 63) // 64 * 64
-        tgt = eng.buf("be_tgt", (Bp,), torch.int32)
-        tgt.zero_()
-        tgt[:B] = pos[s:e]
-        ncol, tl, rk = eng._ncol_all(Bp, B, N), eng.buf("be_tl", (Bp,)), eng.buf("be_rk", (Bp,), torch.int32)
         if dtype == "x3":
-            cap = 64 * Bp
-            hi, lo = eng.buf("be_hi", (Bp * 168,), torch.bfloat16), eng.buf("be_lo", (Bp * 168,), torch.bfloat16)
-            call("ader_rank_targets_x3", ptr(rep[s:e]), eng._pp["emb"], eng.item_num, B, Bp, eng.H, N, ptr(tgt), ptr(ncol), ptr(hi), ptr(lo),
-                 ptr(tl), ptr(eng.buf("be_delta", (Bp,))), ptr(emax), ptr(eng.buf("be_cand", (3 * cap,), torch.int32)), cap,
-                 ptr(eng.buf("be_diag", (2,), torch.int32)), ptr(rk), st)
+            L.rank_targets_x3(ws, st, rep[s:e], emb, eng.item_num, eng.H, N, pos[s:e], emax, RANK_X3_CAND_PER_ROW * L.pad_rows(e - s, 128))
         else:
-            call("ader_rank_targets", ptr(rep[s:e]), eng._pp["emb"], B, Bp, eng.H, N, ptr(tgt), ptr(ncol), ptr(tl), ptr(rk), st)
+            L.rank_targets(ws, st, rep[s:e], emb, eng.H, N, pos[s:e])
 
 
 def measure(name, eng, seq, pos, N, reps, warmup):
@@ -92,12 +84,11 @@ def measure(name, eng, seq, pos, N, reps, warmup):
     seq_d = torch.from_numpy(seq).to(eng.device)
     pos_d = torch.from_numpy(pos).to(eng.device)
     rep = eng.encode(seq_d)
-    emax = torch.zeros(1, device=eng.device)
     whole, launches, fwd, ranks, stats = {"f32": [], "x3": []}, {"f32": [], "x3": []}, [], {}, None
     for it in range(warmup + reps):
         for dt in ("f32", "x3"):                                   # alternating inside every repetition
             t, r = ev_time(lambda: eng.rank_targets(seq_d, pos_d, N, dtype=dt))
-            tl, _ = ev_time(lambda: rank_launches(eng, rep, pos_d, N, dt, emax))
+            tl, _ = ev_time(lambda: rank_launches(eng, rep, pos_d, N, dt))
             if it >= warmup:
                 whole[dt].append(t)
                 launches[dt].append(tl)
@@ -127,18 +118,11 @@ def measure(name, eng, seq, pos, N, reps, warmup):
 
 def among_launches(eng, rep, pos, seq, N, cand, exclude):
     """The rank launches of Engine.rank_targets_among alone, on precomputed representations (no forward, no copy back)."""
-    st = torch.cuda.current_stream().cuda_stream
-    n, M = rep.shape[0], cand.shape[0]
+    ws, st, emb = L.fresh(rep.device), torch.cuda.current_stream().cuda_stream, ptr(eng.param("emb"))
+    n = rep.shape[0]
     for s in range(0, n, eng.MAX_ROWS):
         e = min(n, s + eng.MAX_ROWS)
-        B = e - s
-        Bp = (B + 63) // 64 * 64
-        tgt = eng.buf("be_tgt", (Bp,), torch.int32)
-        tgt.zero_()
-        tgt[:B] = pos[s:e]
-        call("ader_rank_targets_cand", ptr(rep[s:e]), eng._pp["emb"], B, Bp, eng.H, N, ptr(tgt), ptr(eng._ncol_all(Bp, B, N)), ptr(cand), M,
-             ptr(seq[s:e]) if exclude else None, seq.shape[1], ptr(eng.buf("be_tl", (Bp,))), ptr(eng.buf("be_rk", (Bp,), torch.int32)),
-             ptr(eng.status), st)
+        L.rank_targets_cand(ws, st, rep[s:e], emb, eng.H, N, pos[s:e], cand, seq[s:e] if exclude else None, eng.status)
 
 
 def torch_among(eng, seq, pos, N, cand, exclude):
