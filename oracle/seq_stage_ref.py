@@ -579,10 +579,14 @@ def dev_outputs(cap, stage, l, L, names):
     return out
 
 
-def check_capture(cap, cfg, prm, form, emu_arith=None, raise_=True):
+def check_capture(cap, cfg, prm, form, emu_arith=None, raise_=True, forward_only=False):
     """check_stage on every stage of a capture.  Returns [(stage, block, name, error, emulated error, bound, worst)] (raise_=False:
-    and the complaints, instead of raising them)."""
+    and the complaints, instead of raising them).  forward_only: the capture of a forward(save=True) -- it holds no backward tensor,
+    and only the stages embed .. lnf (FWD_STAGES) are restated and judged, in the same measure and bound."""
+    if forward_only:
+        cap = {k: v for k, v in cap.items() if k != "drep"}          # (run_stages stops behind lnf without it)
     ref = run_stages(Arith("f64"), cfg, prm, cap)
+    assert not forward_only or {st for st, _ in ref} == set(FWD_STAGES)
     emu = run_stages(emu_arith, cfg, prm, cap) if emu_arith is not None else emulate_stage(form, cfg, prm, cap)
     rows, bad = [], []
     for (stage, l), r in ref.items():

@@ -67,6 +67,52 @@ def _make_engine(case, form, heads, window):
     return eng
 
 
+def plan_of(A):
+    """The device plan of a packed forward's saved activations as numpy arrays (None: not packed)."""
+    pk = A.get("pack")
+    if pk is None:
+        return None
+    return {k: pk[k].cpu().numpy() for k in ("hdr", "trows", "ids", "lpos", "gpos", "info", "srow0", "slen")}
+
+
+def capture_forward(eng, A, form, B, heads, plan):
+    """The forward half of a capture: the saved activations A of one forward(save=True) (Engine._act) in the canonical layout of
+    oracle/seq_stage_ref.py -> (cap, raw); raw: the tile-ordered (packed) or row-ordered device tensors of the K / V side and of the
+    unpruned blocks.  Used by this file's _run and by tests/test_gpu_logits_anchor.py (eval-mode forward)."""
+    T, L = eng.T, eng.L
+    packed = plan is not None
+    tiles = "tiles" if packed else "rows"
+    rows = lambda t, lay: S.rows_to_canonical(_host(t), lay, B, T, plan)      # noqa: E731
+    cap, raw = {}, {}
+    for l in range(L):
+        Sd = A[l]
+        pruned = Sd["pruned"]
+        assert pruned == (l == L - 1)
+        ql = "compact" if pruned else tiles
+        for k in ("x", "K", "V", "kmask"):
+            cap["%s%d" % (k, l)] = rows(Sd[k], tiles)
+            raw["%s%d" % (k, l)] = Sd[k]
+        for k in ("q_in", "mean1", "std1", "qmask", "Q", "x1", "y", "mean2", "std2", "h1d"):
+            cap["%s%d" % (k, l)] = rows(Sd[k], ql)
+            if not pruned:
+                raw["%s%d" % (k, l)] = Sd[k]
+        if pruned:
+            play = "last"
+        elif packed:
+            play = "tiles"
+        elif form == "fused" or (form == "perop_x3" and eng.attn_x3):
+            play = "kq"
+        else:
+            play = "qk"
+        cap["P%d" % l] = S.p_to_canonical(_host(Sd["P"]), play, B, T, heads, plan)
+        if play == "tiles":
+            raw["P%d" % l] = Sd["P"]
+    cap["x%d" % L] = rows(A["xL"], "compact")
+    for k in ("rep", "meanf", "stdf"):
+        cap[k] = _host(A[k])
+    return cap, raw
+
+
 def _run(case, form, heads, window, monkeypatch):
     """One loss_and_grad; returns (eng, cfg, prm, cap, plan, raw): the capture in the canonical layout and, for the packed form, the
     device plan and the raw tile-ordered tensors."""
@@ -100,36 +146,13 @@ def _run(case, form, heads, window, monkeypatch):
     monkeypatch.setattr(FW, "call", orig)
     A, ws = eng._act, eng._ws
     assert (A.get("pack") is not None) == packed
-    plan = None
-    if packed:
-        pk = A["pack"]
-        plan = {k: pk[k].cpu().numpy() for k in ("hdr", "trows", "ids", "lpos", "gpos", "info", "srow0", "slen")}
+    plan = plan_of(A)
+    cap, raw = capture_forward(eng, A, form, B, heads, plan)
     tiles = "tiles" if packed else "rows"
     rows = lambda t, lay: S.rows_to_canonical(_host(t), lay, B, T, plan)      # noqa: E731
-    cap, raw = {}, {}
     for l in range(L):
-        Sd = A[l]
-        pruned = Sd["pruned"]
-        assert pruned == (l == L - 1)
+        pruned = A[l]["pruned"]
         ql = "compact" if pruned else tiles
-        for k in ("x", "K", "V", "kmask"):
-            cap["%s%d" % (k, l)] = rows(Sd[k], tiles)
-            raw["%s%d" % (k, l)] = Sd[k]
-        for k in ("q_in", "mean1", "std1", "qmask", "Q", "x1", "y", "mean2", "std2", "h1d"):
-            cap["%s%d" % (k, l)] = rows(Sd[k], ql)
-            if not pruned:
-                raw["%s%d" % (k, l)] = Sd[k]
-        if pruned:
-            play = "last"
-        elif packed:
-            play = "tiles"
-        elif form == "fused" or (form == "perop_x3" and eng.attn_x3):
-            play = "kq"
-        else:
-            play = "qk"
-        cap["P%d" % l] = S.p_to_canonical(_host(Sd["P"]), play, B, T, heads, plan)
-        if play == "tiles":
-            raw["P%d" % l] = Sd["P"]
         # backward tensors between the chains
         if packed:
             nm = lambda s: "pbw_%s%d%s" % (s, l, "L" if pruned else "")      # noqa: E731
@@ -146,9 +169,6 @@ def _run(case, form, heads, window, monkeypatch):
         for k in ("dK", "dV"):
             cap["%s%d" % (k, l)] = rows(ws[kv(k)], tiles)
             raw["%s%d" % (k, l)] = ws[kv(k)]
-    cap["x%d" % L] = rows(A["xL"], "compact")
-    for k in ("rep", "meanf", "stdf"):
-        cap[k] = _host(A[k])
     cap["drep"] = _host(ws["drep"])
     cap["dxo%d" % (L - 1)] = rows(ws["dx_L"], "compact")
     # gradient of block l's input = of block l-1's output: blocks L-1, L-2, .. write the ping-pong buffers b, a, b, ..
@@ -196,6 +216,46 @@ def expected_launches(case, form, heads):
     return must, never
 
 
+def packed_exact_complaints(label, plan, raw, seq, T, window, B, split=None):
+    """The exact statements about a packed forward (and whatever backward tensors raw holds): the device plan is numpy_plan of
+    seq [B, T]; no tile row at or beyond its tile's row count and no saved probability outside its session's causal block was written.
+    raw is consumed.  -> complaints."""
+    complaints = []
+    sp = split
+    ref_plan = numpy_plan(seq, T, window, sp["row0"] if sp else 0, sp["n_train"] if sp else -1, sp["row0_ex"] if sp else 0)
+    nt = int(ref_plan["hdr"][0])
+    ok = np.array_equal(plan["hdr"][:4], ref_plan["hdr"]) and np.array_equal(plan["trows"][:nt], ref_plan["tile_rows"])
+    ok = ok and np.array_equal(plan["srow0"], ref_plan["srow0"]) and np.array_equal(plan["slen"], ref_plan["slen"])
+    used = ref_plan["ids"] >= 0
+    for k in ("ids", "lpos", "gpos", "info"):
+        ok = ok and np.array_equal(plan[k][:nt * 64][used].astype(np.int64), ref_plan[k][used])
+    if not ok:
+        complaints.append("%s device plan differs from numpy_plan" % label)
+    # rows at or beyond a tile's row count: allocated zeroed, never written
+    tr = np.zeros(B, dtype=np.int64)
+    tr[:nt] = ref_plan["tile_rows"]
+    beyond = torch.from_numpy((np.arange(64)[None, :] >= tr[:, None]).reshape(-1))
+    dirty = []
+    # ... and of the saved probabilities [tile][key][query] everything but a session's own causal block
+    own = torch.zeros(B, 64, 64, dtype=torch.bool)
+    for b in range(B):
+        u, r0 = divmod(int(ref_plan["srow0"][b]), 64)
+        n = int(ref_plan["slen"][b])
+        own[u, r0:r0 + n, r0:r0 + n] = torch.triu(torch.ones(n, n, dtype=torch.bool))       # key <= query
+    for k in [k for k in raw if k.startswith("P")]:
+        Pt = _host(raw.pop(k)).reshape(B, 64, 64).view(torch.int32)
+        if bool((Pt[~own] != 0).any()):
+            complaints.append("%s %s: a probability outside its session's causal block was written" % (label, k))
+    for k, t in raw.items():
+        t = _host(t) if t.is_cuda else t
+        t2 = t.reshape(B * 64, -1).contiguous().view(torch.int32)
+        if bool((t2[beyond] != 0).any()):
+            dirty.append(k)
+    if dirty:
+        complaints.append("%s tile rows beyond the tile's row count were written: %s" % (label, ", ".join(sorted(dirty))))
+    return complaints
+
+
 @pytest.mark.parametrize("case,form,heads,window", RUNS, ids=RUN_IDS)
 def test_every_stage_matches_its_float64_restatement(case, form, heads, window, monkeypatch):
     eng, batch, cfg, prm, cap, plan, raw, launched = _run(case, form, heads, window, monkeypatch)
@@ -238,36 +298,5 @@ def test_every_stage_matches_its_float64_restatement(case, form, heads, window, 
     if not (bool((demb[0] == 0).all()) and bool((demb[N + 1:] == 0).all())):
         complaints.append("%s table gradient: row 0 or a row beyond max_item is not zero" % label)
     if plan is not None:
-        sp = case["split"]
-        ref_plan = numpy_plan(batch["seq"], T, window, sp["row0"] if sp else 0, sp["n_train"] if sp else -1, sp["row0_ex"] if sp else 0)
-        nt = int(ref_plan["hdr"][0])
-        ok = np.array_equal(plan["hdr"][:4], ref_plan["hdr"]) and np.array_equal(plan["trows"][:nt], ref_plan["tile_rows"])
-        ok = ok and np.array_equal(plan["srow0"], ref_plan["srow0"]) and np.array_equal(plan["slen"], ref_plan["slen"])
-        used = ref_plan["ids"] >= 0
-        for k in ("ids", "lpos", "gpos", "info"):
-            ok = ok and np.array_equal(plan[k][:nt * 64][used].astype(np.int64), ref_plan[k][used])
-        if not ok:
-            complaints.append("%s device plan differs from numpy_plan" % label)
-        # rows at or beyond a tile's row count: allocated zeroed, never written
-        tr = np.zeros(B, dtype=np.int64)
-        tr[:nt] = ref_plan["tile_rows"]
-        beyond = torch.from_numpy((np.arange(64)[None, :] >= tr[:, None]).reshape(-1))
-        dirty = []
-        # ... and of the saved probabilities [tile][key][query] everything but a session's own causal block
-        own = torch.zeros(B, 64, 64, dtype=torch.bool)
-        for b in range(B):
-            u, r0 = divmod(int(ref_plan["srow0"][b]), 64)
-            n = int(ref_plan["slen"][b])
-            own[u, r0:r0 + n, r0:r0 + n] = torch.triu(torch.ones(n, n, dtype=torch.bool))       # key <= query
-        for k in [k for k in raw if k.startswith("P")]:
-            Pt = _host(raw.pop(k)).reshape(B, 64, 64).view(torch.int32)
-            if bool((Pt[~own] != 0).any()):
-                complaints.append("%s %s: a probability outside its session's causal block was written" % (label, k))
-        for k, t in raw.items():
-            t = _host(t) if t.is_cuda else t
-            t2 = t.reshape(B * 64, -1).contiguous().view(torch.int32)
-            if bool((t2[beyond] != 0).any()):
-                dirty.append(k)
-        if dirty:
-            complaints.append("%s tile rows beyond the tile's row count were written: %s" % (label, ", ".join(sorted(dirty))))
+        complaints += packed_exact_complaints(label, plan, raw, batch["seq"], T, window, B, case["split"])
     assert not complaints, "\n".join(complaints)
